@@ -13,16 +13,25 @@ the 256 MiB Infinity Cache and the L2s) followed by ONE SpMV launch, so the
 exactly K steps captured in one HIP graph and replayed between a barrier +
 synchronize on both sides; a graph of K flushes alone is timed the same
 way, and the SpMV's share of a step is (span of K x (flush + SpMV) - span
-of K x flush) / K, HIP events on the launch stream, max over ranks.  A
-rocprofv3 kernel trace of the same kernel, cold (tools/cant_single.py, a
-child process started before this process touches the GPU: every format
-at N=1, the headline format on every rank's GPU at N>1, beside the
-stream-probe ceiling of the same bytes), is reported beside it as
-corroboration (roofline.kernel_ms_trace).  value = N x bytes_alg / (that
-in-process cold SpMV time) = the whole job's throughput of replicated
-configs[1] steps (weak scaling: one matrix per GPU, no collective);
-ms_per_step = that SpMV time; the timed region's wall clock (flushes
-included) is `timed_region`.
+of K x flush) / K, HIP events on the launch stream, max over ranks.
+value = N x bytes_alg / (that in-process cold SpMV time) = the whole job's
+throughput of replicated configs[1] steps (weak scaling: one matrix per
+GPU, no collective); ms_per_step = that SpMV time; the timed region's wall
+clock (flushes included) is `timed_region`.
+
+A plain run (`bench.py --gpus N --steps K --warmup W`) does only that: it
+sets up, warms up, times the K steps, writes y with `--dump-outputs DIR`
+and prints the line.  The next two paragraphs are measured with `--full`
+only (their records are null in a plain run's line); a leg's own switch
+set to `yes` turns that leg on without `--full`.
+
+`--full`: a rocprofv3 kernel trace of the same kernel, cold
+(tools/cant_single.py, a child process started before this process
+touches the GPU: every format at N=1, the headline format on every rank's
+GPU at N>1, beside the stream-probe ceiling of the same bytes), is
+reported beside the headline as corroboration (roofline.kernel_ms_trace);
+the other cold state, SELL-C-sigma on the single matrix (`sell_single`)
+and the CPU baselines (`cpu_baseline`) likewise.
 
 At N=1 also `batch`: ONE launch over 32 cant-like matrices stacked
 block-diagonally (1.58 GB, 6x the Infinity Cache, streamed from HBM; the
@@ -90,21 +99,31 @@ def parse():
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=100)
     p.add_argument("--warmup", type=int, default=10)
+    p.add_argument("--full", action="store_true",
+                   help="also everything beside the headline: the rocprofv3 trace child, the other cold state, SELL on "
+                        "the single matrix, the 32-copy batch and every format on it, the CPU baselines, rmat_strong "
+                        "and banded_strong (every `auto` below means: with --full).  Without it a run sets up, warms "
+                        "up, times the --steps steps and prints the line")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed steps, write what the timed path's last step computed (this rank's y) as "
+                        "DIR/y.npy (float64; rank r > 0: y_rank<r>.npy); above 64 MB a fixed, seeded sample of it")
     p.add_argument("--format", default="csr", choices=sa.ALL_FORMATS)
     p.add_argument("--copies", type=int, default=32, help="cant-like copies per GPU (batch)")
     p.add_argument("--workload", default="cant", choices=["cant", "batch", "cantlike", "rmat", "banded"],
                    help="cant (default: ONE cant-like matrix per GPU, cold, configs[1]/[2]); batch (= cantlike: "
                         "the 32-copy block-diagonal batch); rmat (configs[3]); banded (configs[4])")
     p.add_argument("--batch", default="auto", choices=["auto", "yes", "no"],
-                   help="with --workload cant, also time the 32-copy batch and every format on it (auto: N=1)")
+                   help="with --workload cant, also time the 32-copy batch and every format on it (auto: with --full "
+                        "at N=1)")
     p.add_argument("--banded-rows", type=int, default=100_000_000)
     p.add_argument("--per-format", default="auto", choices=["auto", "yes", "no"],
-                   help="also measure the other formats (default: at N=1 only)")
+                   help="also measure the other formats (auto: with --full at N=1)")
     p.add_argument("--single", default="auto", choices=["auto", "yes", "no"],
                    help="cant_single: ONE cant-like matrix, cold and warm, from a rocprofv3 kernel trace of a "
-                        "child process (auto, with --workload cant: every format at N=1, the headline format "
-                        "on every rank at N>1)")
-    p.add_argument("--cpu-seconds", type=float, default=10.0, help="CPU baseline budget (0: skip)")
+                        "child process (auto: with --full and --workload cant, every format at N=1, the "
+                        "headline format on every rank at N>1)")
+    p.add_argument("--cpu-seconds", type=float, default=None,
+                   help="CPU baseline budget (0: skip; default: 10 with --full, else 0)")
     p.add_argument("--lanes", type=int, default=0)
     p.add_argument("--variant", type=int, default=0, help="CSR kernel variant (0 auto, 1 direct, 2 staged)")
     p.add_argument("--ki", type=int, default=0, help="k-interleave (0: format default, ELL 2, SELL 1)")
@@ -118,10 +137,10 @@ def parse():
     p.add_argument("--share-gpu", action="store_true", help="all ranks on cuda:0 (rehearsal only)")
     p.add_argument("--rmat-strong", default="auto", choices=["auto", "yes", "no"],
                    help="also time CSR on the R-MAT 1e7/1e8 row-sharded over all ranks (strong scaling, "
-                        "north-star sweep; auto: with the default workload)")
+                        "north-star sweep; auto: with --full and the default workload)")
     p.add_argument("--banded-strong", default="auto", choices=["auto", "yes", "no"],
                    help="also time CSR and SELL on the banded 1e8-row / 1.6e9-entry matrix row-sharded over all "
-                        "ranks (configs[4], generated on device; auto: with the default workload)")
+                        "ranks (configs[4], generated on device; auto: with --full and the default workload)")
     p.add_argument("--cold-flush", default="read", choices=["read", "write"],
                    help="headline cold state: 512 MiB READ (clean lines, default) or WRITTEN before every SpMV; "
                         "the other is timed beside it")
@@ -134,10 +153,10 @@ def parse():
                         "replicated in that layout (auto: yes); no = the per-run hot-column table instead")
     p.add_argument("--rmat-per-format", default="auto", choices=["auto", "yes", "no"],
                    help="with rmat_strong at N = 1: every format on the whole R-MAT (configs[3]), cold and warm, "
-                        "beside the gather ceiling of its column sequence")
+                        "beside the gather ceiling of its column sequence (auto: with --full)")
     p.add_argument("--sell-single", default="auto", choices=["auto", "yes", "no"],
                    help="with --workload cant: also SELL-C-sigma on the single matrix (configs[2]) by the "
-                        "headline's in-process method (auto: yes)")
+                        "headline's in-process method (auto: with --full)")
     p.add_argument("--rmat-rows", type=int, default=10_000_000, help="R-MAT rows (configs[3]: 1e7)")
     p.add_argument("--rmat-nnz", type=int, default=100_000_000, help="R-MAT entries (configs[3]: 1e8)")
     p.add_argument("--recuts", type=int, default=None, help="profile-guided R-MAT re-cuts (default RMAT_RECUTS)")
@@ -606,7 +625,7 @@ def cant_single_rocprof(formats=None, local=None, flush_mode="read"):
     return res
 
 
-def single_cold(args, torch, dev, rank, world, dist, cdev, prof, fmt=None):
+def single_cold(args, torch, dev, rank, world, dist, cdev, prof, fmt=None, extras=False):
     """The headline (BASELINE.json configs[1]; configs[2] with --format
     sell): ONE cant-like matrix on this rank's GPU, cold.  A step = 512 MiB
     flush + one SpMV launch.  W untimed warm-up steps; then the K steps are
@@ -619,7 +638,9 @@ def single_cold(args, torch, dev, rank, world, dist, cdev, prof, fmt=None):
     ranks: the headline.  The rocprofv3 trace median and mean of the same
     kernel cold (`prof`, this rank's cant_single child) go beside it.
     fmt: the format (default --format; "sell" for the sell_single record,
-    BASELINE.json configs[2])."""
+    BASELINE.json configs[2]).  extras (--full): also the other cold state
+    and the empty-kernel node, each by timed regions of its own.  The
+    record's "y" is the host copy of y as the last timed step left it."""
     fmt = fmt or args.format
     m = sa.gen_cantlike(0, 1)
     b = sa.bytes_alg(m.n_rows, m.n_cols, m.nnz)
@@ -707,11 +728,12 @@ def single_cold(args, torch, dev, rank, world, dist, cdev, prof, fmt=None):
     K = args.steps
     reps = 1 if args.profile else INPROC_REPS
     wall, inproc, diffs, flush_spans = inprocess(step, flush, K, reps)
-    # the other cold state beside it (not the headline; not in --profile runs,
-    # whose PMC passes average every launch of the kernel)
+    y_host = y.cpu().numpy()
+    # the other cold state beside it (--full; not the headline; not in
+    # --profile runs, whose PMC passes average every launch of the kernel)
     inproc_other = None
     node_ms = None
-    if not args.profile:
+    if extras and not args.profile:
         _, inproc_other, _, _ = inprocess(lambda: (other(), dm.run(x, y)), other, K, reps)
         # what the estimator charges ANY kernel node: the same F B F ... F
         # measurement of an empty one-workgroup kernel (tools/probe.hip
@@ -719,7 +741,7 @@ def single_cold(args, torch, dev, rank, world, dist, cdev, prof, fmt=None):
         # which the rocprofv3 kernel time does not contain
         _, node_ms, _, _ = inprocess(lambda: (flush(), probe.spmv_probe_tag(1, torch.cuda.current_stream().cuda_stream)),
                                      flush, K, reps)
-    bad, first = sa.check(m, xh, y.cpu().numpy())
+    bad, first = sa.check(m, xh, y_host)
     all_ok(dist, cdev, torch, bad == 0, f"cant-like single matrix, row {first}", rank)
 
     # the headline is the in-process figure: the timed region's
@@ -775,7 +797,7 @@ def single_cold(args, torch, dev, rank, world, dist, cdev, prof, fmt=None):
                                      round(inproc_other, 5) if inproc_other else None},
                              "cold_spmv_ms_rocprof_rank0": traced,
                              "cold_ms_per_rank": [round(v, 5) for v in per_rank]},
-            "parity_ok": True,
+            "parity_ok": True, "y": y_host,
             "check": "all 62,451 rows of y against the host check_result rule (1e-6 relative), every rank"}
 
 
@@ -1000,7 +1022,7 @@ def rmat_strong(args, torch, dev, rank, world, dist, cdev):
                    "bytes": 20 * n}
         del od, x0, xp
     per_format = gather_ceiling = None
-    if rank == 0 and world == 1 and args.rmat_per_format != "no":
+    if rank == 0 and world == 1 and on(args.rmat_per_format, args.full):
         loc = rows_of(0, n)
         gather_ceiling = rmat_gather_ceiling(torch, dev, loc, x, b_total)
         per_format = rmat_per_format(args, torch, dev, loc, x, full, hot, b_total, gather_ceiling)
@@ -1280,10 +1302,36 @@ def per_format_leg(args, torch, dev, m, x, y, nnz, bytes_step, hot=None):
     return per_format
 
 
+DUMP_MAX_BYTES = 64 << 20  # --dump-outputs writes at most this much
+
+
+def dump_outputs(out_dir, rank, world, y):
+    """--dump-outputs: this rank's y (host float64, as the last timed step
+    left it) as DIR/y.npy (rank r > 0: y_rank<r>.npy).  Above this rank's
+    share of DUMP_MAX_BYTES the entries at a fixed, seeded, sorted sample of
+    indices instead (the same indices every run, so two builds are compared
+    entry for entry)."""
+    y = np.ascontiguousarray(y, dtype=np.float64)
+    keep = DUMP_MAX_BYTES // 8 // world
+    if y.size > keep:
+        y = y[np.unique(np.random.default_rng(0).integers(0, y.size, size=keep))]
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    np.save(d / ("y.npy" if rank == 0 else f"y_rank{rank}.npy"), y)
+
+
+def on(switch, full):
+    """An auto / yes / no switch of a leg beside the headline: auto = --full."""
+    return switch == "yes" or (switch == "auto" and full)
+
+
 def main():
     args = parse()
     if args.workload == "cantlike":
         args.workload = "batch"
+    full = args.full
+    if args.cpu_seconds is None:
+        args.cpu_seconds = 10.0 if full else 0.0
     if launch.needs_spawn(args.gpus):
         # `--gpus N` from a plain process: N ranks in a child
         # torch.distributed.run job; this process never touches the GPU
@@ -1294,11 +1342,11 @@ def main():
     local = int(os.environ.get("LOCAL_RANK", "0"))
     if world != args.gpus:
         print(f"warning: --gpus {args.gpus} but WORLD_SIZE={world}; using WORLD_SIZE", file=sys.stderr)
-    # the single-matrix kernel trace comes from a profiled CHILD process,
-    # run before this process initialises the GPU (every format at N=1; the
-    # headline format on every rank's own GPU at N>1)
+    # the single-matrix kernel trace (--full) comes from a profiled CHILD
+    # process, run before this process initialises the GPU (every format at
+    # N=1; the headline format on every rank's own GPU at N>1)
     prof = None
-    if not args.profile and args.workload == "cant" and args.single != "no":
+    if not args.profile and args.workload == "cant" and on(args.single, full):
         if world == 1:
             prof = cant_single_rocprof(flush_mode=args.cold_flush)
         else:
@@ -1337,11 +1385,13 @@ def main():
 
     batch = per_format = cpu = allgather = sell_single = None
     if args.workload == "cant":
-        s = single_cold(args, torch, dev, rank, world, dist, cdev, prof)
-        if args.sell_single != "no" and args.format != "sell":
+        s = single_cold(args, torch, dev, rank, world, dist, cdev, prof, extras=full)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, rank, world, s["y"])
+        if on(args.sell_single, full) and args.format != "sell":
             # BASELINE.json configs[2] (the north star's >= 60 % target) by the
             # headline's own in-process method, its trace beside it
-            sv = single_cold(args, torch, dev, rank, world, dist, cdev, prof, fmt="sell")
+            sv = single_cold(args, torch, dev, rank, world, dist, cdev, prof, fmt="sell", extras=full)
             sg = sv["bytes"] / (sv["cold_ms"] * 1e-3) * 1e-9
             sell_single = {"workload": "SELL-C-sigma (C = 64, sigma = 1024) on ONE cant-like matrix, cold "
                                        "(BASELINE.json configs[2])",
@@ -1386,7 +1436,7 @@ def main():
                                   "exchange (weak scaling); the strong-scaling evidence is rmat_strong."
                                   "speedup_cold / speedup_warm")
         launch_desc = s["timed_region"]["what"]
-        do_batch = args.batch == "yes" or (args.batch == "auto" and world == 1)
+        do_batch = args.batch == "yes" or (args.batch == "auto" and world == 1 and full)
         if do_batch:
             w, b_ms, b_kern, b_roof = batch_leg(args, torch, dev, rank, world, dist, cdev)
             batch = {"workload": w["config"]["workload"], "copies_per_gpu": args.copies,
@@ -1421,6 +1471,8 @@ def main():
                        if GRAPH.get("last") == "hip-graph" else "eager launches, one HIP event after each")
         bad = w["check"]()
         all_ok(dist, cdev, torch, bad is None, str(bad), rank)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, rank, world, y[:n_rows].cpu().numpy())
         wall_t = torch.tensor([wall], dtype=torch.float64, device=cdev)
         kern_t = torch.tensor([float(np.mean(kern))], dtype=torch.float64, device=cdev)
         if dist is not None:
@@ -1462,7 +1514,7 @@ def main():
                     "traffic": traffic_for(args.format, bytes_step, kname),
                     "kernel": kname, "kernel_ms": round(kern_ms, 5), "bytes_alg_per_launch": bytes_step}
 
-        do_pf = rank == 0 and (args.per_format == "yes" or (args.per_format == "auto" and world == 1))
+        do_pf = rank == 0 and (args.per_format == "yes" or (args.per_format == "auto" and world == 1 and full))
         if do_pf and args.workload in ("rmat", "batch"):
             m = w["loc"] if args.workload == "rmat" else w["m"]
             del dm, w["dm"]
@@ -1483,11 +1535,11 @@ def main():
 
     rstrong = None
     default_wl = args.workload in ("cant", "batch")
-    if args.rmat_strong == "yes" or (args.rmat_strong == "auto" and default_wl):
+    if args.rmat_strong == "yes" or (args.rmat_strong == "auto" and default_wl and full):
         torch.cuda.empty_cache()
         rstrong = rmat_strong(args, torch, dev, rank, world, dist, cdev)
     bstrong = None
-    if args.banded_strong == "yes" or (args.banded_strong == "auto" and default_wl):
+    if args.banded_strong == "yes" or (args.banded_strong == "auto" and default_wl and full):
         bstrong = banded_strong(args, torch, dev, rank, world, dist, cdev)
 
     if rank == 0:

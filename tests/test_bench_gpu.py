@@ -51,6 +51,35 @@ def test_bench_one_gpu_line():
     assert abs(d["value"] - expect) <= 0.005 * expect  # ms_per_step is printed rounded to 10 ns
 
 
+def test_bench_plain_run_is_lean_and_dumps_y(tmp_path):
+    """A plain run (no --full, no leg switched on) times the headline only:
+    every other record of the line is null; --dump-outputs writes the y of
+    the last timed step (float64, one entry per row, the ramp x's products:
+    finite and not all zero)."""
+    import numpy as np
+
+    r = subprocess.run([sys.executable, str(REPO / "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2",
+                        "--dump-outputs", str(tmp_path / "out")], capture_output=True, text=True, timeout=300,
+                       env=_env(), cwd=str(REPO))
+    assert r.returncode == 0, r.stderr[-3000:]
+    d = _line(r.stdout)
+    assert d["steps"] == 5 and d["warmup"] == 2 and d["ms_per_step"] > 0 and d["higher_is_better"] is True
+    for leg in ("cpu_baseline", "sell_single", "rmat_per_format", "cant_single", "batch", "per_format",
+                "rmat_strong", "strong_scaling", "banded_strong"):
+        assert d[leg] is None, leg
+    assert d["config"]["timed_region"]["empty_kernel_node_ms"] is None
+    assert d["roofline"]["kernel_ms_trace"] is None
+    assert sorted(p.name for p in (tmp_path / "out").iterdir()) == ["y.npy"]
+    y = np.load(tmp_path / "out" / "y.npy")
+    assert y.dtype == np.float64 and y.shape == (d["config"]["rows_rank0"],)
+    assert np.isfinite(y).all() and np.abs(y).max() > 0
+    import spmv_amd as sa
+
+    m = sa.gen_cantlike(0, 1)  # the headline's matrix and x: the dump is that product
+    bad, first = sa.check(m, sa.ramp_x(m.n_cols), y)
+    assert bad == 0, f"dumped y differs from the host rule at row {first}"
+
+
 def test_bench_gpus_2_without_launcher():
     """`python3 bench.py --gpus 2` (the driver's form) measures TWO ranks, and
     the line carries its own strong-scaling evidence: rank 0 times the whole

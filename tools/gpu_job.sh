@@ -54,13 +54,13 @@ for s in "${steps[@]}"; do
     testk) run gpu_tests_k 900 $PYT tests -m gpu -k "${TEST_K:?TEST_K is required}";;
     drivers) run drivers 600 $PYT tests/test_drivers_gpu.py;;
     itertests) run iter_tests 600 $PYT tests/test_iterate_gpu.py;;
-    bench) run "bench${BENCH_TAG:+_$BENCH_TAG}" 900 python bench.py "${bench_args[@]}";;
-    benchrmat) run bench_rmat 600 python bench.py --workload rmat --steps 20;;
-    benchbatch) run bench_batch 600 python bench.py --workload batch --rmat-strong no --banded-strong no;;
+    bench) run "bench${BENCH_TAG:+_$BENCH_TAG}" 900 python bench.py --full "${bench_args[@]}";;
+    benchrmat) run bench_rmat 600 python bench.py --full --workload rmat --steps 20;;
+    benchbatch) run bench_batch 600 python bench.py --full --workload batch --rmat-strong no --banded-strong no;;
     benchbanded) run bench_banded_sell 600 python bench.py --workload banded --format sell --steps 20 &&
                  run bench_banded_csr 600 python bench.py --workload banded --format csr --steps 20;;
-    spawn2) run spawn2 900 python bench.py --gpus 2 --backend gloo --share-gpu --steps 20 --banded-strong no;;
-    rehearse2) run rehearse2 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29511 bench.py --gpus 2 --backend gloo --share-gpu --steps 20;;
+    spawn2) run spawn2 900 python bench.py --full --gpus 2 --backend gloo --share-gpu --steps 20 --banded-strong no;;
+    rehearse2) run rehearse2 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29511 bench.py --full --gpus 2 --backend gloo --share-gpu --steps 20;;
     prof) run prof 900 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof -o run -- python3 bench.py --profile --steps 200;;
     profbatch) run prof_batch 900 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_batch -o run -- python3 bench.py --profile --workload batch --steps 200;;
     single) run cant_single 600 python tools/cant_single.py --json gpurun_out/cant_single.json "${cs_args[@]}";;
