@@ -168,6 +168,45 @@ int spmv_plan_cmrs(spmv_dims d, int32_t h, int64_t n_strips, const int64_t *stri
 /* y = A x on `stream` (NULL = the default stream; the plan's d.stream is
  * used for building only).  x[n_cols], y[n_rows], device pointers.        */
 int spmv_plan_run(const spmv_plan *p, const double *x, double *y, void *stream);
+/* Y = A·X for k vectors stored row-major ("vector index fastest"):
+ * X[c*ldx + j], c < n_cols, j < k;  Y[i*ldy + j], i < n_rows, j < k.
+ * ldx >= k, ldy >= k (leading dimensions in elements), k >= 1.
+ *
+ * The conventions above hold: device pointers, asynchronous on `stream`,
+ * no allocation and no synchronisation inside the call (it can be captured
+ * into a graph), codes of spmv_rc.h, a message in spmv_last_error().
+ *   - Y[i*ldy + j], j < k, is fully overwritten (rows without entries get
+ *     0.0); NO element Y[i*ldy + j] with j >= k is written.
+ *   - NO byte outside X[c*ldx .. c*ldx + k) is read for any c: nothing past
+ *     the end of the last row when ldx == k, and no 16-byte load straddles
+ *     column k-1.
+ *   - X and Y need 8-byte alignment only and any ldx, ldy >= k (odd ones
+ *     too).  16-byte loads and stores of X / Y rows are used only where
+ *     the call has proven them aligned (base address and leading dimension
+ *     both 16-byte compatible); otherwise the 8-byte kernels run.
+ *   - X and Y must not overlap; runs of one plan must be serialised, as for
+ *     spmv_plan_run.
+ *   - The matrix is read once per block of up to 8 vectors, ceil(k/8)
+ *     times.  The kernels exist for 1, 2, 4 and 8 vectors; a block of r
+ *     remaining vectors uses the smallest width >= r, its unused
+ *     accumulator columns load column k-1 again and are never stored.
+ *   - The bits of output column j depend only on the matrix (and the
+ *     plan's format and geometry) and on input column j: not on k, on j's
+ *     place in its block, on ldx / ldy or on the 8- or 16-byte kernels.
+ *     Column j need not equal spmv_plan_run's bits (that path sums in its
+ *     own order); it meets the same 1e-6 per-row criterion.
+ *   - SPMV_OTHER_ERROR with a message, before any device work: NULL plan,
+ *     k < 1, ldx < k or ldy < k, NULL X with entries present, NULL Y with
+ *     rows present, a plan without a multi-vector kernel.
+ * Plans that run: CSR (every path), ELL (both paths), SELL (every path but
+ * SELL16, any C, ki 1 or 2).  The run reads the caller's arrays (never the
+ * plan's hot-renumbered column copy) and gathers X from global memory.
+ * Refused: COO and CMRS (no multi-vector kernel), SELL16 (the plan does not
+ * require the int32 columns to outlive its creation).                      */
+int spmv_plan_run_multi(const spmv_plan *p, int32_t k, const double *X, int64_t ldx,
+                        double *Y, int64_t ldy, void *stream);
+/* 1 when spmv_plan_run_multi can run this plan, else 0 (also for NULL). */
+int spmv_plan_multi_supported(const spmv_plan *p);
 int spmv_plan_get_info(const spmv_plan *p, spmv_plan_info *info);
 /* Frees what the plan allocated (never the caller's arrays). */
 int spmv_plan_destroy(spmv_plan *p);

@@ -270,6 +270,14 @@ int spmv_cpu_coo(int64_t n_rows, int64_t nnz, const int32_t *row,
                  double *y, int threads);
 int spmv_cpu_csr(int64_t n_rows, const int64_t *row_ptr, const int32_t *col,
                  const double *val, const double *x, double *y, int threads);
+/* Y = A X for k >= 1 vectors stored row-major, the layout of
+ * spmv_plan_run_multi (spmv.h): X[c*ldx + j], Y[r*ldy + j], j < k,
+ * ldx >= k, ldy >= k.  Writes Y[r*ldy + j] for j < k only and reads nothing
+ * of X outside [c*ldx, c*ldx + k).  SPMV_OTHER_ERROR for k < 1, a leading
+ * dimension below k or a NULL array that would be read or written.        */
+int spmv_cpu_csr_multi(int64_t n_rows, const int64_t *row_ptr, const int32_t *col,
+                       const double *val, int32_t k, const double *X, int64_t ldx,
+                       double *Y, int64_t ldy);
 int spmv_cpu_ell(int64_t n_rows, int32_t K, int64_t ld, int32_t ki,
                  const int32_t *col, const double *val, const double *x,
                  double *y, int threads);

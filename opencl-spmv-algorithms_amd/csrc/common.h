@@ -101,6 +101,15 @@ int64_t cmrs_tiled_tile_min();
 int launch_carry(int64_t tiles, const int32_t *carry_row, const double *carry_val, double *y,
                  hipStream_t stream);
 
+// multi-vector runs Y = A X (spmm.hip; the contract is spmv_plan_run_multi's,
+// spmv.h): blocks of up to 8 vectors, one pass over the matrix each
+int launch_csr_multi(const spmv_dims &d, int L, const int64_t *row_ptr, const int32_t *col, const double *val,
+                     int32_t k, const double *X, int64_t ldx, double *Y, int64_t ldy);
+// SELL (sell: C, n_slices, slice_ptr, perm) or ELL (K, ld)
+int launch_slot_multi(const spmv_dims &d, bool sell, int32_t ki, int32_t C, int64_t n_slices, const int64_t *slice_ptr,
+                      const int32_t *perm, int32_t K, int64_t ld, const int32_t *col, const double *val, int32_t k,
+                      const double *X, int64_t ldx, double *Y, int64_t ldy);
+
 // ------------------------------------------------------- device helpers
 // Bijective blockIdx remap: blocks b and b+8 are dealt to the same XCD
 // (MI355X_MICROARCH.md §Workgroup dispatch), so give each such group a

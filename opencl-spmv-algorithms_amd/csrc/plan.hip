@@ -801,6 +801,59 @@ int spmv_plan_run(const spmv_plan *p, const double *x, double *y, void *stream)
     return fail_msg(SPMV_OTHER_ERROR, "spmv_plan_run: corrupt plan");
 }
 
+// ------------------------------------------------------ multi-vector run
+// Why a plan has no multi-vector kernel (NULL: it has one).  SELL16: the
+// plan's 16-bit offsets are window-relative and the caller's int32 columns
+// need not outlive plan creation (the binding frees them), so p->col is not
+// read there.
+static const char *multi_refusal(const spmv_plan *p)
+{
+    switch (p->fmt) {
+    case SPMV_FMT_CSR:
+    case SPMV_FMT_ELL:
+        return nullptr;
+    case SPMV_FMT_SELL:
+        return p->path == P_SELL16 ? "spmv_plan_run_multi: SELL16 plans are not supported (the int32 columns are "
+                                     "not kept after plan creation)"
+                                   : nullptr;
+    case SPMV_FMT_COO:
+        return "spmv_plan_run_multi: COO plans have no multi-vector kernel";
+    case SPMV_FMT_CMRS:
+        return "spmv_plan_run_multi: CMRS plans have no multi-vector kernel";
+    }
+    return "spmv_plan_run_multi: corrupt plan";
+}
+
+int spmv_plan_multi_supported(const spmv_plan *p) { return p && !multi_refusal(p) ? 1 : 0; }
+
+int spmv_plan_run_multi(const spmv_plan *p, int32_t k, const double *X, int64_t ldx, double *Y, int64_t ldy,
+                        void *stream)
+{
+    if (!p)
+        return fail_msg(SPMV_OTHER_ERROR, "spmv_plan_run_multi: plan is NULL");
+    if (k < 1)
+        return fail_msg(SPMV_OTHER_ERROR, "spmv_plan_run_multi: k must be at least 1");
+    if (ldx < k || ldy < k)
+        return fail_msg(SPMV_OTHER_ERROR, "spmv_plan_run_multi: ldx and ldy must be at least k");
+    if ((p->d.n_rows > 0 && !Y) || (p->d.nnz > 0 && p->d.n_cols > 0 && !X))
+        return fail_msg(SPMV_OTHER_ERROR, "spmv_plan_run_multi: X or Y is NULL");
+    if (const char *why = multi_refusal(p))
+        return fail_msg(SPMV_OTHER_ERROR, why);
+    spmv_dims d = p->d;
+    d.stream = stream;
+    // the caller's arrays (p->col, never run_col(p): X is gathered by the
+    // original column ids, no hot table and no LDS window)
+    switch (p->fmt) {
+    case SPMV_FMT_CSR:
+        return launch_csr_multi(d, p->lanes, p->ptr, p->col, p->val, k, X, ldx, Y, ldy);
+    case SPMV_FMT_ELL:
+        return launch_slot_multi(d, false, p->ki, 0, 0, nullptr, nullptr, p->K, p->ld, p->col, p->val, k, X, ldx, Y, ldy);
+    default:
+        return launch_slot_multi(d, true, p->ki, p->C, p->n_slices, p->ptr, p->perm, 0, 0, p->col, p->val, k, X, ldx, Y,
+                                 ldy);
+    }
+}
+
 int spmv_plan_get_info(const spmv_plan *p, spmv_plan_info *info)
 {
     if (!p || !info)

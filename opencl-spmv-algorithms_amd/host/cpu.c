@@ -46,6 +46,36 @@ int spmv_cpu_csr(int64_t n_rows, const int64_t *row_ptr, const int32_t *col,
     return SPMV_SUCCESS;
 }
 
+/* Y = A X for k vectors stored row-major (the layout of spmv_plan_run_multi,
+ * spmv.h): Y[r*ldy + j], j < k, is overwritten; nothing is written for
+ * j >= k and nothing of X is read outside [c*ldx, c*ldx + k).  Blocks of 8
+ * vectors share one pass over the row.                                    */
+int spmv_cpu_csr_multi(int64_t n_rows, const int64_t *row_ptr, const int32_t *col,
+                       const double *val, int32_t k, const double *X, int64_t ldx,
+                       double *Y, int64_t ldy)
+{
+    if (n_rows < 0 || k < 1 || ldx < k || ldy < k || !row_ptr || (n_rows > 0 && !Y))
+        return SPMV_OTHER_ERROR;
+    if (n_rows > 0 && row_ptr[n_rows] > row_ptr[0] && (!col || !val || !X))
+        return SPMV_OTHER_ERROR;
+#pragma omp parallel for schedule(static)
+    for (int64_t r = 0; r < n_rows; ++r) {
+        for (int32_t j0 = 0; j0 < k; j0 += 8) {
+            const int32_t w = k - j0 < 8 ? k - j0 : 8;
+            double s[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+            for (int64_t e = row_ptr[r]; e < row_ptr[r + 1]; ++e) {
+                const double v = val[e];
+                const double *xr = X + (int64_t)col[e] * ldx + j0;
+                for (int32_t j = 0; j < w; ++j)
+                    s[j] += v * xr[j];
+            }
+            for (int32_t j = 0; j < w; ++j)
+                Y[r * ldy + j0 + j] = s[j];
+        }
+    }
+    return SPMV_SUCCESS;
+}
+
 int spmv_cpu_ell(int64_t n_rows, int32_t K, int64_t ld, int32_t ki,
                  const int32_t *col, const double *val, const double *x,
                  double *y, int threads)

@@ -116,6 +116,8 @@ HIP_SYMBOLS = {
     "spmv_plan_sell": (ctypes.c_int, [Dims, _c_i32, _c_i32, _c_i32, _c_i64, _vp, _vp, _vp, _vp, _PO, _PP]),
     "spmv_plan_cmrs": (ctypes.c_int, [Dims, _c_i32, _c_i64, _vp, _vp, _vp, _vp, _PO, _PP]),
     "spmv_plan_run": (ctypes.c_int, [_vp, _vp, _vp, _vp]),
+    "spmv_plan_run_multi": (ctypes.c_int, [_vp, _c_i32, _vp, _c_i64, _vp, _c_i64, _vp]),
+    "spmv_plan_multi_supported": (ctypes.c_int, [_vp]),
     "spmv_plan_get_info": (ctypes.c_int, [_vp, ctypes.POINTER(PlanInfo)]),
     "spmv_plan_destroy": (ctypes.c_int, [_vp]),
     "spmv_set_option": (ctypes.c_int, [ctypes.c_int, ctypes.c_int]),
@@ -295,6 +297,7 @@ HOST_SYMBOLS = {
     "spmv_csrg_fill": (ctypes.c_int, [_c_i64, _vp, _vp, _vp, _c_i32, _vp, _vp, _vp, _vp, _vp]),
     "spmv_cpu_coo": (ctypes.c_int, [_c_i64, _c_i64, _vp, _vp, _vp, _vp, _vp, ctypes.c_int]),
     "spmv_cpu_csr": (ctypes.c_int, [_c_i64, _vp, _vp, _vp, _vp, _vp, ctypes.c_int]),
+    "spmv_cpu_csr_multi": (ctypes.c_int, [_c_i64, _vp, _vp, _vp, _c_i32, _vp, _c_i64, _vp, _c_i64]),
     "spmv_cpu_ell": (ctypes.c_int, [_c_i64, _c_i32, _c_i64, _c_i32, _vp, _vp, _vp, _vp, ctypes.c_int]),
     "spmv_cpu_sell": (ctypes.c_int, [_c_i64, _c_i32, _c_i32, _c_i64, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_int]),
     "spmv_cpu_cmrs": (ctypes.c_int, [_c_i64, _c_i32, _c_i64, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_int]),
@@ -715,6 +718,27 @@ def bytes_alg(n_rows: int, n_cols: int, nnz: int) -> int:
     return 12 * nnz + 4 * (n_rows + 1) + 8 * n_cols + 8 * n_rows
 
 
+def bytes_alg_multi(n_rows: int, n_cols: int, nnz: int, k: int) -> int:
+    """Algorithmic bytes of one multi-vector run Y = A X with k vectors: the
+    matrix once, k vectors read and k written (k = 1: bytes_alg)."""
+    return 12 * nnz + 4 * (n_rows + 1) + 8 * k * (n_cols + n_rows)
+
+
+def cpu_csr_multi(n_rows: int, ptr, col, val, X: np.ndarray, Y: np.ndarray, k: int | None = None) -> None:
+    """Host Y = A X (spmv_cpu_csr_multi): X and Y are 2-D float64 arrays with
+    unit inner stride whose row strides are ldx and ldy; k defaults to X's
+    width.  Only Y[:, :k] is written."""
+    for a in (X, Y):
+        if not isinstance(a, np.ndarray) or a.dtype != np.float64 or a.ndim != 2:
+            raise SpmvError(OTHER_ERROR, "cpu_csr_multi", "X and Y must be 2-D float64 arrays")
+        if a.shape[1] > 1 and a.strides[1] != 8 or a.strides[0] % 8:
+            raise SpmvError(OTHER_ERROR, "cpu_csr_multi", "X and Y need unit inner stride")
+    k = X.shape[1] if k is None else int(k)
+    rc = host_lib().spmv_cpu_csr_multi(n_rows, _ptr(ptr), _ptr(col), _ptr(val), k, _ptr(X), X.strides[0] // 8,
+                                       _ptr(Y), Y.strides[0] // 8)
+    _check_host(rc, "spmv_cpu_csr_multi")
+
+
 def check(m: Coo, x: np.ndarray, y: np.ndarray, rel_tol: float = 1e-6, abs_tol: float = 0.0):
     """Host check_result (reference inc/helper_functions.h:184-236)
     -> (bad_rows, first_bad)."""
@@ -842,6 +866,45 @@ class DeviceMatrix:
         else:
             raise SpmvError(OTHER_ERROR, "run", f"format {self.fmt} has no plan and no entry point")
         _check(rc, f"spmv_{self.fmt}_run")
+
+    @property
+    def multi_supported(self) -> bool:
+        """run_multi can run this matrix (spmv_plan_multi_supported)."""
+        return self.plan is not None and bool(hip_lib().spmv_plan_multi_supported(self.plan))
+
+    def run_multi(self, X, Y, stream=None) -> None:
+        """Y = A X on `stream` for k vectors stored row-major (spmv_plan_run_multi):
+        X is (>= n_cols, k), Y is (>= n_rows, k), float64 on the matrix's
+        device with inner stride 1; their row strides (>= k) are ldx and ldy,
+        so column slices of wider tensors work.  Only Y[:n_rows, :k] is written."""
+        torch = _torch()
+        for t in (X, Y):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float64:
+                raise SpmvError(OTHER_ERROR, "run_multi", "X and Y must be float64 tensors")
+            if t.dim() != 2:
+                raise SpmvError(OTHER_ERROR, "run_multi", "X and Y must be 2-D (rows, k)")
+        k = X.shape[1]
+        if k < 1 or Y.shape[1] != k:
+            raise SpmvError(OTHER_ERROR, "run_multi", "X and Y must have the same number k >= 1 of columns")
+        if X.shape[0] < self.n_cols or Y.shape[0] < self.n_rows:
+            raise SpmvError(OTHER_ERROR, "run_multi", "X or Y has too few rows")
+        # raw data_ptr()s and strides go to the C-ABI: rows of k contiguous
+        # values, row stride >= k (a one-row tensor's row stride is never used)
+        for t in (X, Y):
+            if (k > 1 and t.stride(1) != 1) or (t.shape[0] > 1 and t.stride(0) < k):
+                raise SpmvError(OTHER_ERROR, "run_multi", "X and Y need inner stride 1 and a row stride >= k")
+        here = torch.device(self.device)
+        idx = here.index or 0
+        for t in (X, Y):
+            if t.device.type != here.type or (t.device.index or 0) != idx:
+                raise SpmvError(OTHER_ERROR, "run_multi", f"X and Y must be on {here.type}:{idx}")
+        if self.plan is None:
+            raise SpmvError(OTHER_ERROR, "run_multi", f"format {self.fmt} has no plan: no multi-vector run")
+        ldx = X.stride(0) if X.shape[0] > 1 else k
+        ldy = Y.stride(0) if Y.shape[0] > 1 else k
+        st = stream if stream is not None else torch.cuda.current_stream(here)
+        _check(hip_lib().spmv_plan_run_multi(self.plan, k, _ptr(X), ldx, _ptr(Y), ldy, st.cuda_stream),
+               f"spmv_plan_run_multi ({self.fmt})")
 
 
 # the library's A/B switches (include/spmv_ext.h; placement and load policy only)
