@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "spmv.h"
 #include "spmv_ext.h"
 
@@ -16,6 +18,32 @@ constexpr int kBlock = 256;  // 4 waves per workgroup for every kernel
 // ---------------------------------------------------------------- errors
 int fail(int rc, const char *where, hipError_t e);
 int fail_msg(int rc, const char *msg);
+
+// Run-time value -> template argument.  with_int<V0, Vs...>(v, f) calls
+// f(std::integral_constant<int, V>{}) for the listed V equal to v, or for the
+// LAST listed value when none matches (a switch's `default:` arm); with_bool
+// the same with std::true_type / std::false_type.  A launcher is a generic
+// lambda that names its kernel once: kernel<decltype(L)::value, ...>.  An
+// entry point that refuses unlisted values checks the range before it calls.
+template <int V0, int... Vs, typename F>
+inline auto with_int(int v, F &&f)
+{
+    if constexpr (sizeof...(Vs) == 0)
+        return f(std::integral_constant<int, V0>{});
+    else if (v == V0)
+        return f(std::integral_constant<int, V0>{});
+    else
+        return with_int<Vs...>(v, f);
+}
+
+template <typename F>
+inline auto with_bool(bool b, F &&f)
+{
+    if (b)
+        return f(std::true_type{});
+    else
+        return f(std::false_type{});
+}
 
 // Sets the device for the duration of one C-ABI call and restores the
 // caller's device afterwards.
@@ -59,6 +87,12 @@ int launch_coo_staged(const spmv_dims &d, const int32_t *row, const int32_t *col
 // largest tail, or -1 on a launch / copy error
 int64_t coo_tail_build(const spmv_dims &d, const int32_t *row, int32_t *tails);
 int64_t coo_tail_cap();
+// x-window tables (one int2 {lo, hi} per workgroup, written by the *_window
+// kernels at build time).  windows_download: a malloc'd host copy (one
+// synchronising copy; the caller frees it).  windows_xcap: the LDS size of a
+// run, the widest window of at most `cap` entries.  `who` = the entry point.
+int windows_download(const void *win, int64_t n, hipStream_t st, int2 **host, const char *who);
+int windows_xcap(const void *win, int64_t n, int32_t cap, hipStream_t st, int32_t *xcap, const char *who);
 // LDS entries of x a staged COO tile / CMRS strip run may stage (16 KiB)
 constexpr int32_t kStagedXwinCap = 2048;
 int64_t coo_staged_tile();

@@ -700,6 +700,12 @@ static void launch_staged(const spmv_dims &d, const int64_t *row_ptr, const int3
     }
 }
 
+// the lanes per row the CSR kernels are instantiated for
+static bool lanes_ok(int L)
+{
+    return L >= 2 && L <= 64 && (L & (L - 1)) == 0;
+}
+
 template <int L>
 static void launch_csr(const spmv_dims &d, const int64_t *row_ptr,
                        const int32_t *col, const double *val, const double *x,
@@ -758,17 +764,10 @@ extern "C" int spmv_csr_run_variant(spmv_dims d, const int64_t *row_ptr,
         if (v == 1 && L < 64)
             L *= 2;
     }
-    switch (L) {
-    case 2: launch_csr<2>(d, row_ptr, col, val, x, y, v); break;
-    case 4: launch_csr<4>(d, row_ptr, col, val, x, y, v); break;
-    case 8: launch_csr<8>(d, row_ptr, col, val, x, y, v); break;
-    case 16: launch_csr<16>(d, row_ptr, col, val, x, y, v); break;
-    case 32: launch_csr<32>(d, row_ptr, col, val, x, y, v); break;
-    case 64: launch_csr<64>(d, row_ptr, col, val, x, y, v); break;
-    default:
+    if (!lanes_ok(L))
         return fail_msg(SPMV_OTHER_ERROR,
                         "spmv_csr_run: lanes_per_row must be 0 or a power of two in [2,64]");
-    }
+    with_int<2, 4, 8, 16, 32, 64>(L, [&](auto Lc) { launch_csr<decltype(Lc)::value>(d, row_ptr, col, val, x, y, v); });
     SPMV_CHECK_LAUNCH("csr kernel");
     return SPMV_SUCCESS;
 }
@@ -875,37 +874,14 @@ static void launch_csr_xwin(const spmv_dims &d, const int64_t *row_ptr, const Co
     if (mode == 3 && csr_xwin_lds(mode, xcap, gpw, RPB) + sizeof(double2) * kBlock * R * 2 > 64 * 1024)
         mode = 0;
     const size_t lds = csr_xwin_lds(mode, xcap, gpw, RPB);
-    if (n_win > INT32_MAX)
-        return;
     const int remap = csr_xwin_remap_rule(xcap, gpw * RPB, n_win) ? 1 : 0;
     const hipStream_t st = (hipStream_t)d.stream;
     if (mode == 3 && d.nnz >= 2 && csr_xwin_prefetch_rule(n_win))
-        hipLaunchKernelGGL((csr_xwin_kernel<L, R, NT, V, 4, Cols>), dim3((unsigned)n_win), dim3(kBlock), lds, st,
-                           d.n_rows, groups, gpw, row_ptr, cols, val, x, y, win, xcap, remap);
-    else if (mode == 3)
-        hipLaunchKernelGGL((csr_xwin_kernel<L, R, NT, V, 3, Cols>), dim3((unsigned)n_win), dim3(kBlock), lds, st,
-                           d.n_rows, groups, gpw, row_ptr, cols, val, x, y, win, xcap, remap);
-    else
-        hipLaunchKernelGGL((csr_xwin_kernel<L, R, NT, V, 0, Cols>), dim3((unsigned)n_win), dim3(kBlock), lds, st,
-                           d.n_rows, groups, gpw, row_ptr, cols, val, x, y, win, xcap, remap);
-}
-
-// One launcher per column source / value type: L from the switch, R and the
-// load policy from the rules above.
-template <int L, typename V, typename MakeCols>
-static void launch_xwin_l(const spmv_dims &d, const int64_t *row_ptr, MakeCols mk, const V *val, const double *x,
-                          double *y, const int2 *w, int32_t xcap, int64_t gpw)
-{
-    const bool nt = stream_nt(kCsrXwinNtDefault);
-    const bool r4 = csr_stage_rounds(d.n_rows, d.nnz, L) == 4;  // R = 3 or 4 (the rule)
-    if (nt && r4)
-        launch_csr_xwin<L, 4, true>(d, row_ptr, mk.template get<true>(), val, x, y, w, xcap, gpw);
-    else if (nt)
-        launch_csr_xwin<L, 3, true>(d, row_ptr, mk.template get<true>(), val, x, y, w, xcap, gpw);
-    else if (r4)
-        launch_csr_xwin<L, 4, false>(d, row_ptr, mk.template get<false>(), val, x, y, w, xcap, gpw);
-    else
-        launch_csr_xwin<L, 3, false>(d, row_ptr, mk.template get<false>(), val, x, y, w, xcap, gpw);
+        mode = 4;
+    with_int<4, 3, 0>(mode, [&](auto M) {
+        hipLaunchKernelGGL((csr_xwin_kernel<L, R, NT, V, decltype(M)::value, Cols>), dim3((unsigned)n_win),
+                           dim3(kBlock), lds, st, d.n_rows, groups, gpw, row_ptr, cols, val, x, y, win, xcap, remap);
+    });
 }
 
 struct MakeCol32 {
@@ -922,19 +898,23 @@ struct MakeCol16 {
     Col16<NT> get() const { return Col16<NT>{base, off, esc}; }
 };
 
+// One launcher per column source / value type: L as asked, R (3 or 4) and the
+// load policy from the rules above.
 template <typename V, typename MakeCols>
 static int launch_xwin_any(const spmv_dims &d, int L, const int64_t *row_ptr, MakeCols mk, const V *val,
                            const double *x, double *y, const int2 *w, int32_t xcap, int64_t gpw)
 {
-    switch (L) {
-    case 2: launch_xwin_l<2>(d, row_ptr, mk, val, x, y, w, xcap, gpw); break;
-    case 4: launch_xwin_l<4>(d, row_ptr, mk, val, x, y, w, xcap, gpw); break;
-    case 8: launch_xwin_l<8>(d, row_ptr, mk, val, x, y, w, xcap, gpw); break;
-    case 16: launch_xwin_l<16>(d, row_ptr, mk, val, x, y, w, xcap, gpw); break;
-    case 32: launch_xwin_l<32>(d, row_ptr, mk, val, x, y, w, xcap, gpw); break;
-    case 64: launch_xwin_l<64>(d, row_ptr, mk, val, x, y, w, xcap, gpw); break;
-    default: return fail_msg(SPMV_OTHER_ERROR, "csr x-window run: lanes_per_row must be 0 or a power of two in [2,64]");
-    }
+    if (!lanes_ok(L))
+        return fail_msg(SPMV_OTHER_ERROR, "csr x-window run: lanes_per_row must be 0 or a power of two in [2,64]");
+    const bool nt = stream_nt(kCsrXwinNtDefault);
+    with_int<2, 4, 8, 16, 32, 64>(L, [&](auto Lc) {
+        with_int<4, 3>(csr_stage_rounds(d.n_rows, d.nnz, decltype(Lc)::value), [&](auto Rc) {
+            with_bool(nt, [&](auto NT) {
+                launch_csr_xwin<decltype(Lc)::value, decltype(Rc)::value, decltype(NT)::value>(
+                    d, row_ptr, mk.template get<decltype(NT)::value>(), val, x, y, w, xcap, gpw);
+            });
+        });
+    });
     return SPMV_SUCCESS;
 }
 
@@ -971,29 +951,13 @@ extern "C" int spmv_csr_xwin_build(spmv_dims d, const int64_t *row_ptr, const in
     hipLaunchKernelGGL(csr_window_kernel, dim3((unsigned)n_win), dim3(kBlock), 0, st, d.n_rows, rpw, row_ptr,
                        col, (int2 *)win);
     SPMV_CHECK_LAUNCH("csr_window_kernel");
-    int2 *h = (int2 *)malloc(need);
-    if (!h)
-        return fail_msg(SPMV_OTHER_ERROR, "spmv_csr_xwin_build: out of host memory");
-    hipError_t e = hipMemcpyAsync(h, win, need, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess)
-        e = hipStreamSynchronize(st);
-    if (e != hipSuccess) {
-        free(h);
-        return fail(SPMV_PROGRAM_ERROR, "spmv_csr_xwin_build: copy windows", e);
-    }
-    int32_t best = 0;
-    for (int64_t g = 0; g < n_win; ++g) {
-        const int64_t span = (int64_t)h[g].y - h[g].x + 1;
-        if (span <= kCsrXwinCap && span > best)
-            best = (int32_t)span;
-    }
-    free(h);
-    *xcap = best;
-    return SPMV_SUCCESS;
+    return windows_xcap(win, n_win, kCsrXwinCap, st, xcap, "spmv_csr_xwin_build");
 }
 
+// argument checks of the three x-window runs; *L = lanes per row, *gpw = row
+// groups per window (a grid of one workgroup per window)
 static int xwin_args(spmv_dims d, int32_t rows_per_window, const void *win, int32_t xcap, int lanes_per_row,
-                     int *L, const char *who)
+                     int *L, int64_t *gpw, const char *who)
 {
     static thread_local char msg[160];
     if (d.n_rows < 0 || d.n_cols < 0 || d.nnz < 0 || rows_per_window < 0) {
@@ -1005,8 +969,14 @@ static int xwin_args(spmv_dims d, int32_t rows_per_window, const void *win, int3
         return fail_msg(SPMV_OTHER_ERROR, msg);
     }
     *L = lanes_per_row > 0 ? lanes_per_row : spmv_csr_auto_lanes(d.n_rows, d.nnz);
-    if (*L < 2 || *L > 64 || (*L & (*L - 1))) {
+    if (!lanes_ok(*L)) {
         snprintf(msg, sizeof msg, "%s: lanes_per_row must be 0 or a power of two in [2,64]", who);
+        return fail_msg(SPMV_OTHER_ERROR, msg);
+    }
+    *gpw = csr_xwin_gpw(*L, rows_per_window, d.n_rows);
+    const int64_t groups = (d.n_rows + kBlock / *L - 1) / (kBlock / *L);
+    if ((groups + *gpw - 1) / *gpw > INT32_MAX) {
+        snprintf(msg, sizeof msg, "%s: grid too large", who);
         return fail_msg(SPMV_OTHER_ERROR, msg);
     }
     return SPMV_SUCCESS;
@@ -1017,12 +987,12 @@ extern "C" int spmv_csr_run_xwin(spmv_dims d, const int64_t *row_ptr, const int3
                                  const void *win, int32_t xcap)
 {
     int L = 0;
-    int rc = xwin_args(d, rows_per_window, win, xcap, lanes_per_row, &L, "spmv_csr_run_xwin");
+    int64_t gpw = 0;
+    int rc = xwin_args(d, rows_per_window, win, xcap, lanes_per_row, &L, &gpw, "spmv_csr_run_xwin");
     if (rc != SPMV_SUCCESS || d.n_rows == 0)
         return rc;
     SPMV_GUARD(d);
-    rc = launch_xwin_any(d, L, row_ptr, MakeCol32{col}, val, x, y, (const int2 *)win, xcap,
-                         csr_xwin_gpw(L, rows_per_window, d.n_rows));
+    rc = launch_xwin_any(d, L, row_ptr, MakeCol32{col}, val, x, y, (const int2 *)win, xcap, gpw);
     if (rc != SPMV_SUCCESS)
         return rc;
     SPMV_CHECK_LAUNCH("csr_xwin_kernel");
@@ -1042,21 +1012,15 @@ extern "C" int spmv_csr16_run(spmv_dims d, const int64_t *row_ptr, const int32_t
     SPMV_GUARD(d);
     const int L = lanes_per_row > 0 ? lanes_per_row : spmv_csr_auto_lanes(d.n_rows, d.nnz);
     const bool nt = stream_nt(kCsrStreamNtDefault);
-#define SPMV_CSR16(LL)                                                                          \
-    (nt ? launch_csr16<LL, true>(d, row_ptr, Col16<true>{blk_base, col_off, col_esc}, val, x, y) \
-        : launch_csr16<LL, false>(d, row_ptr, Col16<false>{blk_base, col_off, col_esc}, val, x, y))
-    switch (L) {
-    case 2: SPMV_CSR16(2); break;
-    case 4: SPMV_CSR16(4); break;
-    case 8: SPMV_CSR16(8); break;
-    case 16: SPMV_CSR16(16); break;
-    case 32: SPMV_CSR16(32); break;
-    case 64: SPMV_CSR16(64); break;
-    default:
+    if (!lanes_ok(L))
         return fail_msg(SPMV_OTHER_ERROR,
                         "spmv_csr16_run: lanes_per_row must be 0 or a power of two in [2,64]");
-    }
-#undef SPMV_CSR16
+    with_int<2, 4, 8, 16, 32, 64>(L, [&](auto Lc) {
+        with_bool(nt, [&](auto NT) {
+            launch_csr16<decltype(Lc)::value, decltype(NT)::value>(
+                d, row_ptr, Col16<decltype(NT)::value>{blk_base, col_off, col_esc}, val, x, y);
+        });
+    });
     SPMV_CHECK_LAUNCH("csr16 kernel");
     return SPMV_SUCCESS;
 }
@@ -1072,14 +1036,15 @@ extern "C" int spmv_csr16_run_xwin(spmv_dims d, const int64_t *row_ptr, const in
                                    const void *win, int32_t xcap)
 {
     int L = 0;
-    int rc = xwin_args(d, rows_per_window, win, xcap, lanes_per_row, &L, "spmv_csr16_run_xwin");
+    int64_t gpw = 0;
+    int rc = xwin_args(d, rows_per_window, win, xcap, lanes_per_row, &L, &gpw, "spmv_csr16_run_xwin");
     if (rc != SPMV_SUCCESS || d.n_rows == 0)
         return rc;
     if (d.nnz > 0 && (!blk_base || !col_off))
         return fail_msg(SPMV_OTHER_ERROR, "spmv_csr16_run_xwin: missing index arrays");
     SPMV_GUARD(d);
     rc = launch_xwin_any(d, L, row_ptr, MakeCol16{blk_base, col_off, col_esc}, val, x, y, (const int2 *)win, xcap,
-                         csr_xwin_gpw(L, rows_per_window, d.n_rows));
+                         gpw);
     if (rc != SPMV_SUCCESS)
         return rc;
     SPMV_CHECK_LAUNCH("csr_xwin_kernel (16-bit columns)");
@@ -1096,14 +1061,11 @@ extern "C" int spmv_csr_f32v_run_xwin(spmv_dims d, const int64_t *row_ptr, const
                                       const void *win, int32_t xcap)
 {
     int L = 0;
-    int rc = xwin_args(d, rows_per_window, win, xcap, lanes_per_row, &L, "spmv_csr_f32v_run_xwin");
+    int64_t gpw = 0;
+    int rc = xwin_args(d, rows_per_window, win, xcap, lanes_per_row, &L, &gpw, "spmv_csr_f32v_run_xwin");
     if (rc != SPMV_SUCCESS || d.n_rows == 0)
         return rc;
     SPMV_GUARD(d);
-    const int64_t gpw = csr_xwin_gpw(L, rows_per_window, d.n_rows);
-    const int64_t groups = (d.n_rows + kBlock / L - 1) / (kBlock / L);
-    if ((groups + gpw - 1) / gpw > INT32_MAX)
-        return fail_msg(SPMV_OTHER_ERROR, "spmv_csr_f32v_run_xwin: grid too large");
     rc = launch_xwin_any(d, L, row_ptr, MakeCol32{col}, val, x, y, (const int2 *)win, xcap, gpw);
     if (rc != SPMV_SUCCESS)
         return rc;

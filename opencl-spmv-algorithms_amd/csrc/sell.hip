@@ -766,19 +766,15 @@ static void launch_sell_small(int64_t n_slices, const int64_t *slice_ptr, const 
     const size_t lds = XWIN ? (size_t)xcap * sizeof(double) : 0;
     const int64_t blocks = (n_slices + kSellSmallP - 1) / kSellSmallP;
     const int remap = xwin_remap(kSellSmallRemapDefault) ? 1 : 0;
-#define SPMV_SMALL_HG(HH)                                                                                     \
-    hipLaunchKernelGGL((sell_small_kernel<KI, NT, XWIN, XS, CT, HH>), dim3((unsigned)blocks),                 \
-                       dim3(kWave * kSellSmallS * kSellSmallP), lds, st, n_slices, slice_ptr, perm, col, val, xs, \
-                       y, wcap, x, win, xcap, hval, hcol, remap)
-    if constexpr (XWIN) {  // the head (SELL16, or int32 SELL small matrices)
-        if (hval)
-            SPMV_SMALL_HG(kSell16HeadG);
-        else
-            SPMV_SMALL_HG(0);
-    } else {
-        SPMV_SMALL_HG(0);
-    }
-#undef SPMV_SMALL_HG
+    auto go = [&](auto HG) {
+        hipLaunchKernelGGL((sell_small_kernel<KI, NT, XWIN, XS, CT, decltype(HG)::value>), dim3((unsigned)blocks),
+                           dim3(kWave * kSellSmallS * kSellSmallP), lds, st, n_slices, slice_ptr, perm, col, val, xs,
+                           y, wcap, x, win, xcap, hval, hcol, remap);
+    };
+    if constexpr (XWIN)  // the head (SELL16, or int32 SELL small matrices)
+        with_int<kSell16HeadG, 0>(hval ? kSell16HeadG : 0, go);
+    else
+        go(std::integral_constant<int, 0>{});
 }
 
 // SELL16 head copy: waves = 8 per small-kernel workgroup, G groups of
@@ -820,29 +816,6 @@ __global__ __launch_bounds__(kWave * kSellSmallS * kSellSmallP) void sell16_head
             hval[dst] = any ? val[src] : 0.0;
             hcol[dst] = any ? col16[src] : (CT)0;
         }
-}
-
-// x-window variant when win != NULL (windows from spmv_sell_xwin_build:
-// one per workgroup of kSellSmallP slices), else gathers through xs.
-template <typename XS>
-static void launch_sell_small_any(int32_t ki, bool nt, int64_t n_slices, const int64_t *slice_ptr,
-                                  const int32_t *perm, const int32_t *col, const double *val, const XS xs, double *y,
-                                  int64_t wcap, hipStream_t st, const double *x = nullptr,
-                                  const int2 *win = nullptr, int32_t xcap = 0)
-{
-    if (win) {
-        if constexpr (std::is_same<XS, XGlobal>::value) {
-#define SPMV_SMALL_W(K, N) launch_sell_small<K, N, true>(n_slices, slice_ptr, perm, col, val, xs, y, wcap, x, win, xcap, st)
-            if (ki == 2) { if (nt) SPMV_SMALL_W(2, true); else SPMV_SMALL_W(2, false); }
-            else { if (nt) SPMV_SMALL_W(1, true); else SPMV_SMALL_W(1, false); }
-#undef SPMV_SMALL_W
-            return;
-        }
-    }
-#define SPMV_SMALL_G(K, N) launch_sell_small<K, N, false>(n_slices, slice_ptr, perm, col, val, xs, y, wcap, x, (const int2 *)nullptr, 0, st)
-    if (ki == 2) { if (nt) SPMV_SMALL_G(2, true); else SPMV_SMALL_G(2, false); }
-    else { if (nt) SPMV_SMALL_G(1, true); else SPMV_SMALL_G(1, false); }
-#undef SPMV_SMALL_G
 }
 
 // Wide slices (SELL split plan, spmv_sell_split_plan): a slice wider than
@@ -974,6 +947,115 @@ __global__ __launch_bounds__(kBlock) void sell_hot_gather_kernel(int64_t H, cons
 constexpr int32_t kXwinCapWide = 8192;   // 64 KiB of LDS per 1024-slot workgroup (2 per CU)
 constexpr int32_t kXwinCapNarrow = 2048; // 16 KiB per 256-slot workgroup
 
+// f(KI, NT) with the k-interleave (1 or 2, checked by the callers) and the
+// stream load policy as compile-time constants
+template <typename F>
+static void with_ki_nt(int32_t ki, bool nt, F &&f)
+{
+    with_int<2, 1>(ki, [&](auto KI) { with_bool(nt, [&](auto NT) { f(KI, NT); }); });
+}
+
+// The main SELL launch of every run (geometry bt / blocks from
+// sell_geometry).  win != NULL (XGlobal only; windows from
+// spmv_sell_xwin_build, `head` optional): the small-matrix kernel with one x
+// window per workgroup, else sell_xwin_kernel.  Otherwise gathers through xs
+// (int32 columns only: SELL16 always has windows): the small-matrix kernel or
+// sell_kernel.  wcap: slot columns per slice covered here (split plans).
+template <typename XS, typename CT>
+static void launch_sell_main(const spmv_dims &d, int32_t C, int32_t sigma, int32_t ki, bool nt, int bt, int64_t blocks,
+                             int64_t n_slices, const int64_t *slice_ptr, const int32_t *perm, const CT *col,
+                             const double *val, const XS xs, const double *x, double *y, int64_t wcap, int remap,
+                             const int2 *win = nullptr, int32_t xcap = 0, const void *head = nullptr)
+{
+    const hipStream_t st = (hipStream_t)d.stream;
+    const bool small = sell_small(C, n_slices);
+    const double *hval = (const double *)head;
+    const CT *hcol = head ? (const CT *)(hval + sell16_head_elems(n_slices, ki)) : nullptr;
+    with_ki_nt(ki, nt, [&](auto KIc, auto NTc) {
+        constexpr int KI = decltype(KIc)::value;
+        constexpr bool NT = decltype(NTc)::value;
+        if constexpr (std::is_same<XS, XGlobal>::value) {
+            if (win && small) {
+                launch_sell_small<KI, NT, true, XS, CT>(n_slices, slice_ptr, perm, col, val, xs, y, wcap, x, win, xcap,
+                                                        st, hval, hcol);
+                return;
+            }
+            if (win) {
+                hipLaunchKernelGGL((sell_xwin_kernel<KI, NT, 4, CT>), dim3((unsigned)blocks), dim3(bt),
+                                   (size_t)xcap * sizeof(double), st, C, n_slices, slice_ptr, perm, col, val, x, y,
+                                   win, xcap, wcap, xwin_remap(false) ? 1 : 0,
+                                   sell_ystage(bt, sigma) ? d.n_rows : (int64_t)0);
+                return;
+            }
+        }
+        if constexpr (std::is_same<CT, int32_t>::value) {
+            if (small)
+                launch_sell_small<KI, NT, false, XS, CT>(n_slices, slice_ptr, perm, col, val, xs, y, wcap, x,
+                                                         (const int2 *)nullptr, 0, st);
+            else
+                hipLaunchKernelGGL((sell_kernel<KI, NT, 4, XS>), dim3((unsigned)blocks), dim3(bt), 0, st, C, n_slices,
+                                   slice_ptr, perm, col, val, xs, y, remap, wcap);
+        }
+    });
+}
+
+static int launch_sell_fix(int32_t C, int64_t n_chunks, const int32_t *chunk_slice, const int32_t *perm,
+                           const double *part, double *y, hipStream_t st)
+{
+    hipLaunchKernelGGL(sell_split_fix_kernel, dim3((unsigned)n_chunks), dim3(kSellFixThreads), 0, st, C, n_chunks,
+                       chunk_slice, perm, part, y);
+    SPMV_CHECK_LAUNCH("sell_split_fix_kernel");
+    return SPMV_SUCCESS;
+}
+
+// The chunks of a split plan beyond the main kernel's T slot columns, then
+// the fix pass that adds them to y.
+template <typename XS>
+static int launch_sell_chunks(int32_t C, int32_t ki, bool nt, int32_t T, int64_t n_chunks, int64_t cblocks,
+                              const int64_t *slice_ptr, const int32_t *chunk_slice, const int32_t *chunk_k0,
+                              const int32_t *perm, const int32_t *col, const double *val, const XS xs, double *part,
+                              double *y, hipStream_t st)
+{
+    with_ki_nt(ki, nt, [&](auto KI, auto NT) {
+        hipLaunchKernelGGL((sell_split_kernel<decltype(KI)::value, decltype(NT)::value, kSellSplitU, XS>),
+                           dim3((unsigned)cblocks), dim3(kBlock), 0, st, C, n_chunks, T, slice_ptr, chunk_slice,
+                           chunk_k0, col, val, xs, part);
+    });
+    SPMV_CHECK_LAUNCH("sell_split_kernel");
+    return launch_sell_fix(C, n_chunks, chunk_slice, perm, part, y, st);
+}
+
+// K / ld / ki of an ELL part
+static bool ell_args_ok(const spmv_dims &d, int32_t K, int64_t ld, int32_t ki)
+{
+    return d.n_rows >= 0 && K >= 0 && ld >= d.n_rows && ld % 64 == 0 && (ki == 1 || ki == 2) && K % ki == 0;
+}
+
+static int ell_check_args(const spmv_dims &d, int32_t K, int64_t ld, int32_t ki, const char *who)
+{
+    static thread_local char msg[160];
+    if (ell_args_ok(d, K, ld, ki))
+        return SPMV_SUCCESS;
+    if (d.n_rows < 0 || K < 0 || ld < d.n_rows || ld % 64 != 0) {
+        snprintf(msg, sizeof msg, "%s: bad K / ld", who);
+        return fail_msg(SPMV_OTHER_ERROR, msg);
+    }
+    snprintf(msg, sizeof msg, "%s: ki must be 1 or 2 and divide K", who);
+    return fail_msg(SPMV_OTHER_ERROR, msg);
+}
+
+// ell_kernel over the x source xs
+template <typename XS>
+static void launch_ell(const spmv_dims &d, int32_t K, int64_t ld, int32_t ki, const int32_t *col, const double *val,
+                       const XS xs, double *y, int remap)
+{
+    const int64_t blocks = (d.n_rows + kBlock - 1) / kBlock;
+    with_ki_nt(ki, stream_nt(kSellStreamNtDefault), [&](auto KI, auto NT) {
+        hipLaunchKernelGGL((ell_kernel<decltype(KI)::value, decltype(NT)::value, 4, XS>), dim3((unsigned)blocks),
+                           dim3(kBlock), 0, (hipStream_t)d.stream, d.n_rows, K, ld, col, val, xs, y, remap);
+    });
+}
+
 }  // namespace spmv
 
 // k-interleave for a SELL matrix of n_rows built for this device: 2 when
@@ -1004,18 +1086,8 @@ extern "C" int spmv_sell_run(spmv_dims d, int32_t C, int32_t sigma, int32_t ki,
     sell_geometry(C, sigma, n_slices, &bt, &blocks);
     if (blocks > INT32_MAX)
         return fail_msg(SPMV_OTHER_ERROR, "spmv_sell_run: grid too large");
-    const int remap = xcd_remap_enabled() ? 1 : 0;
-    const bool nt = stream_nt(kSellStreamNtDefault);
-    if (sell_small(C, n_slices)) {
-        launch_sell_small_any(ki, nt, n_slices, slice_ptr, perm, col, val, XGlobal{x}, y, INT64_MAX,
-                              (hipStream_t)d.stream);
-        SPMV_CHECK_LAUNCH("sell_small_kernel");
-        return SPMV_SUCCESS;
-    }
-    auto kern = ki == 2 ? (nt ? sell_kernel<2, true, 4> : sell_kernel<2, false, 4>)
-                        : (nt ? sell_kernel<1, true, 4> : sell_kernel<1, false, 4>);
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(bt), 0, (hipStream_t)d.stream, C,
-                       n_slices, slice_ptr, perm, col, val, XGlobal{x}, y, remap, (int64_t)INT64_MAX);
+    launch_sell_main(d, C, sigma, ki, stream_nt(kSellStreamNtDefault), bt, blocks, n_slices, slice_ptr, perm, col, val,
+                     XGlobal{x}, x, y, INT64_MAX, xcd_remap_enabled() ? 1 : 0);
     SPMV_CHECK_LAUNCH("sell_kernel");
     return SPMV_SUCCESS;
 }
@@ -1054,25 +1126,50 @@ extern "C" int spmv_sell_xwin_build(spmv_dims d, int32_t C, int32_t sigma, int64
     SPMV_CHECK_LAUNCH("sell_window_kernel");
     // the LDS size of the run: the widest window, up to the cap (build time,
     // so the one synchronising copy is off the SpMV path)
-    int2 *h = (int2 *)malloc((size_t)blocks * sizeof(int2));
-    if (!h)
-        return fail_msg(SPMV_OTHER_ERROR, "spmv_sell_xwin_build: out of host memory");
-    hipError_t e = hipMemcpyAsync(h, win, (size_t)blocks * sizeof(int2), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess)
-        e = hipStreamSynchronize(st);
-    if (e != hipSuccess) {
-        free(h);
-        return fail(SPMV_PROGRAM_ERROR, "spmv_sell_xwin_build: copy windows", e);
+    return windows_xcap(win, blocks, bt >= 1024 ? kXwinCapWide : kXwinCapNarrow, st, xcap, "spmv_sell_xwin_build");
+}
+
+static int sell16_check(const spmv_dims &d, int32_t C, int32_t sigma, int32_t ki, int64_t n_slices, const char *who)
+{
+    int rc = sell_check_args(d, C, sigma, ki, n_slices, who);
+    if (rc != SPMV_SUCCESS)
+        return rc;
+    if (C != kWave)
+        return fail_msg(SPMV_OTHER_ERROR, "SELL16: C must be 64 (one slot column per wave)");
+    return SPMV_SUCCESS;
+}
+
+// The x-window run behind spmv_sell_run_xwin, spmv_sell_run_xwin_head (int32
+// columns) and spmv_sell16_run (16-bit offsets): the small-matrix kernel with
+// per-workgroup x windows (same bits as spmv_sell_run) and the optional head,
+// else sell_xwin_kernel.  `who` = the entry point called.
+template <typename CT>
+static int run_sell_xwin(const spmv_dims &d, int32_t C, int32_t sigma, int32_t ki, int64_t n_slices,
+                         const int64_t *slice_ptr, const int32_t *perm, const CT *col, const double *val,
+                         const double *x, double *y, const void *win, int32_t xcap, const void *head, const char *who)
+{
+    static thread_local char msg[160];
+    int rc = std::is_same<CT, uint16_t>::value ? sell16_check(d, C, sigma, ki, n_slices, who)
+                                               : sell_check_args(d, C, sigma, ki, n_slices, who);
+    if (rc != SPMV_SUCCESS)
+        return rc;
+    if (d.n_rows == 0 || n_slices == 0)
+        return SPMV_SUCCESS;
+    if (!win || xcap < 0 || xcap > kXwinCapWide) {
+        snprintf(msg, sizeof msg, "%s: bad window arguments", who);
+        return fail_msg(SPMV_OTHER_ERROR, msg);
     }
-    const int32_t cap = bt >= 1024 ? kXwinCapWide : kXwinCapNarrow;
-    int32_t need = 0;
-    for (int64_t b = 0; b < blocks; ++b) {
-        const int64_t span = (int64_t)h[b].y - h[b].x + 1;
-        if (span <= cap && span > need)
-            need = (int32_t)span;
+    SPMV_GUARD(d);
+    int bt;
+    int64_t blocks;
+    sell_geometry(C, sigma, n_slices, &bt, &blocks);
+    if (blocks > INT32_MAX) {
+        snprintf(msg, sizeof msg, "%s: grid too large", who);
+        return fail_msg(SPMV_OTHER_ERROR, msg);
     }
-    free(h);
-    *xcap = need;
+    launch_sell_main(d, C, sigma, ki, stream_nt(kSellStreamNtDefault), bt, blocks, n_slices, slice_ptr, perm, col, val,
+                     XGlobal{x}, x, y, INT64_MAX, 0, (const int2 *)win, xcap, head);
+    SPMV_CHECK_LAUNCH("sell x-window kernel");
     return SPMV_SUCCESS;
 }
 
@@ -1081,34 +1178,8 @@ extern "C" int spmv_sell_run_xwin(spmv_dims d, int32_t C, int32_t sigma, int32_t
                                   const double *val, const double *x, double *y, const void *win,
                                   int32_t xcap)
 {
-    int rc = sell_check_args(d, C, sigma, ki, n_slices, "spmv_sell_run_xwin");
-    if (rc != SPMV_SUCCESS)
-        return rc;
-    if (d.n_rows == 0 || n_slices == 0)
-        return SPMV_SUCCESS;
-    if (!win || xcap < 0 || xcap > kXwinCapWide)
-        return fail_msg(SPMV_OTHER_ERROR, "spmv_sell_run_xwin: bad window arguments");
-    SPMV_GUARD(d);
-    int bt;
-    int64_t blocks;
-    sell_geometry(C, sigma, n_slices, &bt, &blocks);
-    if (blocks > INT32_MAX)
-        return fail_msg(SPMV_OTHER_ERROR, "spmv_sell_run_xwin: grid too large");
-    const bool nt = stream_nt(kSellStreamNtDefault);
-    if (sell_small(C, n_slices)) {  // few slices: the waves-per-slice kernel with per-slice x windows (same bits as spmv_sell_run)
-        launch_sell_small_any(ki, nt, n_slices, slice_ptr, perm, col, val, XGlobal{x}, y, INT64_MAX,
-                              (hipStream_t)d.stream, x, (const int2 *)win, xcap);
-        SPMV_CHECK_LAUNCH("sell_small_kernel");
-        return SPMV_SUCCESS;
-    }
-    auto kern = ki == 2 ? (nt ? sell_xwin_kernel<2, true, 4> : sell_xwin_kernel<2, false, 4>)
-                        : (nt ? sell_xwin_kernel<1, true, 4> : sell_xwin_kernel<1, false, 4>);
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(bt), (size_t)xcap * sizeof(double),
-                       (hipStream_t)d.stream, C, n_slices, slice_ptr, perm, col, val, x, y,
-                       (const int2 *)win, xcap, (int64_t)INT64_MAX, xwin_remap(false) ? 1 : 0,
-                       sell_ystage(bt, sigma) ? d.n_rows : (int64_t)0);
-    SPMV_CHECK_LAUNCH("sell_xwin_kernel");
-    return SPMV_SUCCESS;
+    return run_sell_xwin(d, C, sigma, ki, n_slices, slice_ptr, perm, col, val, x, y, win, xcap, nullptr,
+                         "spmv_sell_run_xwin");
 }
 
 // SELL16: the column of every stored slot as a 16-bit offset from its
@@ -1131,16 +1202,6 @@ __global__ __launch_bounds__(kBlock) void sell16_fill_kernel(int32_t C, int bt, 
         col16[e] = (uint16_t)(col[e] - lo);
 }
 
-static int sell16_check(const spmv_dims &d, int32_t C, int32_t sigma, int32_t ki, int64_t n_slices, const char *who)
-{
-    int rc = sell_check_args(d, C, sigma, ki, n_slices, who);
-    if (rc != SPMV_SUCCESS)
-        return rc;
-    if (C != kWave)
-        return fail_msg(SPMV_OTHER_ERROR, "SELL16: C must be 64 (one slot column per wave)");
-    return SPMV_SUCCESS;
-}
-
 extern "C" int spmv_sell16_fill(spmv_dims d, int32_t C, int32_t sigma, int64_t n_slices, const int64_t *slice_ptr,
                                 const int32_t *col, const void *win, uint16_t *col16)
 {
@@ -1160,16 +1221,10 @@ extern "C" int spmv_sell16_fill(spmv_dims d, int32_t C, int32_t sigma, int64_t n
     const hipStream_t st = (hipStream_t)d.stream;
     // every window must span at most 65,536 columns (build time: one
     // synchronising copy of the window table)
-    int2 *h = (int2 *)malloc((size_t)blocks * sizeof(int2));
-    if (!h)
-        return fail_msg(SPMV_OTHER_ERROR, "spmv_sell16_fill: out of host memory");
-    hipError_t e = hipMemcpyAsync(h, win, (size_t)blocks * sizeof(int2), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess)
-        e = hipStreamSynchronize(st);
-    if (e != hipSuccess) {
-        free(h);
-        return fail(SPMV_PROGRAM_ERROR, "spmv_sell16_fill: copy windows", e);
-    }
+    int2 *h;
+    rc = windows_download(win, blocks, st, &h, "spmv_sell16_fill");
+    if (rc != SPMV_SUCCESS)
+        return rc;
     int64_t wide = 0;
     for (int64_t b = 0; b < blocks; ++b)
         wide += (int64_t)h[b].y - h[b].x + 1 > 65536;
@@ -1182,76 +1237,73 @@ extern "C" int spmv_sell16_fill(spmv_dims d, int32_t C, int32_t sigma, int64_t n
     return SPMV_SUCCESS;
 }
 
-extern "C" size_t spmv_sell16_head_bytes(int64_t n_slices, int32_t C, int32_t ki)
+// Bytes of the head (every small-kernel wave's first slot groups: values,
+// then columns of type CT); 0 when the matrix has none.
+template <typename CT>
+static size_t sell_head_bytes(int64_t n_slices, int32_t C, int32_t ki)
 {
     if (n_slices <= 0 || (ki != 1 && ki != 2) || !sell_small(C, n_slices))
         return 0;
-    return (size_t)sell16_head_elems(n_slices, ki) * (sizeof(double) + sizeof(uint16_t));
+    return (size_t)sell16_head_elems(n_slices, ki) * (sizeof(double) + sizeof(CT));
+}
+
+template <typename CT>
+static int sell_head_fill(const spmv_dims &d, int32_t C, int32_t sigma, int32_t ki, int64_t n_slices,
+                          const int64_t *slice_ptr, const double *val, const CT *col, void *head, size_t head_bytes,
+                          const char *who)
+{
+    static thread_local char msg[160];
+    int rc = std::is_same<CT, uint16_t>::value ? sell16_check(d, C, sigma, ki, n_slices, who)
+                                               : sell_check_args(d, C, sigma, ki, n_slices, who);
+    if (rc != SPMV_SUCCESS)
+        return rc;
+    const size_t need = sell_head_bytes<CT>(n_slices, C, ki);
+    if (need == 0) {
+        snprintf(msg, sizeof msg, "%s: no head (not a small-kernel matrix)", who);
+        return fail_msg(SPMV_OTHER_ERROR, msg);
+    }
+    if (!head || head_bytes < need || !slice_ptr || !val || !col) {
+        snprintf(msg, sizeof msg, "%s: arrays or head buffer missing", who);
+        return fail_msg(SPMV_OTHER_ERROR, msg);
+    }
+    SPMV_GUARD(d);
+    double *hval = (double *)head;
+    CT *hcol = (CT *)(hval + sell16_head_elems(n_slices, ki));
+    const int64_t blocks = (n_slices + kSellSmallP - 1) / kSellSmallP;
+    with_int<2, 1>(ki, [&](auto KI) {
+        hipLaunchKernelGGL((sell16_head_kernel<decltype(KI)::value, kSell16HeadG, CT>), dim3((unsigned)blocks),
+                           dim3(kWave * kSellSmallS * kSellSmallP), 0, (hipStream_t)d.stream, n_slices, slice_ptr, val,
+                           col, hval, hcol);
+    });
+    SPMV_CHECK_LAUNCH("sell16_head_kernel");
+    return SPMV_SUCCESS;
+}
+
+extern "C" size_t spmv_sell16_head_bytes(int64_t n_slices, int32_t C, int32_t ki)
+{
+    return sell_head_bytes<uint16_t>(n_slices, C, ki);
 }
 
 extern "C" int spmv_sell16_head_fill(spmv_dims d, int32_t C, int32_t sigma, int32_t ki, int64_t n_slices,
                                      const int64_t *slice_ptr, const double *val, const uint16_t *col16, void *head,
                                      size_t head_bytes)
 {
-    int rc = sell16_check(d, C, sigma, ki, n_slices, "spmv_sell16_head_fill");
-    if (rc != SPMV_SUCCESS)
-        return rc;
-    const size_t need = spmv_sell16_head_bytes(n_slices, C, ki);
-    if (need == 0)
-        return fail_msg(SPMV_OTHER_ERROR, "spmv_sell16_head_fill: no head (not a small-kernel matrix)");
-    if (!head || head_bytes < need || !slice_ptr || !val || !col16)
-        return fail_msg(SPMV_OTHER_ERROR, "spmv_sell16_head_fill: arrays or head buffer missing");
-    SPMV_GUARD(d);
-    double *hval = (double *)head;
-    uint16_t *hcol = (uint16_t *)(hval + sell16_head_elems(n_slices, ki));
-    const int64_t blocks = (n_slices + kSellSmallP - 1) / kSellSmallP;
-    const hipStream_t st = (hipStream_t)d.stream;
-#define SPMV_HEAD_FILL(K, HH)                                                                                    \
-    hipLaunchKernelGGL((sell16_head_kernel<K, HH, uint16_t>), dim3((unsigned)blocks),                             \
-                       dim3(kWave * kSellSmallS * kSellSmallP), 0, st, n_slices, slice_ptr, val, col16, hval, hcol)
-    if (ki == 2)
-        SPMV_HEAD_FILL(2, kSell16HeadG);
-    else
-        SPMV_HEAD_FILL(1, kSell16HeadG);
-#undef SPMV_HEAD_FILL
-    SPMV_CHECK_LAUNCH("sell16_head_kernel");
-    return SPMV_SUCCESS;
+    return sell_head_fill(d, C, sigma, ki, n_slices, slice_ptr, val, col16, head, head_bytes,
+                          "spmv_sell16_head_fill");
 }
 
 // The head for int32 SELL (small matrices): the same copy of every wave's
 // first slot groups, with int32 columns (12 B per slot).
 extern "C" size_t spmv_sell_head_bytes(int64_t n_slices, int32_t C, int32_t ki)
 {
-    if (n_slices <= 0 || (ki != 1 && ki != 2) || !sell_small(C, n_slices))
-        return 0;
-    return (size_t)sell16_head_elems(n_slices, ki) * (sizeof(double) + sizeof(int32_t));
+    return sell_head_bytes<int32_t>(n_slices, C, ki);
 }
 
 extern "C" int spmv_sell_head_fill(spmv_dims d, int32_t C, int32_t sigma, int32_t ki, int64_t n_slices,
                                    const int64_t *slice_ptr, const double *val, const int32_t *col, void *head,
                                    size_t head_bytes)
 {
-    int rc = sell_check_args(d, C, sigma, ki, n_slices, "spmv_sell_head_fill");
-    if (rc != SPMV_SUCCESS)
-        return rc;
-    const size_t need = spmv_sell_head_bytes(n_slices, C, ki);
-    if (need == 0)
-        return fail_msg(SPMV_OTHER_ERROR, "spmv_sell_head_fill: no head (not a small-kernel matrix)");
-    if (!head || head_bytes < need || !slice_ptr || !val || !col)
-        return fail_msg(SPMV_OTHER_ERROR, "spmv_sell_head_fill: arrays or head buffer missing");
-    SPMV_GUARD(d);
-    double *hval = (double *)head;
-    int32_t *hcol = (int32_t *)(hval + sell16_head_elems(n_slices, ki));
-    const int64_t blocks = (n_slices + kSellSmallP - 1) / kSellSmallP;
-    const hipStream_t st = (hipStream_t)d.stream;
-    if (ki == 2)
-        hipLaunchKernelGGL((sell16_head_kernel<2, kSell16HeadG, int32_t>), dim3((unsigned)blocks),
-                           dim3(kWave * kSellSmallS * kSellSmallP), 0, st, n_slices, slice_ptr, val, col, hval, hcol);
-    else
-        hipLaunchKernelGGL((sell16_head_kernel<1, kSell16HeadG, int32_t>), dim3((unsigned)blocks),
-                           dim3(kWave * kSellSmallS * kSellSmallP), 0, st, n_slices, slice_ptr, val, col, hval, hcol);
-    SPMV_CHECK_LAUNCH("sell_head_kernel");
-    return SPMV_SUCCESS;
+    return sell_head_fill(d, C, sigma, ki, n_slices, slice_ptr, val, col, head, head_bytes, "spmv_sell_head_fill");
 }
 
 // spmv_sell_run_xwin with the head (small matrices): same bits.
@@ -1262,26 +1314,8 @@ extern "C" int spmv_sell_run_xwin_head(spmv_dims d, int32_t C, int32_t sigma, in
 {
     if (!head || !sell_small(C, n_slices))
         return spmv_sell_run_xwin(d, C, sigma, ki, n_slices, slice_ptr, perm, col, val, x, y, win, xcap);
-    int rc = sell_check_args(d, C, sigma, ki, n_slices, "spmv_sell_run_xwin_head");
-    if (rc != SPMV_SUCCESS)
-        return rc;
-    if (d.n_rows == 0 || n_slices == 0)
-        return SPMV_SUCCESS;
-    if (!win || xcap < 0 || xcap > kXwinCapWide)
-        return fail_msg(SPMV_OTHER_ERROR, "spmv_sell_run_xwin_head: bad window arguments");
-    SPMV_GUARD(d);
-    const bool nt = stream_nt(kSellStreamNtDefault);
-    const hipStream_t st = (hipStream_t)d.stream;
-    const int2 *w = (const int2 *)win;
-    const double *hval = (const double *)head;
-    const int32_t *hcol = (const int32_t *)(hval + sell16_head_elems(n_slices, ki));
-#define SPMV_SMALLH(K, N) \
-    launch_sell_small<K, N, true, XGlobal, int32_t>(n_slices, slice_ptr, perm, col, val, XGlobal{x}, y, INT64_MAX, x, w, xcap, st, hval, hcol)
-    if (ki == 2) { if (nt) SPMV_SMALLH(2, true); else SPMV_SMALLH(2, false); }
-    else { if (nt) SPMV_SMALLH(1, true); else SPMV_SMALLH(1, false); }
-#undef SPMV_SMALLH
-    SPMV_CHECK_LAUNCH("sell_small_kernel (head)");
-    return SPMV_SUCCESS;
+    return run_sell_xwin(d, C, sigma, ki, n_slices, slice_ptr, perm, col, val, x, y, win, xcap, head,
+                         "spmv_sell_run_xwin_head");
 }
 
 extern "C" int spmv_sell16_run(spmv_dims d, int32_t C, int32_t sigma, int32_t ki, int64_t n_slices,
@@ -1289,60 +1323,19 @@ extern "C" int spmv_sell16_run(spmv_dims d, int32_t C, int32_t sigma, int32_t ki
                                const double *val, const double *x, double *y, const void *win, int32_t xcap,
                                const void *head)
 {
-    int rc = sell16_check(d, C, sigma, ki, n_slices, "spmv_sell16_run");
-    if (rc != SPMV_SUCCESS)
-        return rc;
-    if (d.n_rows == 0 || n_slices == 0)
-        return SPMV_SUCCESS;
-    if (!win || xcap < 0 || xcap > kXwinCapWide)
-        return fail_msg(SPMV_OTHER_ERROR, "spmv_sell16_run: bad window arguments");
-    SPMV_GUARD(d);
-    int bt;
-    int64_t blocks;
-    sell_geometry(C, sigma, n_slices, &bt, &blocks);
-    if (blocks > INT32_MAX)
-        return fail_msg(SPMV_OTHER_ERROR, "spmv_sell16_run: grid too large");
-    const bool nt = stream_nt(kSellStreamNtDefault);
-    const hipStream_t st = (hipStream_t)d.stream;
-    const int2 *w = (const int2 *)win;
-    if (sell_small(C, n_slices)) {
-        const double *hval = (const double *)head;
-        const uint16_t *hcol = head ? (const uint16_t *)(hval + sell16_head_elems(n_slices, ki)) : nullptr;
-#define SPMV_SMALL16(K, N) \
-    launch_sell_small<K, N, true, XGlobal, uint16_t>(n_slices, slice_ptr, perm, col16, val, XGlobal{x}, y, INT64_MAX, x, w, xcap, st, hval, hcol)
-        if (ki == 2) { if (nt) SPMV_SMALL16(2, true); else SPMV_SMALL16(2, false); }
-        else { if (nt) SPMV_SMALL16(1, true); else SPMV_SMALL16(1, false); }
-#undef SPMV_SMALL16
-        SPMV_CHECK_LAUNCH("sell_small_kernel (SELL16)");
-        return SPMV_SUCCESS;
-    }
-    auto kern = ki == 2 ? (nt ? sell_xwin_kernel<2, true, 4, uint16_t> : sell_xwin_kernel<2, false, 4, uint16_t>)
-                        : (nt ? sell_xwin_kernel<1, true, 4, uint16_t> : sell_xwin_kernel<1, false, 4, uint16_t>);
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(bt), (size_t)xcap * sizeof(double), st, C, n_slices,
-                       slice_ptr, perm, col16, val, x, y, w, xcap, (int64_t)INT64_MAX, xwin_remap(false) ? 1 : 0,
-                       sell_ystage(bt, sigma) ? d.n_rows : (int64_t)0);
-    SPMV_CHECK_LAUNCH("sell_xwin_kernel (SELL16)");
-    return SPMV_SUCCESS;
+    return run_sell_xwin(d, C, sigma, ki, n_slices, slice_ptr, perm, col16, val, x, y, win, xcap, head,
+                         "spmv_sell16_run");
 }
 
 extern "C" int spmv_ell_run(spmv_dims d, int32_t K, int64_t ld, int32_t ki,
                             const int32_t *col, const double *val,
                             const double *x, double *y)
 {
-    if (d.n_rows < 0 || K < 0 || ld < d.n_rows || ld % 64 != 0)
-        return fail_msg(SPMV_OTHER_ERROR, "spmv_ell_run: bad K / ld");
-    if ((ki != 1 && ki != 2) || K % ki != 0)
-        return fail_msg(SPMV_OTHER_ERROR, "spmv_ell_run: ki must be 1 or 2 and divide K");
-    if (d.n_rows == 0)
-        return SPMV_SUCCESS;
+    int rc = ell_check_args(d, K, ld, ki, "spmv_ell_run");
+    if (rc != SPMV_SUCCESS || d.n_rows == 0)
+        return rc;
     SPMV_GUARD(d);
-    const int64_t blocks = (d.n_rows + kBlock - 1) / kBlock;
-    const int remap = xcd_remap_enabled() ? 1 : 0;
-    const bool nt = stream_nt(kSellStreamNtDefault);
-    auto kern = ki == 2 ? (nt ? ell_kernel<2, true, 4> : ell_kernel<2, false, 4>)
-                        : (nt ? ell_kernel<1, true, 4> : ell_kernel<1, false, 4>);
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(kBlock), 0, (hipStream_t)d.stream,
-                       d.n_rows, K, ld, col, val, XGlobal{x}, y, remap);
+    launch_ell(d, K, ld, ki, col, val, XGlobal{x}, y, xcd_remap_enabled() ? 1 : 0);
     SPMV_CHECK_LAUNCH("ell_kernel");
     return SPMV_SUCCESS;
 }
@@ -1355,13 +1348,15 @@ extern "C" size_t spmv_ell_xwin_bytes(int64_t n_rows)
 extern "C" int spmv_ell_xwin_build(spmv_dims d, int32_t K, int64_t ld, int32_t ki, const int32_t *col,
                                    void *win, size_t win_bytes, int32_t *xcap)
 {
-    if (d.n_rows < 0 || K < 0 || ld < d.n_rows || ld % 64 != 0 || (ki != 1 && ki != 2) || K % ki != 0 || !xcap)
-        return fail_msg(SPMV_OTHER_ERROR, "spmv_ell_xwin_build: bad arguments");
+    int rc = ell_check_args(d, K, ld, ki, "spmv_ell_xwin_build");
+    if (rc != SPMV_SUCCESS)
+        return rc;
+    if (!xcap)
+        return fail_msg(SPMV_OTHER_ERROR, "spmv_ell_xwin_build: xcap is NULL");
     *xcap = 0;
     if (d.n_rows == 0)
         return SPMV_SUCCESS;
-    const size_t need = spmv_ell_xwin_bytes(d.n_rows);
-    if (!win || win_bytes < need)
+    if (!win || win_bytes < spmv_ell_xwin_bytes(d.n_rows))
         return fail_msg(SPMV_OTHER_ERROR, "spmv_ell_xwin_build: window buffer too small");
     SPMV_GUARD(d);
     const int64_t blocks = (d.n_rows + kBlock - 1) / kBlock;
@@ -1369,49 +1364,27 @@ extern "C" int spmv_ell_xwin_build(spmv_dims d, int32_t K, int64_t ld, int32_t k
     hipLaunchKernelGGL(ell_window_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, st, d.n_rows, K, ld, ki, col,
                        (int2 *)win);
     SPMV_CHECK_LAUNCH("ell_window_kernel");
-    int2 *h = (int2 *)malloc(need);
-    if (!h)
-        return fail_msg(SPMV_OTHER_ERROR, "spmv_ell_xwin_build: out of host memory");
-    hipError_t e = hipMemcpyAsync(h, win, need, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess)
-        e = hipStreamSynchronize(st);
-    if (e != hipSuccess) {
-        free(h);
-        return fail(SPMV_PROGRAM_ERROR, "spmv_ell_xwin_build: copy windows", e);
-    }
-    int32_t best = 0;
-    for (int64_t b = 0; b < blocks; ++b) {
-        const int64_t span = (int64_t)h[b].y - h[b].x + 1;
-        if (span <= kEllXwinCap && span > best)
-            best = (int32_t)span;
-    }
-    free(h);
-    *xcap = best;
-    return SPMV_SUCCESS;
+    return windows_xcap(win, blocks, kEllXwinCap, st, xcap, "spmv_ell_xwin_build");
 }
 
 extern "C" int spmv_ell_run_xwin(spmv_dims d, int32_t K, int64_t ld, int32_t ki, const int32_t *col,
                                  const double *val, const double *x, double *y, const void *win, int32_t xcap)
 {
-    if (d.n_rows < 0 || K < 0 || ld < d.n_rows || ld % 64 != 0)
-        return fail_msg(SPMV_OTHER_ERROR, "spmv_ell_run_xwin: bad K / ld");
-    if ((ki != 1 && ki != 2) || K % ki != 0)
-        return fail_msg(SPMV_OTHER_ERROR, "spmv_ell_run_xwin: ki must be 1 or 2 and divide K");
-    if (d.n_rows == 0)
-        return SPMV_SUCCESS;
+    int rc = ell_check_args(d, K, ld, ki, "spmv_ell_run_xwin");
+    if (rc != SPMV_SUCCESS || d.n_rows == 0)
+        return rc;
     if (!win || xcap < 0 || xcap > kEllXwinCap)
         return fail_msg(SPMV_OTHER_ERROR, "spmv_ell_run_xwin: bad window arguments");
     SPMV_GUARD(d);
     const int64_t blocks = (d.n_rows + kBlock - 1) / kBlock;
-    const bool nt = stream_nt(kSellStreamNtDefault);
-    auto kern = blocks <= 4 * 256
-                    ? (ki == 2 ? (nt ? ell_xwin_kernel<2, true, 4, true> : ell_xwin_kernel<2, false, 4, true>)
-                               : (nt ? ell_xwin_kernel<1, true, 4, true> : ell_xwin_kernel<1, false, 4, true>))
-                    : (ki == 2 ? (nt ? ell_xwin_kernel<2, true, 4> : ell_xwin_kernel<2, false, 4>)
-                               : (nt ? ell_xwin_kernel<1, true, 4> : ell_xwin_kernel<1, false, 4>));
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(kBlock), (size_t)xcap * sizeof(double),
-                       (hipStream_t)d.stream, d.n_rows, K, ld, col, val, x, y, (const int2 *)win, xcap,
-                       xwin_remap(kEllRemapDefault) ? 1 : 0);
+    with_ki_nt(ki, stream_nt(kSellStreamNtDefault), [&](auto KI, auto NT) {
+        with_bool(blocks <= 4 * 256, [&](auto WB) {
+            hipLaunchKernelGGL((ell_xwin_kernel<decltype(KI)::value, decltype(NT)::value, 4, decltype(WB)::value>),
+                               dim3((unsigned)blocks), dim3(kBlock), (size_t)xcap * sizeof(double),
+                               (hipStream_t)d.stream, d.n_rows, K, ld, col, val, x, y, (const int2 *)win, xcap,
+                               xwin_remap(kEllRemapDefault) ? 1 : 0);
+        });
+    });
     SPMV_CHECK_LAUNCH("ell_xwin_kernel");
     return SPMV_SUCCESS;
 }
@@ -1423,7 +1396,23 @@ extern "C" int spmv_ell_run_xwin(spmv_dims d, int32_t K, int64_t ld, int32_t ki,
 // 1.587 -> 0.870 ms).  Bad K / ld / ki fall through to the ELL checks.
 static bool hyb_is_coo(const spmv_dims &d, int32_t K, int64_t ld, int32_t ki, int64_t tail_nnz)
 {
-    return K == 0 && d.n_rows > 0 && ld >= d.n_rows && ld % 64 == 0 && (ki == 1 || ki == 2) && tail_nnz > 0;
+    return K == 0 && d.n_rows > 0 && tail_nnz > 0 && ell_args_ok(d, K, ld, ki);
+}
+
+// Shared start of the spmv_hyb_run* entries: *dt = the tail's dims, *as_coo =
+// the whole matrix is the tail (hyb_is_coo).
+static int hyb_begin(const spmv_dims &d, int32_t K, int64_t ld, int32_t ki, int64_t tail_nnz, const char *who,
+                     spmv_dims *dt, bool *as_coo)
+{
+    static thread_local char msg[160];
+    if (tail_nnz < 0) {
+        snprintf(msg, sizeof msg, "%s: negative tail size", who);
+        return fail_msg(SPMV_OTHER_ERROR, msg);
+    }
+    *dt = d;
+    dt->nnz = tail_nnz;
+    *as_coo = hyb_is_coo(d, K, ld, ki, tail_nnz);
+    return SPMV_SUCCESS;
 }
 
 extern "C" size_t spmv_hyb_ws_bytes(int64_t tail_nnz)
@@ -1440,13 +1429,14 @@ extern "C" int spmv_hyb_run(spmv_dims d, int32_t K, int64_t ld, int32_t ki, cons
                             const int32_t *tail_col, const double *tail_val, const double *x, double *y,
                             void *ws, size_t ws_bytes)
 {
-    if (tail_nnz < 0)
-        return fail_msg(SPMV_OTHER_ERROR, "spmv_hyb_run: negative tail size");
-    spmv_dims dt = d;
-    dt.nnz = tail_nnz;
-    if (hyb_is_coo(d, K, ld, ki, tail_nnz))
+    spmv_dims dt;
+    bool as_coo;
+    int rc = hyb_begin(d, K, ld, ki, tail_nnz, "spmv_hyb_run", &dt, &as_coo);
+    if (rc != SPMV_SUCCESS)
+        return rc;
+    if (as_coo)
         return spmv_coo_run(dt, tail_row, tail_col, tail_val, x, y, ws, ws_bytes);
-    int rc = spmv_ell_run(d, K, ld, ki, ell_col, ell_val, x, y);
+    rc = spmv_ell_run(d, K, ld, ki, ell_col, ell_val, x, y);
     if (rc != SPMV_SUCCESS || tail_nnz == 0 || d.n_rows == 0)
         return rc;
     if (!ws || ws_bytes < spmv_hyb_ws_bytes(tail_nnz))
@@ -1461,6 +1451,33 @@ extern "C" int spmv_hyb_run(spmv_dims d, int32_t K, int64_t ld, int32_t ki, cons
     return launch_carry(tiles, carry_row, carry_val, y, (hipStream_t)d.stream);
 }
 
+// HYB with a single-pass tail (spmv_hyb_run_tail; with xwin, the ELL part
+// through the x-window ELL kernel: spmv_hyb_run_tail_xwin)
+static int run_hyb_tail(const spmv_dims &d, int32_t K, int64_t ld, int32_t ki, const int32_t *ell_col,
+                        const double *ell_val, int64_t tail_nnz, const int32_t *tail_row, const int32_t *tail_col,
+                        const double *tail_val, const double *x, double *y, const void *tails, bool xwin,
+                        const void *win, int32_t xcap, const char *who)
+{
+    static thread_local char msg[160];
+    spmv_dims dt;
+    bool as_coo;
+    int rc = hyb_begin(d, K, ld, ki, tail_nnz, who, &dt, &as_coo);
+    if (rc != SPMV_SUCCESS)
+        return rc;
+    if (as_coo)
+        return spmv_coo_run_tail(dt, tail_row, tail_col, tail_val, x, y, tails);
+    rc = xwin ? spmv_ell_run_xwin(d, K, ld, ki, ell_col, ell_val, x, y, win, xcap)
+              : spmv_ell_run(d, K, ld, ki, ell_col, ell_val, x, y);
+    if (rc != SPMV_SUCCESS || tail_nnz == 0 || d.n_rows == 0)
+        return rc;
+    if (!tails) {
+        snprintf(msg, sizeof msg, "%s: no tail plan", who);
+        return fail_msg(SPMV_OTHER_ERROR, msg);
+    }
+    SPMV_GUARD(d);
+    return launch_coo_staged_acc(dt, tail_row, tail_col, tail_val, x, y, nullptr, nullptr, (const int32_t *)tails);
+}
+
 // HYB with a single-pass tail: `tails` from spmv_coo_tail_build over the
 // tail arrays (dims with nnz = tail_nnz); each tile of the tail finishes its
 // last row, so no carry pass and no workspace.
@@ -1469,20 +1486,8 @@ extern "C" int spmv_hyb_run_tail(spmv_dims d, int32_t K, int64_t ld, int32_t ki,
                                  const int32_t *tail_col, const double *tail_val, const double *x, double *y,
                                  const void *tails)
 {
-    if (tail_nnz < 0)
-        return fail_msg(SPMV_OTHER_ERROR, "spmv_hyb_run_tail: negative tail size");
-    spmv_dims dt = d;
-    dt.nnz = tail_nnz;
-    if (hyb_is_coo(d, K, ld, ki, tail_nnz))
-        return spmv_coo_run_tail(dt, tail_row, tail_col, tail_val, x, y, tails);
-    int rc = spmv_ell_run(d, K, ld, ki, ell_col, ell_val, x, y);
-    if (rc != SPMV_SUCCESS || tail_nnz == 0 || d.n_rows == 0)
-        return rc;
-    if (!tails)
-        return fail_msg(SPMV_OTHER_ERROR, "spmv_hyb_run_tail: no tail plan");
-    SPMV_GUARD(d);
-    return launch_coo_staged_acc(dt, tail_row, tail_col, tail_val, x, y, nullptr, nullptr,
-                                 (const int32_t *)tails);
+    return run_hyb_tail(d, K, ld, ki, ell_col, ell_val, tail_nnz, tail_row, tail_col, tail_val, x, y, tails, false,
+                        nullptr, 0, "spmv_hyb_run_tail");
 }
 
 // HYB with a single-pass tail and the ELL part through the x-window ELL
@@ -1493,20 +1498,8 @@ extern "C" int spmv_hyb_run_tail_xwin(spmv_dims d, int32_t K, int64_t ld, int32_
                                       const int32_t *tail_col, const double *tail_val, const double *x, double *y,
                                       const void *tails, const void *win, int32_t xcap)
 {
-    if (tail_nnz < 0)
-        return fail_msg(SPMV_OTHER_ERROR, "spmv_hyb_run_tail_xwin: negative tail size");
-    spmv_dims dt = d;
-    dt.nnz = tail_nnz;
-    if (hyb_is_coo(d, K, ld, ki, tail_nnz))
-        return spmv_coo_run_tail(dt, tail_row, tail_col, tail_val, x, y, tails);
-    int rc = spmv_ell_run_xwin(d, K, ld, ki, ell_col, ell_val, x, y, win, xcap);
-    if (rc != SPMV_SUCCESS || tail_nnz == 0 || d.n_rows == 0)
-        return rc;
-    if (!tails)
-        return fail_msg(SPMV_OTHER_ERROR, "spmv_hyb_run_tail_xwin: no tail plan");
-    SPMV_GUARD(d);
-    return launch_coo_staged_acc(dt, tail_row, tail_col, tail_val, x, y, nullptr, nullptr,
-                                 (const int32_t *)tails);
+    return run_hyb_tail(d, K, ld, ki, ell_col, ell_val, tail_nnz, tail_row, tail_col, tail_val, x, y, tails, true, win,
+                        xcap, "spmv_hyb_run_tail_xwin");
 }
 
 extern "C" size_t spmv_sell_split_ws_bytes(int64_t n_chunks, int32_t C)
@@ -1548,46 +1541,22 @@ extern "C" int spmv_sell_run_split(spmv_dims d, int32_t C, int32_t sigma, int32_
     if (win && n_chunks > 0 && !sell_small(C, n_slices) && bt == kBlock && !sell_ystage(bt, sigma) &&
         blocks + cblocks <= INT32_MAX && kSellSplitFused) {
         // chunks and main workgroups in one grid (sell_split_fused_kernel)
-        auto kern = ki == 2 ? (nt ? sell_split_fused_kernel<2, true, 4, kSellSplitU>
-                                  : sell_split_fused_kernel<2, false, 4, kSellSplitU>)
-                            : (nt ? sell_split_fused_kernel<1, true, 4, kSellSplitU>
-                                  : sell_split_fused_kernel<1, false, 4, kSellSplitU>);
-        hipLaunchKernelGGL(kern, dim3((unsigned)(cblocks + blocks)), dim3(kBlock), (size_t)xcap * sizeof(double), st,
-                           cblocks, C, n_slices, slice_ptr, perm, col, val, x, y, (const int2 *)win, xcap, T,
-                           n_chunks, chunk_slice, chunk_k0, part);
+        with_ki_nt(ki, nt, [&](auto KI, auto NT) {
+            hipLaunchKernelGGL((sell_split_fused_kernel<decltype(KI)::value, decltype(NT)::value, 4, kSellSplitU>),
+                               dim3((unsigned)(cblocks + blocks)), dim3(kBlock), (size_t)xcap * sizeof(double), st,
+                               cblocks, C, n_slices, slice_ptr, perm, col, val, x, y, (const int2 *)win, xcap, T,
+                               n_chunks, chunk_slice, chunk_k0, part);
+        });
         SPMV_CHECK_LAUNCH("sell_split_fused_kernel");
-        hipLaunchKernelGGL(sell_split_fix_kernel, dim3((unsigned)n_chunks), dim3(kSellFixThreads), 0, st, C, n_chunks,
-                           chunk_slice, perm, part, y);
-        SPMV_CHECK_LAUNCH("sell_split_fix_kernel");
-        return SPMV_SUCCESS;
+        return launch_sell_fix(C, n_chunks, chunk_slice, perm, part, y, st);
     }
-    if (sell_small(C, n_slices)) {
-        launch_sell_small_any(ki, nt, n_slices, slice_ptr, perm, col, val, XGlobal{x}, y, (int64_t)T, st, x,
-                              (const int2 *)win, xcap);
-    } else if (win) {
-        auto kern = ki == 2 ? (nt ? sell_xwin_kernel<2, true, 4> : sell_xwin_kernel<2, false, 4>)
-                            : (nt ? sell_xwin_kernel<1, true, 4> : sell_xwin_kernel<1, false, 4>);
-        hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(bt), (size_t)xcap * sizeof(double), st, C, n_slices,
-                           slice_ptr, perm, col, val, x, y, (const int2 *)win, xcap, (int64_t)T,
-                           xwin_remap(false) ? 1 : 0, sell_ystage(bt, sigma) ? d.n_rows : (int64_t)0);
-    } else {
-        auto kern = ki == 2 ? (nt ? sell_kernel<2, true, 4> : sell_kernel<2, false, 4>)
-                            : (nt ? sell_kernel<1, true, 4> : sell_kernel<1, false, 4>);
-        hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(bt), 0, st, C, n_slices, slice_ptr, perm, col, val,
-                           XGlobal{x}, y, 0, (int64_t)T);
-    }
+    launch_sell_main(d, C, sigma, ki, nt, bt, blocks, n_slices, slice_ptr, perm, col, val, XGlobal{x}, x, y,
+                     (int64_t)T, 0, (const int2 *)win, xcap);
     SPMV_CHECK_LAUNCH("sell kernel (split main)");
     if (n_chunks == 0)
         return SPMV_SUCCESS;
-    auto sk = ki == 2 ? (nt ? sell_split_kernel<2, true, kSellSplitU> : sell_split_kernel<2, false, kSellSplitU>)
-                      : (nt ? sell_split_kernel<1, true, kSellSplitU> : sell_split_kernel<1, false, kSellSplitU>);
-    hipLaunchKernelGGL(sk, dim3((unsigned)cblocks), dim3(kBlock), 0, st, C, n_chunks, T, slice_ptr, chunk_slice,
-                       chunk_k0, col, val, XGlobal{x}, part);
-    SPMV_CHECK_LAUNCH("sell_split_kernel");
-    hipLaunchKernelGGL(sell_split_fix_kernel, dim3((unsigned)n_chunks), dim3(kSellFixThreads), 0, st, C, n_chunks,
-                       chunk_slice, perm, part, y);
-    SPMV_CHECK_LAUNCH("sell_split_fix_kernel");
-    return SPMV_SUCCESS;
+    return launch_sell_chunks(C, ki, nt, T, n_chunks, cblocks, slice_ptr, chunk_slice, chunk_k0, perm, col, val,
+                              XGlobal{x}, part, y, st);
 }
 
 extern "C" size_t spmv_sell_hot_ws_bytes(int64_t n_chunks, int32_t C, int64_t H)
@@ -1608,7 +1577,8 @@ extern "C" int spmv_sell_run_hot(spmv_dims d, int32_t C, int32_t sigma, int32_t 
     int rc = sell_check_args(d, C, sigma, ki, n_slices, "spmv_sell_run_hot");
     if (rc != SPMV_SUCCESS)
         return rc;
-    if (T <= 0 || T % ki != 0 || n_chunks < 0 || H < 0 || d.n_cols + H > INT32_MAX)
+    // T = INT32_MAX: no split plan (every slice is narrower, so ki need not divide it)
+    if (T <= 0 || (T != INT32_MAX && T % ki != 0) || n_chunks < 0 || H < 0 || d.n_cols + H > INT32_MAX)
         return fail_msg(SPMV_OTHER_ERROR, "spmv_sell_run_hot: bad T / H");
     if (d.n_rows == 0 || n_slices == 0)
         return SPMV_SUCCESS;
@@ -1630,26 +1600,13 @@ extern "C" int spmv_sell_run_hot(spmv_dims d, int32_t C, int32_t sigma, int32_t 
                            H, hot, x, xh);
     const XHot xs{x, xh, (int32_t)d.n_cols};
     const bool nt = stream_nt(kSellStreamNtDefault);
-    if (sell_small(C, n_slices)) {
-        launch_sell_small_any(ki, nt, n_slices, slice_ptr, perm, col_hot, val, xs, y, (int64_t)T, st);
-    } else {
-        auto kern = ki == 2 ? (nt ? sell_kernel<2, true, 4, XHot> : sell_kernel<2, false, 4, XHot>)
-                            : (nt ? sell_kernel<1, true, 4, XHot> : sell_kernel<1, false, 4, XHot>);
-        hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(bt), 0, st, C, n_slices, slice_ptr, perm, col_hot, val,
-                           xs, y, 0, (int64_t)T);
-    }
+    launch_sell_main(d, C, sigma, ki, nt, bt, blocks, n_slices, slice_ptr, perm, col_hot, val, xs, x, y, (int64_t)T,
+                     0);
     SPMV_CHECK_LAUNCH("sell kernel (hot columns)");
     if (n_chunks == 0)
         return SPMV_SUCCESS;
-    auto sk = ki == 2 ? (nt ? sell_split_kernel<2, true, kSellSplitU, XHot> : sell_split_kernel<2, false, kSellSplitU, XHot>)
-                      : (nt ? sell_split_kernel<1, true, kSellSplitU, XHot> : sell_split_kernel<1, false, kSellSplitU, XHot>);
-    hipLaunchKernelGGL(sk, dim3((unsigned)cblocks), dim3(kBlock), 0, st, C, n_chunks, T, slice_ptr, chunk_slice,
-                       chunk_k0, col_hot, val, xs, part);
-    SPMV_CHECK_LAUNCH("sell_split_kernel (hot columns)");
-    hipLaunchKernelGGL(sell_split_fix_kernel, dim3((unsigned)n_chunks), dim3(kSellFixThreads), 0, st, C, n_chunks,
-                       chunk_slice, perm, part, y);
-    SPMV_CHECK_LAUNCH("sell_split_fix_kernel");
-    return SPMV_SUCCESS;
+    return launch_sell_chunks(C, ki, nt, T, n_chunks, cblocks, slice_ptr, chunk_slice, chunk_k0, perm, col_hot, val,
+                              xs, part, y, st);
 }
 
 extern "C" size_t spmv_hyb_hot_ws_bytes(int64_t tail_nnz, int64_t H)
@@ -1676,10 +1633,9 @@ extern "C" int spmv_hyb_run_hot(spmv_dims d, int32_t K, int64_t ld, int32_t ki, 
         dt.nnz = tail_nnz;
         return spmv_coo_run_hot(dt, tail_row, tail_col_hot, tail_val, x, y, H, hot, ws, ws_bytes);
     }
-    if (d.n_rows < 0 || K < 0 || ld < d.n_rows || ld % 64 != 0 || (ki != 1 && ki != 2) || K % ki != 0)
-        return fail_msg(SPMV_OTHER_ERROR, "spmv_hyb_run_hot: bad K / ld / ki");
-    if (d.n_rows == 0)
-        return SPMV_SUCCESS;
+    int rc = ell_check_args(d, K, ld, ki, "spmv_hyb_run_hot");
+    if (rc != SPMV_SUCCESS || d.n_rows == 0)
+        return rc;
     if (!hot || !ws || ws_bytes < spmv_hyb_hot_ws_bytes(tail_nnz, H))
         return fail_msg(SPMV_OTHER_ERROR, "spmv_hyb_run_hot: hot list or workspace missing");
     SPMV_GUARD(d);
@@ -1688,12 +1644,7 @@ extern "C" int spmv_hyb_run_hot(spmv_dims d, int32_t K, int64_t ld, int32_t ki, 
     hipLaunchKernelGGL(sell_hot_gather_kernel, dim3((unsigned)((H + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, H,
                        hot, x, xh);
     const XHot xs{x, xh, (int32_t)d.n_cols};
-    const int64_t blocks = (d.n_rows + kBlock - 1) / kBlock;
-    const bool nt = stream_nt(kSellStreamNtDefault);
-    auto kern = ki == 2 ? (nt ? ell_kernel<2, true, 4, XHot> : ell_kernel<2, false, 4, XHot>)
-                        : (nt ? ell_kernel<1, true, 4, XHot> : ell_kernel<1, false, 4, XHot>);
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(kBlock), 0, st, d.n_rows, K, ld, ell_col_hot, ell_val, xs,
-                       y, 0);
+    launch_ell(d, K, ld, ki, ell_col_hot, ell_val, xs, y, 0);
     SPMV_CHECK_LAUNCH("ell_kernel (hot columns)");
     if (tail_nnz == 0)
         return SPMV_SUCCESS;
@@ -1702,7 +1653,7 @@ extern "C" int spmv_hyb_run_hot(spmv_dims d, int32_t K, int64_t ld, int32_t ki, 
     int32_t *carry_row = (int32_t *)(carry_val + tiles);
     spmv_dims dt = d;
     dt.nnz = tail_nnz;
-    int rc = launch_coo_staged_acc_hot(dt, tail_row, tail_col_hot, tail_val, x, y, carry_row, carry_val, xs);
+    rc = launch_coo_staged_acc_hot(dt, tail_row, tail_col_hot, tail_val, x, y, carry_row, carry_val, xs);
     if (rc != SPMV_SUCCESS)
         return rc;
     return launch_carry(tiles, carry_row, carry_val, y, st);

@@ -349,18 +349,6 @@ void launch_csr_multi_kv(const spmv_dims &d, const int64_t *row_ptr, const int32
                        val, b.X, ldx, b.Y, ldy, b.r);
 }
 
-template <int L>
-void launch_csr_multi_l(const spmv_dims &d, const int64_t *row_ptr, const int32_t *col, const double *val,
-                        const MultiBlock &b, int64_t ldx, int64_t ldy)
-{
-    switch (b.kv) {
-    case 1: launch_csr_multi_kv<L, 1>(d, row_ptr, col, val, b, ldx, ldy); break;
-    case 2: launch_csr_multi_kv<L, 2>(d, row_ptr, col, val, b, ldx, ldy); break;
-    case 4: launch_csr_multi_kv<L, 4>(d, row_ptr, col, val, b, ldx, ldy); break;
-    default: launch_csr_multi_kv<L, 8>(d, row_ptr, col, val, b, ldx, ldy); break;
-    }
-}
-
 template <int KI, int KV, bool SELL>
 void launch_slot_multi_kv(const spmv_dims &d, int64_t slots, int32_t C, int64_t n_slices, const int64_t *slice_ptr,
                           const int32_t *perm, int32_t K, int64_t ld, const int32_t *col, const double *val,
@@ -377,27 +365,6 @@ void launch_slot_multi_kv(const spmv_dims &d, int64_t slots, int32_t C, int64_t 
                        slice_ptr, perm, K, ld, col, val, b.X, ldx, b.Y, ldy, b.r);
 }
 
-template <int KI, bool SELL>
-void launch_slot_multi_ki(const spmv_dims &d, int64_t slots, int32_t C, int64_t n_slices, const int64_t *slice_ptr,
-                          const int32_t *perm, int32_t K, int64_t ld, const int32_t *col, const double *val,
-                          const MultiBlock &b, int64_t ldx, int64_t ldy)
-{
-    switch (b.kv) {
-    case 1:
-        launch_slot_multi_kv<KI, 1, SELL>(d, slots, C, n_slices, slice_ptr, perm, K, ld, col, val, b, ldx, ldy);
-        break;
-    case 2:
-        launch_slot_multi_kv<KI, 2, SELL>(d, slots, C, n_slices, slice_ptr, perm, K, ld, col, val, b, ldx, ldy);
-        break;
-    case 4:
-        launch_slot_multi_kv<KI, 4, SELL>(d, slots, C, n_slices, slice_ptr, perm, K, ld, col, val, b, ldx, ldy);
-        break;
-    default:
-        launch_slot_multi_kv<KI, 8, SELL>(d, slots, C, n_slices, slice_ptr, perm, K, ld, col, val, b, ldx, ldy);
-        break;
-    }
-}
-
 }  // namespace
 
 int launch_csr_multi(const spmv_dims &d, int L, const int64_t *row_ptr, const int32_t *col, const double *val,
@@ -412,14 +379,11 @@ int launch_csr_multi(const spmv_dims &d, int L, const int64_t *row_ptr, const in
     SPMV_GUARD(d);
     for (int32_t j0 = 0; j0 < k; j0 += 8) {
         const MultiBlock b = multi_block(k, j0, X, ldx, Y, ldy, false);
-        switch (L) {
-        case 2: launch_csr_multi_l<2>(d, row_ptr, col, val, b, ldx, ldy); break;
-        case 4: launch_csr_multi_l<4>(d, row_ptr, col, val, b, ldx, ldy); break;
-        case 8: launch_csr_multi_l<8>(d, row_ptr, col, val, b, ldx, ldy); break;
-        case 16: launch_csr_multi_l<16>(d, row_ptr, col, val, b, ldx, ldy); break;
-        case 32: launch_csr_multi_l<32>(d, row_ptr, col, val, b, ldx, ldy); break;
-        default: launch_csr_multi_l<64>(d, row_ptr, col, val, b, ldx, ldy); break;
-        }
+        with_int<2, 4, 8, 16, 32, 64>(L, [&](auto Lc) {
+            with_int<1, 2, 4, 8>(b.kv, [&](auto KV) {
+                launch_csr_multi_kv<decltype(Lc)::value, decltype(KV)::value>(d, row_ptr, col, val, b, ldx, ldy);
+            });
+        });
         SPMV_CHECK_LAUNCH("csr_multi_kernel");
     }
     return SPMV_SUCCESS;
@@ -439,14 +403,14 @@ int launch_slot_multi(const spmv_dims &d, bool sell, int32_t ki, int32_t C, int6
     SPMV_GUARD(d);
     for (int32_t j0 = 0; j0 < k; j0 += 8) {
         const MultiBlock b = multi_block(k, j0, X, ldx, Y, ldy, true);
-        if (sell && ki == 2)
-            launch_slot_multi_ki<2, true>(d, slots, C, n_slices, slice_ptr, perm, K, ld, col, val, b, ldx, ldy);
-        else if (sell)
-            launch_slot_multi_ki<1, true>(d, slots, C, n_slices, slice_ptr, perm, K, ld, col, val, b, ldx, ldy);
-        else if (ki == 2)
-            launch_slot_multi_ki<2, false>(d, slots, C, n_slices, slice_ptr, perm, K, ld, col, val, b, ldx, ldy);
-        else
-            launch_slot_multi_ki<1, false>(d, slots, C, n_slices, slice_ptr, perm, K, ld, col, val, b, ldx, ldy);
+        with_bool(sell, [&](auto SELL) {
+            with_int<2, 1>(ki, [&](auto KI) {
+                with_int<1, 2, 4, 8>(b.kv, [&](auto KV) {
+                    launch_slot_multi_kv<decltype(KI)::value, decltype(KV)::value, decltype(SELL)::value>(
+                        d, slots, C, n_slices, slice_ptr, perm, K, ld, col, val, b, ldx, ldy);
+                });
+            });
+        });
         SPMV_CHECK_LAUNCH("slot_multi_kernel");
     }
     return SPMV_SUCCESS;

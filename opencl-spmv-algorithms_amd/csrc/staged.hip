@@ -16,6 +16,7 @@
 // out-of-bounds tail store); COO replaces the reference's CAS-atomic coo
 // kernel (reference kernels/Coo.cl:4-32) — rows that start in an earlier
 // tile go through the same deterministic carry pass as coo.hip.
+#include <stdio.h>
 #include <stdlib.h>
 
 #include "common.h"
@@ -988,35 +989,19 @@ int launch_cmrs_tiled(const spmv_dims &d, int32_t h, int64_t n_strips, const int
     int L = spmv_csr_auto_lanes(d.n_rows, d.nnz);
     while (L > 1 && L * h > kBlock)
         L >>= 1;
-#define SPMV_CMRS_TILED_R(LL, R)                                                                     \
-    do {                                                                                             \
-        if (H > 0)                                                                                   \
-            hipLaunchKernelGGL((cmrs_tiled_kernel<LL, R, XHot>), dim3((unsigned)tiles), dim3(kBlock), 0, \
-                               st, d.n_rows, h, n_strips, d.nnz, tiles, strip_ptr, rin, col, val,       \
-                               XHot{x, xh, (int32_t)d.n_cols}, y, own_lo, carry_row, carry_val);       \
-        else                                                                                         \
-            hipLaunchKernelGGL((cmrs_tiled_kernel<LL, R, XGlobal>), dim3((unsigned)tiles), dim3(kBlock), \
-                               0, st, d.n_rows, h, n_strips, d.nnz, tiles, strip_ptr, rin, col, val,    \
-                               XGlobal{x}, y, own_lo, carry_row, carry_val);                            \
-    } while (0)
-#define SPMV_CMRS_TILED(LL)                 \
-    do {                                    \
-        if (ch == 2 * kBlock)               \
-            SPMV_CMRS_TILED_R(LL, 1);       \
-        else                                \
-            SPMV_CMRS_TILED_R(LL, 3);       \
-    } while (0)
-    switch (L) {
-    case 1: SPMV_CMRS_TILED(1); break;
-    case 2: SPMV_CMRS_TILED(2); break;
-    case 4: SPMV_CMRS_TILED(4); break;
-    case 8: SPMV_CMRS_TILED(8); break;
-    case 16: SPMV_CMRS_TILED(16); break;
-    case 32: SPMV_CMRS_TILED(32); break;
-    default: SPMV_CMRS_TILED(64); break;
-    }
-#undef SPMV_CMRS_TILED
-#undef SPMV_CMRS_TILED_R
+    with_int<1, 2, 4, 8, 16, 32, 64>(L, [&](auto Lc) {
+        with_int<1, 3>(cmrs_tiled_r(d.n_rows, d.nnz), [&](auto Rc) {
+            auto go = [&](auto xs) {
+                hipLaunchKernelGGL((cmrs_tiled_kernel<decltype(Lc)::value, decltype(Rc)::value, decltype(xs)>),
+                                   dim3((unsigned)tiles), dim3(kBlock), 0, st, d.n_rows, h, n_strips, d.nnz, tiles,
+                                   strip_ptr, rin, col, val, xs, y, own_lo, carry_row, carry_val);
+            };
+            if (H > 0)
+                go(XHot{x, xh, (int32_t)d.n_cols});
+            else
+                go(XGlobal{x});
+        });
+    });
     SPMV_CHECK_LAUNCH("cmrs_tiled_kernel");
     return launch_carry((int64_t)h * tiles, carry_row, carry_val, y, st);
 }
@@ -1032,31 +1017,12 @@ int launch_cmrs_tiled(const spmv_dims &d, int32_t h, int64_t n_strips, const int
 // (0.826 / 0.831 / 0.861 ms with R = 1 / 2 / 3, profiles/round2/ab_tiled_r.log);
 // with round 3's wave-per-long-row phase the hot-table R-MAT ran 0.800 /
 // 0.785 / 0.788 ms (profiles/round3/rmat_tiled_r.log).  Workspaces and plans
-// are sized for the smallest tile (R = 1).
-static int tiled_r(int64_t n_rows, int64_t nnz)
-{
-    (void)n_rows;
-    (void)nnz;
-    return 1;
-}
+// are sized for the smallest tile (R = 1).  Only <kTiledR, true, ...> (non-
+// temporal stream loads; the plain-load variant was R = 3's) is instantiated.
+constexpr int kTiledR = 1;
 
-int64_t csr_tiled_tile(int64_t n_rows, int64_t nnz) { return 2 * kBlock * tiled_r(n_rows, nnz); }
+int64_t csr_tiled_tile(int64_t, int64_t) { return 2 * kBlock * kTiledR; }
 int64_t csr_tiled_tile_min() { return 2 * kBlock; }
-
-template <int R, typename XS, typename V>
-static void launch_tiled_r(const spmv_dims &d, int64_t tiles, const int64_t *row_ptr, const int32_t *col,
-                           const V *val, XS xs, double *y, const int32_t *own_lo, int32_t *carry_row,
-                           double *carry_val, const int32_t *big, int64_t big_len)
-{
-    const hipStream_t st = (hipStream_t)d.stream;
-    // the plain-load variant exists for R = 3 only
-    if (R == 3 && !stream_nt(true))
-        hipLaunchKernelGGL((csr_tiled_kernel<R, false, XS, V>), dim3((unsigned)tiles), dim3(kBlock), 0, st, d.n_rows,
-                           d.nnz, row_ptr, col, val, xs, y, own_lo, carry_row, carry_val, R == 1 ? big : nullptr, big_len);
-    else
-        hipLaunchKernelGGL((csr_tiled_kernel<R, true, XS, V>), dim3((unsigned)tiles), dim3(kBlock), 0, st, d.n_rows,
-                           d.nnz, row_ptr, col, val, xs, y, own_lo, carry_row, carry_val, R == 1 ? big : nullptr, big_len);
-}
 
 // A matrix of fewer than two entries (the tiled kernel loads entry pairs):
 // one workgroup, a row per thread; the carry pass that follows finds none.
@@ -1087,11 +1053,9 @@ static void launch_tiled_xs(const spmv_dims &d, int64_t tiles, const int64_t *ro
                            tiles, row_ptr, col, val, xs, y, carry_row);
         return;
     }
-    switch (tiled_r(d.n_rows, d.nnz)) {
-    case 1: launch_tiled_r<1>(d, tiles, row_ptr, col, val, xs, y, own_lo, carry_row, carry_val, big, big_len); break;
-    case 2: launch_tiled_r<2>(d, tiles, row_ptr, col, val, xs, y, own_lo, carry_row, carry_val, big, big_len); break;
-    default: launch_tiled_r<3>(d, tiles, row_ptr, col, val, xs, y, own_lo, carry_row, carry_val, big, big_len); break;
-    }
+    hipLaunchKernelGGL((csr_tiled_kernel<kTiledR, true, XS, V>), dim3((unsigned)tiles), dim3(kBlock), 0,
+                       (hipStream_t)d.stream, d.n_rows, d.nnz, row_ptr, col, val, xs, y, own_lo, carry_row, carry_val,
+                       big, big_len);
 }
 
 int launch_csr_tiled(const spmv_dims &d, const int64_t *row_ptr, const int32_t *col,
@@ -1169,31 +1133,20 @@ int launch_cmrs_staged(const spmv_dims &d, int32_t h, int64_t n_strips,
     const size_t lds = win ? (size_t)xcap * sizeof(double) : 0;
     const bool nt = stream_nt(true);  // +5 % on the cant batch (0.321 vs 0.338 ms)
     const int remap = xwin_remap(kCmrsRemapDefault) ? 1 : 0;
-#define SPMV_CMRS_STAGED(LL)                                                                            \
-    do {                                                                                                \
-        if (win && nt)                                                                             \
-            hipLaunchKernelGGL((cmrs_staged_kernel<LL, R, true, true>), dim3((unsigned)blocks),          \
-                               dim3(kBlock), lds, st, d.n_rows, h, G, n_strips, strip_ptr, rin, col, val, \
-                               x, y, win, xcap, remap);                                                 \
-        else if (win)                                                                                   \
-            hipLaunchKernelGGL((cmrs_staged_kernel<LL, R, true>), dim3((unsigned)blocks), dim3(kBlock),  \
-                               lds, st, d.n_rows, h, G, n_strips, strip_ptr, rin, col, val, x, y, win,   \
-                               xcap, remap);                                                            \
-        else                                                                                            \
-            hipLaunchKernelGGL((cmrs_staged_kernel<LL, R, false>), dim3((unsigned)blocks), dim3(kBlock), \
-                               0, st, d.n_rows, h, G, n_strips, strip_ptr, rin, col, val, x, y,          \
-                               (const int2 *)nullptr, 0);                                               \
-    } while (0)
-    switch (L) {
-    case 1: SPMV_CMRS_STAGED(1); break;
-    case 2: SPMV_CMRS_STAGED(2); break;
-    case 4: SPMV_CMRS_STAGED(4); break;
-    case 8: SPMV_CMRS_STAGED(8); break;
-    case 16: SPMV_CMRS_STAGED(16); break;
-    case 32: SPMV_CMRS_STAGED(32); break;
-    default: SPMV_CMRS_STAGED(64); break;
-    }
-#undef SPMV_CMRS_STAGED
+    // without windows: no LDS, no remap, plain loads only
+    auto go = [&](auto kern) {
+        hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(kBlock), lds, st, d.n_rows, h, G, n_strips, strip_ptr,
+                           rin, col, val, x, y, win, win ? xcap : 0, win ? remap : 0);
+    };
+    with_int<1, 2, 4, 8, 16, 32, 64>(L, [&](auto Lc) {
+        constexpr int LL = decltype(Lc)::value;
+        if (win && nt)
+            go(cmrs_staged_kernel<LL, R, true, true>);
+        else if (win)
+            go(cmrs_staged_kernel<LL, R, true>);
+        else
+            go(cmrs_staged_kernel<LL, R, false>);
+    });
     SPMV_CHECK_LAUNCH("cmrs_staged_kernel");
     return SPMV_SUCCESS;
 }
@@ -1209,6 +1162,16 @@ static int coo_hot_r(int64_t n_rows, int64_t nnz)
 }
 
 int64_t coo_hot_tile(int64_t n_rows, int64_t nnz) { return 2 * kBlock * coo_hot_r(n_rows, nnz); }
+
+// Lanes per row of the COO kernels: rows per tile ~ tile / mean row length;
+// 4 lanes per row unless rows are long: 8 lanes.  Round 6 on the cant-like
+// single pass, event-cold µs over two pairs: L=8 18.56/18.60, L=4
+// 18.44/18.54 (noise), L=16 19.40/19.36 (profiles/round6/ab_coo_lanes.md)
+static int coo_lanes(const spmv_dims &d)
+{
+    const double mean = d.n_rows > 0 ? (double)d.nnz / (double)d.n_rows : 0.0;
+    return mean >= 48.0 ? 8 : mean >= 12.0 ? 4 : 2;
+}
 
 // The single pass on fewer than two entries (its kernel loads entry pairs):
 // one workgroup; ACC adds into y, else y is written (zeros, then the entry).
@@ -1329,8 +1292,6 @@ int launch_coo_staged(const spmv_dims &d, const int32_t *row, const int32_t *col
         return fail_msg(SPMV_OTHER_ERROR, "spmv_coo_run: grid too large");
     const hipStream_t st = (hipStream_t)d.stream;
     const size_t lds = win ? (size_t)xcap * sizeof(double) : 0;
-    // rows per tile ~ tile / mean row length; 4 lanes per row unless rows are long
-    const double mean = d.n_rows > 0 ? (double)d.nnz / (double)d.n_rows : 0.0;
     // non-temporal stream loads: 0.4451 vs 0.4570 ms on the cant batch
     // (SPMV_STREAM_NT=0), three interleaved pairs on one box,
     // profiles/round2/ab_coo_nt.log
@@ -1341,53 +1302,27 @@ int launch_coo_staged(const spmv_dims &d, const int32_t *row, const int32_t *col
         SPMV_CHECK_LAUNCH("coo_tiny_kernel");
         return SPMV_SUCCESS;
     }
-#define SPMV_COO_STAGED(LL)                                                                              \
-    do {                                                                                                 \
-        if (tails)                                                                                       \
-            hipLaunchKernelGGL((coo_staged_kernel<LL, R, false, false, true, XGlobal, true, RC>),        \
-                               dim3((unsigned)tiles), dim3(kBlock), 0, st, d.n_rows, d.nnz, row, col, val, \
-                               x, y, carry_row, carry_val, (const int2 *)nullptr, 0, XGlobal{x}, tails,   \
-                               remap);                                                                   \
-        else if (win && r1)                                                                              \
-            hipLaunchKernelGGL((coo_staged_kernel<LL, 1, false, true>), dim3((unsigned)tiles),            \
-                               dim3(kBlock), lds, st, d.n_rows, d.nnz, row, col, val, x, y, carry_row,    \
-                               carry_val, win, xcap, XGlobal{x});                                        \
-        else if (win)                                                                                    \
-            hipLaunchKernelGGL((coo_staged_kernel<LL, R, false, true>), dim3((unsigned)tiles),            \
-                               dim3(kBlock), lds, st, d.n_rows, d.nnz, row, col, val, x, y, carry_row,    \
-                               carry_val, win, xcap, XGlobal{x});                                        \
-        else if (nt && r1)                                                                               \
-            hipLaunchKernelGGL((coo_staged_kernel<LL, 1, false, false, true, XGlobal, false, RC>),       \
-                               dim3((unsigned)tiles), dim3(kBlock), 0, st, d.n_rows, d.nnz, row, col, val, \
-                               x, y, carry_row, carry_val, (const int2 *)nullptr, 0, XGlobal{x});         \
-        else if (nt)                                                                                     \
-            hipLaunchKernelGGL((coo_staged_kernel<LL, R, false, false, true, XGlobal, false, RC>),       \
-                               dim3((unsigned)tiles),                                                    \
-                               dim3(kBlock), 0, st, d.n_rows, d.nnz, row, col, val, x, y, carry_row,      \
-                               carry_val, (const int2 *)nullptr, 0, XGlobal{x});                         \
-        else if (r1)                                                                                     \
-            hipLaunchKernelGGL((coo_staged_kernel<LL, 1, false, false>), dim3((unsigned)tiles),           \
-                               dim3(kBlock), 0, st, d.n_rows, d.nnz, row, col, val, x, y, carry_row,      \
-                               carry_val, (const int2 *)nullptr, 0, XGlobal{x});                         \
-        else                                                                                             \
-            hipLaunchKernelGGL((coo_staged_kernel<LL, R, false, false>), dim3((unsigned)tiles),           \
-                               dim3(kBlock), 0, st, d.n_rows, d.nnz, row, col, val, x, y, carry_row,      \
-                               carry_val, (const int2 *)nullptr, 0, XGlobal{x});                         \
-    } while (0)
-    // long rows: 8 lanes. Round 6 on the cant-like single pass, event-cold
-    // µs over two pairs: L=8 18.56/18.60, L=4 18.44/18.54 (noise), L=16
-    // 19.40/19.36 (profiles/round6/ab_coo_lanes.md)
-    if (mean >= 48.0) {
-        constexpr int RC = kCooRowCapShort;
-        SPMV_COO_STAGED(8);
-    } else if (mean >= 12.0) {
-        constexpr int RC = kCooRowCapShort;
-        SPMV_COO_STAGED(4);
-    } else {
-        constexpr int RC = kCooRowCap;
-        SPMV_COO_STAGED(2);
-    }
-#undef SPMV_COO_STAGED
+    // the single pass takes no windows; the carry pass no tail plan or remap
+    auto go = [&](auto kern) {
+        const int2 *w = tails ? nullptr : win;
+        hipLaunchKernelGGL(kern, dim3((unsigned)tiles), dim3(kBlock), w ? lds : 0, st, d.n_rows, d.nnz, row, col, val,
+                           x, y, carry_row, carry_val, w, w ? xcap : 0, XGlobal{x}, tails, tails ? remap : 0);
+    };
+    with_int<8, 4, 2>(coo_lanes(d), [&](auto Lc) {
+        with_int<1, R>(r1 ? 1 : R, [&](auto Rc) {
+            constexpr int LL = decltype(Lc)::value, RR = decltype(Rc)::value;
+            // the row cap of the non-temporal kernels (the others: the default)
+            constexpr int RC = LL == 2 ? kCooRowCap : kCooRowCapShort;
+            if (tails)  // always whole coo_staged_tile() tiles
+                go(coo_staged_kernel<LL, R, false, false, true, XGlobal, true, RC>);
+            else if (win)
+                go(coo_staged_kernel<LL, RR, false, true>);
+            else if (nt)
+                go(coo_staged_kernel<LL, RR, false, false, true, XGlobal, false, RC>);
+            else
+                go(coo_staged_kernel<LL, RR, false, false>);
+        });
+    });
     SPMV_CHECK_LAUNCH("coo_staged_kernel");
     return SPMV_SUCCESS;
 }
@@ -1405,26 +1340,13 @@ int launch_coo_staged_hot(const spmv_dims &d, const int32_t *row, const int32_t 
     const hipStream_t st = (hipStream_t)d.stream;
     launch_hot_gather(H, hot, x, xh, st);
     const XHot xs{x, xh, (int32_t)d.n_cols};
-    const double mean = d.n_rows > 0 ? (double)d.nnz / (double)d.n_rows : 0.0;
-#define SPMV_COO_HOT_R(LL, RR)                                                                           \
-    hipLaunchKernelGGL((coo_staged_kernel<LL, RR, false, false, true, XHot>), dim3((unsigned)tiles),      \
-                       dim3(kBlock), 0, st, d.n_rows, d.nnz, row, col, val, x, y, carry_row, carry_val,    \
-                       (const int2 *)nullptr, 0, xs)
-#define SPMV_COO_HOT(LL)                \
-    do {                                \
-        if (R == 1)                     \
-            SPMV_COO_HOT_R(LL, 1);      \
-        else                            \
-            SPMV_COO_HOT_R(LL, kCooR);  \
-    } while (0)
-    if (mean >= 48.0)
-        SPMV_COO_HOT(8);
-    else if (mean >= 12.0)
-        SPMV_COO_HOT(4);
-    else
-        SPMV_COO_HOT(2);
-#undef SPMV_COO_HOT
-#undef SPMV_COO_HOT_R
+    with_int<8, 4, 2>(coo_lanes(d), [&](auto Lc) {
+        with_int<1, kCooR>(R, [&](auto Rc) {
+            hipLaunchKernelGGL((coo_staged_kernel<decltype(Lc)::value, decltype(Rc)::value, false, false, true, XHot>),
+                               dim3((unsigned)tiles), dim3(kBlock), 0, st, d.n_rows, d.nnz, row, col, val, x, y,
+                               carry_row, carry_val, (const int2 *)nullptr, 0, xs);
+        });
+    });
     SPMV_CHECK_LAUNCH("coo_staged_kernel (hot columns)");
     return SPMV_SUCCESS;
 }
@@ -1465,19 +1387,33 @@ __global__ __launch_bounds__(kBlock) void cmrs_window_kernel(int64_t n_strips, i
         win[blockIdx.x] = r;
 }
 
-static int windows_xcap(const int2 *win, int64_t n, int32_t cap, hipStream_t st, int32_t *xcap,
-                        const char *who)
+int windows_download(const void *win, int64_t n, hipStream_t st, int2 **host, const char *who)
 {
+    static thread_local char msg[160];
+    *host = nullptr;
     int2 *h = (int2 *)malloc((size_t)n * sizeof(int2));
-    if (!h)
-        return fail_msg(SPMV_OTHER_ERROR, who);
+    if (!h) {
+        snprintf(msg, sizeof msg, "%s: out of host memory", who);
+        return fail_msg(SPMV_OTHER_ERROR, msg);
+    }
     hipError_t e = hipMemcpyAsync(h, win, (size_t)n * sizeof(int2), hipMemcpyDeviceToHost, st);
     if (e == hipSuccess)
         e = hipStreamSynchronize(st);
     if (e != hipSuccess) {
         free(h);
-        return fail(SPMV_PROGRAM_ERROR, who, e);
+        snprintf(msg, sizeof msg, "%s: copy windows", who);
+        return fail(SPMV_PROGRAM_ERROR, msg, e);
     }
+    *host = h;
+    return SPMV_SUCCESS;
+}
+
+int windows_xcap(const void *win, int64_t n, int32_t cap, hipStream_t st, int32_t *xcap, const char *who)
+{
+    int2 *h;
+    const int rc = windows_download(win, n, st, &h, who);
+    if (rc != SPMV_SUCCESS)
+        return rc;
     int32_t best = 0;
     for (int64_t b = 0; b < n; ++b) {
         const int64_t span = (int64_t)h[b].y - h[b].x + 1;
@@ -1517,7 +1453,7 @@ extern "C" int spmv_coo_xwin_build(spmv_dims d, const int32_t *col, void *win, s
     hipLaunchKernelGGL(tile_window_kernel, dim3((unsigned)tiles), dim3(kBlock), 0, st, d.nnz, tile, col,
                        (int2 *)win);
     SPMV_CHECK_LAUNCH("tile_window_kernel");
-    return windows_xcap((const int2 *)win, tiles, kStagedXwinCap, st, xcap, "spmv_coo_xwin_build: copy windows");
+    return windows_xcap(win, tiles, kStagedXwinCap, st, xcap, "spmv_coo_xwin_build");
 }
 
 extern "C" size_t spmv_cmrs_xwin_bytes(spmv_dims d, int32_t h, int64_t n_strips)
@@ -1550,7 +1486,7 @@ extern "C" int spmv_cmrs_xwin_build(spmv_dims d, int32_t h, int64_t n_strips, co
     hipLaunchKernelGGL(cmrs_window_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, st, n_strips, G, strip_ptr, col,
                        (int2 *)win);
     SPMV_CHECK_LAUNCH("cmrs_window_kernel");
-    return windows_xcap((const int2 *)win, blocks, kStagedXwinCap, st, xcap, "spmv_cmrs_xwin_build: copy windows");
+    return windows_xcap(win, blocks, kStagedXwinCap, st, xcap, "spmv_cmrs_xwin_build");
 }
 
 // The tile -> first owned row table of the entry-balanced CSR depends on

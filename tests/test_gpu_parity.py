@@ -260,6 +260,72 @@ def test_stream_load_policy_same_bits(torch_dev, fmt, kw):
     assert_parity(m, out[1].cpu().numpy(), x.cpu().numpy())
 
 
+# One 300 x 300 matrix with m entries in every row per branch of the launch
+# rules: COO lanes per row (mean < 12: 2, < 48: 4, else 8) and the R = 3
+# tiles of COO and CMRS (mean >= 96).
+ARM_ROW_LENGTHS = [4, 20, 64, 128]
+ARM_PARAMS = [
+    ("coo", {"coo_tail": False}),
+    ("coo", {"xwin": True}),
+    ("coo", {}),
+    ("coo", {"hot": 64}),
+    ("cmrs", {"cmrs_variant": 0, "h": 1}),
+    ("cmrs", {"cmrs_variant": 0, "h": 8}),
+    ("cmrs", {"cmrs_variant": 0, "h": 64}),
+    ("cmrs", {"cmrs_variant": 1, "h": 1}),
+    ("cmrs", {"cmrs_variant": 1, "h": 8}),
+    ("cmrs", {"cmrs_variant": 1, "h": 64}),
+    ("cmrs", {"cmrs_variant": 1, "hot": 64}),
+    ("csr", {"variant": 4}),
+    ("sell", {"C": 32, "ki": 1}),  # the sigma-window kernel
+    ("sell", {"C": 32, "ki": 2}),
+    ("sell", {"C": 64, "ki": 1}),  # the small-matrix kernel
+    ("sell", {"C": 64, "ki": 2}),
+    ("sell", {"split": 2}),
+    ("sell", {"hot": 64}),
+    ("sell16", {}),
+    ("hyb", {"hyb_k": 2}),
+    ("hyb", {"hyb_k": 2, "hot": 64}),
+    ("csr16", {}),
+    ("csrf32", {}),
+]
+ARM_IDS = [f"{f}-{'-'.join(f'{k}{v}' for k, v in kw.items()) or 'default'}" for f, kw in ARM_PARAMS]
+
+
+@pytest.fixture(scope="module")
+def arm_matrices():
+    out = {}
+    for i, n in enumerate(ARM_ROW_LENGTHS):
+        m = sa.gen_random(300, 300, n, n, 11 + i)
+        x = np.random.default_rng(5 + i).uniform(-1, 1, m.n_cols)
+        out[n] = (m, x, oracle.file_order_spmv(m.n_rows, m.row, m.col, m.val, x))
+    return out
+
+
+@pytest.mark.parametrize("fmt,kw", ARM_PARAMS, ids=ARM_IDS)
+@pytest.mark.parametrize("row_len", ARM_ROW_LENGTHS)
+def test_stream_load_policy_same_bits_every_arm(torch_dev, arm_matrices, row_len, fmt, kw):
+    """As test_stream_load_policy_same_bits, on every launcher that picks a
+    kernel by the load policy, the lanes per row or the tile size: both
+    policies give the same bits, and those pass the parity criterion."""
+    torch, dev = torch_dev
+    m, xh, y_ref = arm_matrices[row_len]
+    x = torch.from_numpy(xh).to(dev)
+    dm = sa.to_device(m, fmt, dev, **kw)
+    out = []
+    try:
+        for nt in (0, 1):
+            sa.set_option("stream_nt", nt)
+            y = torch.full((m.n_rows,), float("nan"), dtype=torch.float64, device=dev)
+            dm.run(x, y)
+            torch.cuda.synchronize()
+            out.append(y)
+    finally:
+        sa.set_option("stream_nt", None)
+    assert torch.equal(out[0].view(torch.int64), out[1].view(torch.int64))
+    assert_parity(m, out[1].cpu().numpy(), xh, y_ref=y_ref)
+
+
 @pytest.fixture(scope="module")
 def rmat_full():
     m = sa.gen_rmat()
