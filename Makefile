@@ -35,7 +35,7 @@ LIB_HIP  := $(LIBDIR)/libspmv_hip.so
 LIB_HOST := $(LIBDIR)/libspmv_host.so
 ORACLE   := oracle/liboracle.so
 
-.PHONY: all default lib oracle probes lab test-san test-cpu test-gpu clean $(TARGETS)
+.PHONY: all default lib oracle probes lab test-san test-san-transpose test-cpu test-gpu clean $(TARGETS)
 
 default: all
 all: lib $(TARGETS) probes
@@ -130,6 +130,16 @@ test-san: build/san/host_harness build/san/libspmv_host.so build/san/liboracle.s
 	  $(SANENV) build/san/bin/$$f --matrix $$m > build/san/$$f.log 2>&1; rc=$$?; \
 	  if [ $$rc -ne 0 ] && [ $$rc -ne 1 ]; then echo "$$f $$m: exit $$rc"; cat build/san/$$f.log; exit 1; fi; \
 	done; done; echo "sanitized drivers: clean (exit 0 on a GPU; 1 = no GPU found, before any input is read)"
+
+# the host side of the transposed product (spmv_csr_transpose, spmv_cpu_csr_t)
+# under ASan + UBSan: a stand-alone program over the fixtures and the refused
+# inputs (tests/san/transpose_harness.c)
+build/san/transpose_harness: tests/san/transpose_harness.c $(HOST_SRC) include/spmv_host.h include/spmv_rc.h
+	@mkdir -p build/san
+	$(CC) -std=c11 -Wall -Wextra -Werror -fopenmp -Iinclude $(SANFLAGS) $< $(HOST_SRC) -o $@ -lm
+
+test-san-transpose: build/san/transpose_harness
+	$(SANENV) ASAN_OPTIONS=detect_leaks=1:exitcode=99 build/san/transpose_harness tests/golden/*.mtx
 
 test-gpu: all oracle
 	python -m pytest tests/ -x -q -m gpu

@@ -207,6 +207,61 @@ int spmv_plan_run_multi(const spmv_plan *p, int32_t k, const double *X, int64_t 
                         double *Y, int64_t ldy, void *stream);
 /* 1 when spmv_plan_run_multi can run this plan, else 0 (also for NULL). */
 int spmv_plan_multi_supported(const spmv_plan *p);
+/* The transposed product y = A^T x on the same plan: A is n_rows x n_cols,
+ * x[n_rows], y[n_cols].  CSR plans only (every path); two modes, built by
+ * spmv_plan_prepare_transpose:
+ *   SPMV_T_SCATTER  no second copy of the matrix.  One workgroup per block
+ *       of 128 rows streams the block's entries once; a block whose columns
+ *       span at most `cap` (2,048) entries sums val * x[row] in an LDS
+ *       accumulator and adds it to y with one fp64 atomic per touched
+ *       column (consecutive lanes, consecutive columns), a wider block adds
+ *       every product straight into y with a global fp64 atomic.  The plan
+ *       owns 8 bytes per row block.  Results are NOT bitwise reproducible
+ *       from run to run (the atomics arrive in any order); they meet the
+ *       project's 1e-6 per-row criterion.  y must be ordinary device memory
+ *       (hipMalloc, torch): hardware float atomics are not defined on
+ *       fine-grained or host memory.
+ *   SPMV_T_COPY     A^T built once on the device as CSR
+ *       (spmv_dev_csr_transpose, spmv_ext.h; about 12 nnz + 8 (n_cols + 1)
+ *       plan-owned bytes) and run by an inner forward CSR plan with default
+ *       options, whose rules pick its kernel from A^T's own row lengths.
+ *       Bitwise reproducible: the bits of a forward CSR plan with default
+ *       options on the same three arrays.
+ * spmv_plan_prepare_transpose (build time) runs on the plan's d.stream and
+ * synchronises it before returning, so runs may come on any stream.
+ * Preparing the mode the plan already has is a no-op; preparing the other
+ * mode frees the first mode's buffers; SPMV_T_NONE frees everything;
+ * spmv_plan_destroy frees whatever was built.  SPMV_OTHER_ERROR with a
+ * message: NULL plan, unknown mode, a plan that is not CSR.
+ * spmv_plan_run_t follows the conventions above: asynchronous on `stream`,
+ * no allocation and no synchronisation (it can be captured into a graph on
+ * one stream), codes of spmv_rc.h.
+ *   - y[0 .. n_cols) is FULLY overwritten (columns without entries get
+ *     0.0); NO byte of y at or past n_cols is written.
+ *   - x and y must not overlap; runs of one plan must be serialised, as for
+ *     spmv_plan_run.
+ *   - SPMV_OTHER_ERROR with a message, before any device work: NULL plan,
+ *     a plan that was not prepared, NULL x with rows present, NULL y with
+ *     columns present.
+ * The transposed run reads the caller's row_ptr, col and val (never the
+ * plan's hot-renumbered column copy).  spmv_plan_get_info and its
+ * owned_bytes do not change: the transposed path reports its own bytes in
+ * spmv_transpose_info.                                                     */
+enum spmv_transpose_mode { SPMV_T_NONE = 0, SPMV_T_SCATTER = 1, SPMV_T_COPY = 2 };
+typedef struct spmv_transpose_info {
+    int32_t mode;          /* enum spmv_transpose_mode */
+    int32_t cap;           /* scatter: LDS accumulator entries per workgroup */
+    int64_t blocks;        /* scatter: row blocks */
+    int64_t lds_blocks;    /* scatter: row blocks whose column span fits cap */
+    int64_t flush_entries; /* scatter: y entries added by window flushes per run (sum of those spans) */
+    int64_t owned_bytes;   /* device bytes the transposed path allocated */
+    char kernel[64];       /* dominant kernel, as spmv_plan_info.kernel */
+} spmv_transpose_info;
+/* 1: CSR plans (every path); 0 otherwise and for NULL */
+int spmv_plan_transpose_supported(const spmv_plan *p);
+int spmv_plan_prepare_transpose(spmv_plan *p, int mode);
+int spmv_plan_get_transpose_info(const spmv_plan *p, spmv_transpose_info *info);
+int spmv_plan_run_t(const spmv_plan *p, const double *x, double *y, void *stream);
 int spmv_plan_get_info(const spmv_plan *p, spmv_plan_info *info);
 /* Frees what the plan allocated (never the caller's arrays). */
 int spmv_plan_destroy(spmv_plan *p);

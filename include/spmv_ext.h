@@ -372,6 +372,16 @@ int spmv_dev_sell_fill(spmv_dims d, const int64_t *row_ptr, const int32_t *col, 
                        double *val_out);
 int spmv_dev_cmrs_build(spmv_dims d, const int64_t *row_ptr, int32_t h, int64_t *strip_ptr,
                         uint8_t *row_in_strip);
+/* A^T as CSR from a CSR already in HBM (d = the dims of A; row_ptr[0] = 0):
+ * t_ptr[n_cols+1], t_col[nnz] (row ids of A), t_val[nnz].  A stable radix
+ * sort of the column keys over ceil(log2 n_cols) bits with the entry index
+ * as payload, then a gather: inside a row of A^T the entries keep their
+ * position in A's CSR (increasing row of A, duplicates in their CSR order),
+ * element for element spmv_csr_transpose (spmv_host.h).  A column outside
+ * [0, n_cols) returns SPMV_OTHER_ERROR.  Same rules as the builders above:
+ * own scratch, d.stream, synchronised before returning.                  */
+int spmv_dev_csr_transpose(spmv_dims d, const int64_t *row_ptr, const int32_t *col, const double *val,
+                           int64_t *t_ptr, int32_t *t_col, double *t_val);
 
 /* ------------------------------------------------- iterated SpMV -------
  * Vector kernels for power iteration / CG over row shards (SURVEY.md §8f

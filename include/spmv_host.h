@@ -73,6 +73,16 @@ int spmv_coo_sort_by_row(int64_t n_rows, int64_t nnz, const int32_t *row,
 int spmv_csr_from_coo(int64_t n_rows, int64_t nnz, const int32_t *row,
                       const int32_t *col, const double *val,
                       int64_t *row_ptr, int32_t *col_out, double *val_out);
+/* A^T as CSR from the CSR of an n_rows x n_cols matrix (row_ptr[0] = 0):
+ * stable counting sort by column.  t_ptr[n_cols+1], t_col[nnz] (row ids of
+ * A), t_val[nnz]; inside a row of A^T the entries keep their position in A's
+ * CSR (increasing row of A, duplicates in their CSR order) — element for
+ * element the device builder spmv_dev_csr_transpose (spmv_ext.h).
+ * SPMV_OTHER_ERROR for negative sizes, n_rows > INT32_MAX, a column outside
+ * [0, n_cols) or a NULL array that would be read or written.             */
+int spmv_csr_transpose(int64_t n_rows, int64_t n_cols, const int64_t *row_ptr,
+                       const int32_t *col, const double *val,
+                       int64_t *t_ptr, int32_t *t_col, double *t_val);
 /* Entries of every CSR row reordered by increasing column (stable).  With
  * degree-relabelled columns (spmv_column_relabel) a long row then reads x
  * from its dense hot prefix in address order.  Changes each row's
@@ -278,6 +288,13 @@ int spmv_cpu_csr(int64_t n_rows, const int64_t *row_ptr, const int32_t *col,
 int spmv_cpu_csr_multi(int64_t n_rows, const int64_t *row_ptr, const int32_t *col,
                        const double *val, int32_t k, const double *X, int64_t ldx,
                        double *Y, int64_t ldy);
+/* y = A^T x (x[n_rows], y[n_cols]): zeroes y[0 .. n_cols), then scatters
+ * val * x[row] row by row.  Serial and deterministic: the CPU statement of
+ * spmv_plan_run_t (spmv.h), never a device fallback.  SPMV_OTHER_ERROR for
+ * negative sizes, a column outside [0, n_cols) or a NULL array that would be
+ * read or written (nothing of y past a bad entry's row is touched).       */
+int spmv_cpu_csr_t(int64_t n_rows, int64_t n_cols, const int64_t *row_ptr,
+                   const int32_t *col, const double *val, const double *x, double *y);
 int spmv_cpu_ell(int64_t n_rows, int32_t K, int64_t ld, int32_t ki,
                  const int32_t *col, const double *val, const double *x,
                  double *y, int threads);

@@ -16,7 +16,9 @@
 //         64-bit keys in LDS — slice widths = longest row of the slice,
 //         padding column = the row's last column, else the first column of
 //         the first non-empty row of the slice;
-//   CMRS  strip_ptr from row_ptr, row_in_strip = row % h.
+//   CMRS  strip_ptr from row_ptr, row_in_strip = row % h;
+//   A^T   CSR of the transpose from a CSR (spmv_dev_csr_transpose): the same
+//         stable sort over the column keys, rows of A as the new columns.
 // Builders allocate their scratch, run on d.stream and synchronise it
 // before returning (build time, never on the SpMV path).
 #include <hipcub/hipcub.hpp>
@@ -130,6 +132,74 @@ static int csr_from_coo_impl(const spmv_dims &d, const int32_t *row, const int32
         (e = hipStreamSynchronize(st)) != hipSuccess)
         return fail(SPMV_PROGRAM_ERROR, "spmv_dev_csr_from_coo: sync", e);
     return h_bad ? fail_msg(SPMV_OTHER_ERROR, "spmv_dev_csr_from_coo: row index out of range") : SPMV_SUCCESS;
+}
+
+// --------------------------------------------------------- CSR transpose
+// Entry i of A^T (sorted position) is entry j = idx[i] of A: its value, and
+// as its column the row of A that holds j, the last r with row_ptr[r] <= j
+// (a binary search; empty rows share their offset with the next row).
+template <typename I>
+__global__ void transpose_gather_kernel(int64_t nnz, int64_t n_rows, const I *__restrict__ idx,
+                                        const int64_t *__restrict__ row_ptr, const double *__restrict__ val,
+                                        int32_t *__restrict__ t_col, double *__restrict__ t_val)
+{
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nnz; i += stride) {
+        const int64_t j = (int64_t)idx[i];
+        int64_t lo = 0, hi = n_rows;  // row_ptr[lo] <= j < row_ptr[hi]
+        while (hi - lo > 1) {
+            const int64_t mid = lo + (hi - lo) / 2;
+            if (row_ptr[mid] <= j)
+                lo = mid;
+            else
+                hi = mid;
+        }
+        t_col[i] = (int32_t)lo;
+        t_val[i] = val[j];
+    }
+}
+
+template <typename I>
+static int csr_transpose_impl(const spmv_dims &d, const int64_t *row_ptr, const int32_t *col, const double *val,
+                              int64_t *t_ptr, int32_t *t_col, double *t_val)
+{
+    const hipStream_t st = (hipStream_t)d.stream;
+    const int64_t nnz = d.nnz, n = d.n_cols;
+    Scratch keys_in, keys_out, idx_in, idx_out, bad, tmp;
+    hipError_t e;
+    if ((e = keys_in.alloc(nnz * 4)) != hipSuccess || (e = keys_out.alloc(nnz * 4)) != hipSuccess ||
+        (e = idx_in.alloc(nnz * sizeof(I))) != hipSuccess || (e = idx_out.alloc(nnz * sizeof(I))) != hipSuccess ||
+        (e = bad.alloc(sizeof(int))) != hipSuccess)
+        return fail(SPMV_PROGRAM_ERROR, "spmv_dev_csr_transpose: scratch", e);
+    if ((e = hipMemsetAsync(bad.p, 0, sizeof(int), st)) != hipSuccess)
+        return fail(SPMV_PROGRAM_ERROR, "spmv_dev_csr_transpose: memset", e);
+    // the column keys, range-checked (the row check of the COO builder)
+    hipLaunchKernelGGL(coo_rows_check_kernel, dim3(grid_for(nnz)), dim3(kBlock), 0, st, nnz, n, col,
+                       (uint32_t *)keys_in.p, (int *)bad.p);
+    hipLaunchKernelGGL((iota_kernel<I>), dim3(grid_for(nnz)), dim3(kBlock), 0, st, nnz, (I *)idx_in.p);
+    int end_bit = 1;
+    while (end_bit < 32 && ((int64_t)1 << end_bit) < n)
+        ++end_bit;
+    size_t tbytes = 0;
+    e = hipcub::DeviceRadixSort::SortPairs(nullptr, tbytes, (const uint32_t *)keys_in.p, (uint32_t *)keys_out.p,
+                                           (const I *)idx_in.p, (I *)idx_out.p, nnz, 0, end_bit, st);
+    if (e == hipSuccess)
+        e = tmp.alloc(tbytes);
+    if (e == hipSuccess)
+        e = hipcub::DeviceRadixSort::SortPairs(tmp.p, tbytes, (const uint32_t *)keys_in.p, (uint32_t *)keys_out.p,
+                                               (const I *)idx_in.p, (I *)idx_out.p, nnz, 0, end_bit, st);
+    if (e != hipSuccess)
+        return fail(SPMV_PROGRAM_ERROR, "spmv_dev_csr_transpose: radix sort", e);
+    hipLaunchKernelGGL(row_ptr_from_sorted_kernel, dim3(grid_for(nnz + 1)), dim3(kBlock), 0, st, nnz, n,
+                       (const uint32_t *)keys_out.p, t_ptr);
+    hipLaunchKernelGGL((transpose_gather_kernel<I>), dim3(grid_for(nnz)), dim3(kBlock), 0, st, nnz, d.n_rows,
+                       (const I *)idx_out.p, row_ptr, val, t_col, t_val);
+    SPMV_CHECK_LAUNCH("csr transpose kernels");
+    int h_bad = 0;
+    if ((e = hipMemcpyAsync(&h_bad, bad.p, sizeof(int), hipMemcpyDeviceToHost, st)) != hipSuccess ||
+        (e = hipStreamSynchronize(st)) != hipSuccess)
+        return fail(SPMV_PROGRAM_ERROR, "spmv_dev_csr_transpose: sync", e);
+    return h_bad ? fail_msg(SPMV_OTHER_ERROR, "spmv_dev_csr_transpose: column index out of range") : SPMV_SUCCESS;
 }
 
 // ------------------------------------------------------------------ ELL
@@ -329,6 +399,24 @@ extern "C" int spmv_dev_csr_from_coo(spmv_dims d, const int32_t *row, const int3
     return d.nnz <= (int64_t)UINT32_MAX
                ? csr_from_coo_impl<uint32_t>(d, row, col, val, row_ptr, col_out, val_out)
                : csr_from_coo_impl<uint64_t>(d, row, col, val, row_ptr, col_out, val_out);
+}
+
+extern "C" int spmv_dev_csr_transpose(spmv_dims d, const int64_t *row_ptr, const int32_t *col, const double *val,
+                                      int64_t *t_ptr, int32_t *t_col, double *t_val)
+{
+    if (d.n_rows < 0 || d.n_cols < 0 || d.nnz < 0 || d.n_rows > INT32_MAX || d.n_cols > INT32_MAX)
+        return fail_msg(SPMV_OTHER_ERROR, "spmv_dev_csr_transpose: bad sizes");
+    if (!t_ptr || (d.nnz > 0 && (!row_ptr || !col || !val || !t_col || !t_val)))
+        return fail_msg(SPMV_OTHER_ERROR, "spmv_dev_csr_transpose: NULL array");
+    SPMV_GUARD(d);
+    if (d.nnz == 0) {
+        hipError_t e = hipMemsetAsync(t_ptr, 0, (size_t)(d.n_cols + 1) * sizeof(int64_t), (hipStream_t)d.stream);
+        if (e == hipSuccess)
+            e = hipStreamSynchronize((hipStream_t)d.stream);
+        return e == hipSuccess ? SPMV_SUCCESS : fail(SPMV_PROGRAM_ERROR, "spmv_dev_csr_transpose", e);
+    }
+    return d.nnz <= (int64_t)UINT32_MAX ? csr_transpose_impl<uint32_t>(d, row_ptr, col, val, t_ptr, t_col, t_val)
+                                        : csr_transpose_impl<uint64_t>(d, row_ptr, col, val, t_ptr, t_col, t_val);
 }
 
 extern "C" int spmv_dev_ell_plan(spmv_dims d, const int64_t *row_ptr, int32_t ki, int32_t *K, int64_t *ld)

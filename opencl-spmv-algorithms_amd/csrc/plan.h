@@ -1,0 +1,58 @@
+// plan.h — struct spmv_plan, private to the library: built and run by
+// plan.hip, extended with the transposed path (y = A^T x) by transpose.hip.
+#pragma once
+
+#include "common.h"
+
+struct spmv_plan {
+    int fmt;  // SPMV_FMT_*
+    int path; // PlanPath (plan.hip)
+    spmv_dims d;
+    spmv_plan_opts o;
+    // the caller's arrays (device)
+    const int64_t *ptr = nullptr;  // CSR row_ptr / SELL slice_ptr / CMRS strip_ptr
+    const int32_t *row = nullptr, *col = nullptr, *perm = nullptr;
+    const uint8_t *rin = nullptr;
+    const double *val = nullptr;
+    // geometry
+    int32_t K = 0, C = 0, sigma = 0, ki = 0, h = 0, lanes = 0, variant = 0, xwin_rows = 0;
+    int64_t ld = 0, n_slices = 0, n_strips = 0;
+    // owned by the plan (device)
+    void *win = nullptr;
+    int32_t xcap = 0;
+    void *head = nullptr;
+    size_t head_bytes = 0;
+    void *tails = nullptr;
+    void *ws = nullptr;
+    size_t ws_bytes = 0;
+    int32_t *own_lo = nullptr;
+    int32_t *big = nullptr;
+    int64_t big_len = 0, big_tiles = 0, big_tile = 0;
+    int32_t split_T = 0;
+    bool tiles_planned = false;  // tiled CMRS: the tile -> first-strip table filled at build
+    int64_t n_chunks = 0;
+    int32_t *chunk_slice = nullptr, *chunk_k0 = nullptr;
+    uint16_t *col16 = nullptr;
+    int32_t *hcol = nullptr;  // the columns with hot ids (plan-owned), or NULL
+    int32_t *hot = nullptr;   // hot[H]: the hot columns in rank order
+    int64_t H = 0;
+    size_t owned = 0;
+    char kernel[64] = "";
+    char desc[320] = "";
+    // the transposed path (spmv_plan_prepare_transpose, transpose.hip); its
+    // bytes are counted in t_owned, never in `owned`
+    int32_t t_mode = 0;        // enum spmv_transpose_mode
+    int32_t t_xcap = 0;        // scatter: LDS accumulator entries of a run (widest window that fits the cap)
+    int64_t t_blocks = 0, t_lds_blocks = 0, t_flush = 0;
+    void *t_win = nullptr;     // scatter: int2 {lo, hi} column range per row block
+    int64_t *t_ptr = nullptr;  // copy: A^T as CSR (t_ptr[n_cols+1], t_col/t_val[nnz])
+    int32_t *t_col = nullptr;
+    double *t_val = nullptr;
+    spmv_plan *t_inner = nullptr;  // copy: the forward CSR plan over A^T
+    size_t t_owned = 0;
+};
+
+namespace spmv {
+// frees what spmv_plan_prepare_transpose built (the plan's device is current)
+void plan_transpose_free(spmv_plan *p);
+}  // namespace spmv

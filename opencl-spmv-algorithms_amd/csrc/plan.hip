@@ -23,6 +23,7 @@
 #include <new>
 
 #include "common.h"
+#include "plan.h"
 #include "spmv_host.h"
 
 namespace spmv {
@@ -79,43 +80,6 @@ __global__ __launch_bounds__(kBlock) void max_len_kernel(int64_t n, const int64_
 }  // namespace spmv
 
 using namespace spmv;
-
-struct spmv_plan {
-    int fmt;  // SPMV_FMT_*
-    int path; // PlanPath
-    spmv_dims d;
-    spmv_plan_opts o;
-    // the caller's arrays (device)
-    const int64_t *ptr = nullptr;  // CSR row_ptr / SELL slice_ptr / CMRS strip_ptr
-    const int32_t *row = nullptr, *col = nullptr, *perm = nullptr;
-    const uint8_t *rin = nullptr;
-    const double *val = nullptr;
-    // geometry
-    int32_t K = 0, C = 0, sigma = 0, ki = 0, h = 0, lanes = 0, variant = 0, xwin_rows = 0;
-    int64_t ld = 0, n_slices = 0, n_strips = 0;
-    // owned by the plan (device)
-    void *win = nullptr;
-    int32_t xcap = 0;
-    void *head = nullptr;
-    size_t head_bytes = 0;
-    void *tails = nullptr;
-    void *ws = nullptr;
-    size_t ws_bytes = 0;
-    int32_t *own_lo = nullptr;
-    int32_t *big = nullptr;
-    int64_t big_len = 0, big_tiles = 0, big_tile = 0;
-    int32_t split_T = 0;
-    bool tiles_planned = false;  // tiled CMRS: the tile -> first-strip table filled at build
-    int64_t n_chunks = 0;
-    int32_t *chunk_slice = nullptr, *chunk_k0 = nullptr;
-    uint16_t *col16 = nullptr;
-    int32_t *hcol = nullptr;  // the columns with hot ids (plan-owned), or NULL
-    int32_t *hot = nullptr;   // hot[H]: the hot columns in rank order
-    int64_t H = 0;
-    size_t owned = 0;
-    char kernel[64] = "";
-    char desc[320] = "";
-};
 
 namespace {
 
@@ -294,6 +258,7 @@ int spmv_plan_destroy(spmv_plan *p)
     (void)hipGetDevice(&dev);
     if (dev != p->d.device)
         (void)hipSetDevice(p->d.device);
+    plan_transpose_free(p);
     for (void *q : owned)
         if (q)
             (void)hipFree(q);

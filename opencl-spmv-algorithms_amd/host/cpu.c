@@ -76,6 +76,27 @@ int spmv_cpu_csr_multi(int64_t n_rows, const int64_t *row_ptr, const int32_t *co
     return SPMV_SUCCESS;
 }
 
+/* y = A^T x: y[0 .. n_cols) zeroed, then one serial scatter row by row (the
+ * deterministic CPU statement of spmv_plan_run_t).                         */
+int spmv_cpu_csr_t(int64_t n_rows, int64_t n_cols, const int64_t *row_ptr,
+                   const int32_t *col, const double *val, const double *x, double *y)
+{
+    if (n_rows < 0 || n_cols < 0 || !row_ptr || (n_cols > 0 && !y))
+        return SPMV_OTHER_ERROR;
+    if (row_ptr[n_rows] > row_ptr[0] && (!col || !val || !x))
+        return SPMV_OTHER_ERROR;
+    if (n_cols > 0)
+        memset(y, 0, (size_t)n_cols * sizeof(double));
+    for (int64_t r = 0; r < n_rows; ++r) {
+        for (int64_t e = row_ptr[r]; e < row_ptr[r + 1]; ++e) {
+            if (col[e] < 0 || col[e] >= n_cols)
+                return SPMV_OTHER_ERROR;
+            y[col[e]] += val[e] * x[r];
+        }
+    }
+    return SPMV_SUCCESS;
+}
+
 int spmv_cpu_ell(int64_t n_rows, int32_t K, int64_t ld, int32_t ki,
                  const int32_t *col, const double *val, const double *x,
                  double *y, int threads)

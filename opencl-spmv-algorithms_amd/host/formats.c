@@ -81,6 +81,39 @@ int spmv_csr_from_coo(int64_t n_rows, int64_t nnz, const int32_t *row,
     return SPMV_SUCCESS;
 }
 
+/* A^T as CSR: the stable counting sort of spmv_csr_from_coo over the column
+ * keys, the row of A as the new column. */
+int spmv_csr_transpose(int64_t n_rows, int64_t n_cols, const int64_t *row_ptr,
+                       const int32_t *col, const double *val,
+                       int64_t *t_ptr, int32_t *t_col, double *t_val)
+{
+    if (n_rows < 0 || n_cols < 0 || n_rows > INT32_MAX || !row_ptr || !t_ptr)
+        return SPMV_OTHER_ERROR;
+    const int64_t nnz = row_ptr[n_rows];
+    if (nnz < 0 || (nnz > 0 && (!col || !val || !t_col || !t_val)))
+        return SPMV_OTHER_ERROR;
+    memset(t_ptr, 0, ((size_t)n_cols + 1) * sizeof(int64_t));
+    for (int64_t e = 0; e < nnz; ++e) {
+        if (col[e] < 0 || col[e] >= n_cols)
+            return SPMV_OTHER_ERROR;
+        t_ptr[col[e] + 1]++;
+    }
+    for (int64_t c = 0; c < n_cols; ++c)
+        t_ptr[c + 1] += t_ptr[c];
+    /* stable scatter: t_ptr[c] is the cursor, shifted back afterwards */
+    for (int64_t r = 0; r < n_rows; ++r) {
+        for (int64_t e = row_ptr[r]; e < row_ptr[r + 1]; ++e) {
+            int64_t p = t_ptr[col[e]]++;
+            t_col[p] = (int32_t)r;
+            t_val[p] = val[e];
+        }
+    }
+    for (int64_t c = n_cols; c > 0; --c)
+        t_ptr[c] = t_ptr[c - 1];
+    t_ptr[0] = 0;
+    return SPMV_SUCCESS;
+}
+
 int spmv_csr_row_stats(int64_t n_rows, const int64_t *row_ptr,
                        int64_t *min_len, int64_t *max_len, double *mean_len)
 {

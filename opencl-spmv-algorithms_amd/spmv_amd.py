@@ -104,6 +104,16 @@ class PlanInfo(ctypes.Structure):
                [("kernel", ctypes.c_char * 64), ("desc", ctypes.c_char * 320)]
 
 
+class TransposeInfo(ctypes.Structure):
+    """``spmv_transpose_info`` (include/spmv.h)."""
+
+    _fields_ = [("mode", _c_i32), ("cap", _c_i32)] + \
+               [(k, _c_i64) for k in ("blocks", "lds_blocks", "flush_entries", "owned_bytes")] + \
+               [("kernel", ctypes.c_char * 64)]
+
+
+TRANSPOSE_MODES = {None: 0, "scatter": 1, "copy": 2}  # enum spmv_transpose_mode
+
 _PP = ctypes.POINTER(_vp)
 _PO = ctypes.POINTER(PlanOpts)
 
@@ -118,6 +128,10 @@ HIP_SYMBOLS = {
     "spmv_plan_run": (ctypes.c_int, [_vp, _vp, _vp, _vp]),
     "spmv_plan_run_multi": (ctypes.c_int, [_vp, _c_i32, _vp, _c_i64, _vp, _c_i64, _vp]),
     "spmv_plan_multi_supported": (ctypes.c_int, [_vp]),
+    "spmv_plan_transpose_supported": (ctypes.c_int, [_vp]),
+    "spmv_plan_prepare_transpose": (ctypes.c_int, [_vp, ctypes.c_int]),
+    "spmv_plan_get_transpose_info": (ctypes.c_int, [_vp, ctypes.POINTER(TransposeInfo)]),
+    "spmv_plan_run_t": (ctypes.c_int, [_vp, _vp, _vp, _vp]),
     "spmv_plan_get_info": (ctypes.c_int, [_vp, ctypes.POINTER(PlanInfo)]),
     "spmv_plan_destroy": (ctypes.c_int, [_vp]),
     "spmv_set_option": (ctypes.c_int, [ctypes.c_int, ctypes.c_int]),
@@ -210,6 +224,7 @@ HIP_SYMBOLS = {
     "spmv_gen_banded_device": (ctypes.c_int, [_c_i64, ctypes.c_uint64, _c_i64, _c_i64, ctypes.c_int, _c_i32,
                                               _c_i32, _vp, _vp, _vp, _vp, ctypes.c_int, _vp]),
     "spmv_dev_csr_from_coo": (ctypes.c_int, [Dims, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "spmv_dev_csr_transpose": (ctypes.c_int, [Dims, _vp, _vp, _vp, _vp, _vp, _vp]),
     "spmv_dev_ell_plan": (ctypes.c_int, [Dims, _vp, _c_i32, ctypes.POINTER(_c_i32), ctypes.POINTER(_c_i64)]),
     "spmv_dev_ell_fill": (ctypes.c_int, [Dims, _vp, _vp, _vp, _c_i32, _c_i64, _c_i32, _vp, _vp]),
     "spmv_dev_sell_plan": (ctypes.c_int, [Dims, _vp, _vp, _c_i32, _c_i32, _c_i32, _c_i64, _vp, _vp, _vp,
@@ -263,6 +278,7 @@ HOST_SYMBOLS = {
     "spmv_bin_read": (ctypes.c_int, [ctypes.c_char_p, ctypes.POINTER(MtxInfo), _vp, _vp, _vp]),
     "spmv_coo_sort_by_row": (ctypes.c_int, [_c_i64, _c_i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "spmv_csr_from_coo": (ctypes.c_int, [_c_i64, _c_i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "spmv_csr_transpose": (ctypes.c_int, [_c_i64, _c_i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "spmv_csr_sort_rows": (ctypes.c_int, [_c_i64, _vp, _vp, _vp]),
     "spmv_csr_row_stats": (ctypes.c_int, [_c_i64, _vp, ctypes.POINTER(_c_i64), ctypes.POINTER(_c_i64), ctypes.POINTER(ctypes.c_double)]),
     "spmv_csr_pick_variant": (ctypes.c_int, [_c_i64, _vp]),
@@ -298,6 +314,7 @@ HOST_SYMBOLS = {
     "spmv_cpu_coo": (ctypes.c_int, [_c_i64, _c_i64, _vp, _vp, _vp, _vp, _vp, ctypes.c_int]),
     "spmv_cpu_csr": (ctypes.c_int, [_c_i64, _vp, _vp, _vp, _vp, _vp, ctypes.c_int]),
     "spmv_cpu_csr_multi": (ctypes.c_int, [_c_i64, _vp, _vp, _vp, _c_i32, _vp, _c_i64, _vp, _c_i64]),
+    "spmv_cpu_csr_t": (ctypes.c_int, [_c_i64, _c_i64, _vp, _vp, _vp, _vp, _vp]),
     "spmv_cpu_ell": (ctypes.c_int, [_c_i64, _c_i32, _c_i64, _c_i32, _vp, _vp, _vp, _vp, ctypes.c_int]),
     "spmv_cpu_sell": (ctypes.c_int, [_c_i64, _c_i32, _c_i32, _c_i64, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_int]),
     "spmv_cpu_cmrs": (ctypes.c_int, [_c_i64, _c_i32, _c_i64, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_int]),
@@ -465,6 +482,30 @@ def csr_from_coo(m: Coo):
     _check_host(host_lib().spmv_csr_from_coo(m.n_rows, m.nnz, _ptr(m.row), _ptr(m.col), _ptr(m.val),
                                              _ptr(ptr), _ptr(col), _ptr(val)), "csr_from_coo")
     return ptr, col, val
+
+
+def csr_transpose(n_rows: int, n_cols: int, ptr, col, val):
+    """A^T as CSR (spmv_csr_transpose) -> (t_ptr[n_cols+1], t_col, t_val): a
+    stable counting sort by column, t_col the row ids of A."""
+    nnz = int(ptr[n_rows])
+    t_ptr = np.empty(n_cols + 1, np.int64)
+    t_col = np.empty(nnz, np.int32)
+    t_val = np.empty(nnz, np.float64)
+    _check_host(host_lib().spmv_csr_transpose(n_rows, n_cols, _ptr(ptr), _ptr(col), _ptr(val), _ptr(t_ptr),
+                                              _ptr(t_col), _ptr(t_val)), "csr_transpose")
+    return t_ptr, t_col, t_val
+
+
+def cpu_csr_t(n_rows: int, n_cols: int, ptr, col, val, x: np.ndarray, y: np.ndarray) -> None:
+    """Host y = A^T x (spmv_cpu_csr_t): x has n_rows entries; y[:n_cols] is
+    overwritten, nothing past it."""
+    for a, n in ((x, n_rows), (y, n_cols)):
+        if not isinstance(a, np.ndarray) or a.dtype != np.float64 or a.ndim != 1 or not a.flags.c_contiguous:
+            raise SpmvError(OTHER_ERROR, "cpu_csr_t", "x and y must be contiguous 1-D float64 arrays")
+        if a.size < n:
+            raise SpmvError(OTHER_ERROR, "cpu_csr_t", "x or y too short")
+    _check_host(host_lib().spmv_cpu_csr_t(n_rows, n_cols, _ptr(ptr), _ptr(col), _ptr(val), _ptr(x), _ptr(y)),
+                "spmv_cpu_csr_t")
 
 
 def csr_sort_rows(n_rows: int, ptr, col, val) -> None:
@@ -906,6 +947,57 @@ class DeviceMatrix:
         _check(hip_lib().spmv_plan_run_multi(self.plan, k, _ptr(X), ldx, _ptr(Y), ldy, st.cuda_stream),
                f"spmv_plan_run_multi ({self.fmt})")
 
+    @property
+    def transpose_supported(self) -> bool:
+        """prepare_transpose / run_t can run this matrix (spmv_plan_transpose_supported)."""
+        return self.plan is not None and bool(hip_lib().spmv_plan_transpose_supported(self.plan))
+
+    def prepare_transpose(self, mode="scatter") -> None:
+        """Build what run_t needs (spmv_plan_prepare_transpose, build time):
+        "scatter" (no second copy of the matrix, fp64 atomics, not bitwise
+        reproducible), "copy" (A^T built on the device and run by the forward
+        kernels, reproducible) or None (free everything)."""
+        if mode not in TRANSPOSE_MODES:
+            raise SpmvError(OTHER_ERROR, "prepare_transpose", 'mode must be "scatter", "copy" or None')
+        if self.plan is None:
+            raise SpmvError(OTHER_ERROR, "prepare_transpose", f"format {self.fmt} has no plan: no transposed run")
+        _check(hip_lib().spmv_plan_prepare_transpose(self.plan, TRANSPOSE_MODES[mode]),
+               f"spmv_plan_prepare_transpose ({self.fmt})")
+
+    @property
+    def transpose_info(self) -> dict:
+        """spmv_transpose_info as a dict; mode is None, "scatter" or "copy"."""
+        if self.plan is None:
+            raise SpmvError(OTHER_ERROR, "transpose_info", f"format {self.fmt} has no plan")
+        info = TransposeInfo()
+        _check(hip_lib().spmv_plan_get_transpose_info(self.plan, ctypes.byref(info)), "spmv_plan_get_transpose_info")
+        out = {k: int(getattr(info, k)) for k in ("cap", "blocks", "lds_blocks", "flush_entries", "owned_bytes")}
+        out["mode"] = {v: k for k, v in TRANSPOSE_MODES.items()}[info.mode]
+        out["kernel"] = info.kernel.decode()
+        return out
+
+    def run_t(self, x, y, stream=None) -> None:
+        """y = A^T x on `stream` (spmv_plan_run_t): x has >= n_rows entries,
+        y[:n_cols] is overwritten.  Needs prepare_transpose first."""
+        torch = _torch()
+        for t in (x, y):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float64:
+                raise SpmvError(OTHER_ERROR, "run_t", "x and y must be float64 tensors")
+        if x.numel() < self.n_rows or y.numel() < self.n_cols:
+            raise SpmvError(OTHER_ERROR, "run_t", "x or y too short")
+        if not (x.is_contiguous() and y.is_contiguous()):
+            raise SpmvError(OTHER_ERROR, "run_t", "x and y must be contiguous")
+        here = torch.device(self.device)
+        idx = here.index or 0
+        for t in (x, y):
+            if t.device.type != here.type or (t.device.index or 0) != idx:
+                raise SpmvError(OTHER_ERROR, "run_t", f"x and y must be on {here.type}:{idx}")
+        if self.plan is None:
+            raise SpmvError(OTHER_ERROR, "run_t", f"format {self.fmt} has no plan: no transposed run")
+        st = stream if stream is not None else torch.cuda.current_stream(here)
+        _check(hip_lib().spmv_plan_run_t(self.plan, _ptr(x), _ptr(y), st.cuda_stream),
+               f"spmv_plan_run_t ({self.fmt})")
+
 
 # the library's A/B switches (include/spmv_ext.h; placement and load policy only)
 OPTIONS = {"xwin_remap": 1, "xcd_remap": 2, "stream_nt": 3, "csr_prefetch": 4}
@@ -1249,6 +1341,22 @@ def device_build(m: Coo, fmt: str, device="cuda:0", *, lanes: int = 0, ki: int =
         _plan_cmrs(dm, variant=cmrs_variant, xwin=xwin)
     dm.arrays["row_ptr_csr"] = ptr
     return dm
+
+
+def dev_csr_transpose(dm: DeviceMatrix):
+    """A^T of a CSR DeviceMatrix as CSR, built on the device
+    (spmv_dev_csr_transpose) -> (t_ptr[n_cols+1], t_col[nnz], t_val[nnz])
+    device tensors, element for element csr_transpose's arrays."""
+    torch = _torch()
+    a = dm.arrays
+    if dm.fmt != "csr" or not all(k in a for k in ("row_ptr", "col", "val")):
+        raise SpmvError(OTHER_ERROR, "dev_csr_transpose", "needs a CSR DeviceMatrix")
+    t_ptr = torch.empty(dm.n_cols + 1, dtype=torch.int64, device=dm.device)
+    t_col = torch.empty(max(dm.nnz, 1), dtype=torch.int32, device=dm.device)
+    t_val = torch.empty(max(dm.nnz, 1), dtype=torch.float64, device=dm.device)
+    _check(hip_lib().spmv_dev_csr_transpose(dm.dims(), _ptr(a["row_ptr"]), _ptr(a["col"]), _ptr(a["val"]),
+                                            _ptr(t_ptr), _ptr(t_col), _ptr(t_val)), "spmv_dev_csr_transpose")
+    return t_ptr, t_col[: dm.nnz], t_val[: dm.nnz]
 
 
 def banded_to_device(n: int, fmt: str, device="cuda:0", row_begin: int = 0, row_end: int | None = None,
