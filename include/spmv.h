@@ -166,7 +166,17 @@ int spmv_plan_sell(spmv_dims d, int32_t C, int32_t sigma, int32_t ki, int64_t n_
 int spmv_plan_cmrs(spmv_dims d, int32_t h, int64_t n_strips, const int64_t *strip_ptr, const uint8_t *row_in_strip,
                    const int32_t *col, const double *val, const spmv_plan_opts *o, spmv_plan **out);
 /* y = A x on `stream` (NULL = the default stream; the plan's d.stream is
- * used for building only).  x[n_cols], y[n_rows], device pointers.        */
+ * used for building only).  x[n_cols], y[n_rows], device pointers.
+ *   - y[0 .. n_rows) is FULLY overwritten (rows without entries get 0.0);
+ *     NO byte of y outside it is written.
+ *   - x and y need 8-byte alignment only: every load of x and store of y is
+ *     8 bytes wide (the 16-byte loads are of the matrix arrays and of
+ *     plan-owned buffers).
+ *   - NO value outside x[0 .. n_cols) enters a result (padding slots
+ *     included).
+ *   - x and y must not overlap; runs of one plan must be serialised.
+ * tests/test_exact_gpu.py (test_forward_memory_contract) holds every format
+ * to this with x and y one element into larger buffers.                   */
 int spmv_plan_run(const spmv_plan *p, const double *x, double *y, void *stream);
 /* Y = A·X for k vectors stored row-major ("vector index fastest"):
  * X[c*ldx + j], c < n_cols, j < k;  Y[i*ldy + j], i < n_rows, j < k.
