@@ -35,7 +35,7 @@ LIB_HIP  := $(LIBDIR)/libspmv_hip.so
 LIB_HOST := $(LIBDIR)/libspmv_host.so
 ORACLE   := oracle/liboracle.so
 
-.PHONY: all default lib oracle probes lab test-san test-san-transpose test-cpu test-gpu clean $(TARGETS)
+.PHONY: all default lib oracle probes lab test-san test-san-transpose test-san-transpose-multi test-cpu test-gpu clean $(TARGETS)
 
 default: all
 all: lib $(TARGETS) probes
@@ -140,6 +140,16 @@ build/san/transpose_harness: tests/san/transpose_harness.c $(HOST_SRC) include/s
 
 test-san-transpose: build/san/transpose_harness
 	$(SANENV) ASAN_OPTIONS=detect_leaks=1:exitcode=99 build/san/transpose_harness tests/golden/*.mtx
+
+# the host side of the multi-vector transposed product (spmv_cpu_csr_t_multi)
+# under ASan + UBSan: a stand-alone program over the fixtures with
+# exactly-sized allocations (tests/san/transpose_multi_harness.c)
+build/san/transpose_multi_harness: tests/san/transpose_multi_harness.c $(HOST_SRC) include/spmv_host.h include/spmv_rc.h
+	@mkdir -p build/san
+	$(CC) -std=c11 -Wall -Wextra -Werror -fopenmp -Iinclude $(SANFLAGS) $< $(HOST_SRC) -o $@ -lm
+
+test-san-transpose-multi: build/san/transpose_multi_harness
+	$(SANENV) ASAN_OPTIONS=detect_leaks=1:exitcode=99 build/san/transpose_multi_harness tests/golden/*.mtx
 
 test-gpu: all oracle
 	python -m pytest tests/ -x -q -m gpu

@@ -272,6 +272,65 @@ int spmv_plan_transpose_supported(const spmv_plan *p);
 int spmv_plan_prepare_transpose(spmv_plan *p, int mode);
 int spmv_plan_get_transpose_info(const spmv_plan *p, spmv_transpose_info *info);
 int spmv_plan_run_t(const spmv_plan *p, const double *x, double *y, void *stream);
+/* Y = A^T·X for k vectors stored row-major, the layout of spmv_plan_run_multi
+ * with the roles swapped: X[r*ldx + j], r < n_rows;  Y[c*ldy + j], c < n_cols;
+ * j < k;  ldx >= k, ldy >= k (elements), k >= 1.  Needs
+ * spmv_plan_prepare_transpose first and runs in whichever mode was prepared.
+ *
+ * The conventions above hold: device pointers, asynchronous on `stream`, no
+ * allocation and no synchronisation inside the call (it can be captured into
+ * a graph on one stream), codes of spmv_rc.h, a message in spmv_last_error().
+ *   - Y[c*ldy + j], j < k, is fully overwritten (columns of A without
+ *     entries get 0.0); NO element with j >= k and nothing at or past row
+ *     n_cols is written.
+ *   - NO byte outside X[r*ldx .. r*ldx + k) is read for any r.
+ *   - X and Y need 8-byte alignment only and any ldx, ldy >= k: every load
+ *     of X and every add to Y is 8 bytes wide.
+ *   - X and Y must not overlap; runs of one plan must be serialised.
+ *   - Reads the caller's row_ptr, col and val, never the plan's
+ *     hot-renumbered column copy.
+ *   - SPMV_OTHER_ERROR with a message, before any device work: NULL plan, a
+ *     plan that was not prepared (every plan that is not CSR: it cannot be),
+ *     k < 1, ldx < k or ldy < k, NULL X with rows present, NULL Y with
+ *     columns present.
+ * SPMV_T_COPY: spmv_plan_run_multi on the inner forward plan over A^T and
+ *     nothing else, so its bit rule carries over: the bits of column j are
+ *     those of spmv_plan_run_multi on a default forward CSR plan over
+ *     spmv_csr_transpose's arrays, independent of k, of j's place in its
+ *     block of 8 and of ldx / ldy.
+ * SPMV_T_SCATTER: csr_t_multi_kernel<KV>, KV in {1, 2, 4, 8}.  The matrix is
+ *     streamed once per block of up to 8 vectors (ceil(k/8) passes, pass b on
+ *     X + 8b, Y + 8b); a block of r remaining vectors runs the smallest
+ *     KV >= r and neither loads nor adds its unused columns.  Y is zeroed once
+ *     before the first pass.  The geometry is spmv_plan_run_t's (one
+ *     workgroup per 128 rows, the same recorded column ranges); the LDS
+ *     accumulator holds span * KV sums, so a row block sums in LDS when its
+ *     column span is at most cap_cols[w] = 8,192 / KV and adds every product
+ *     straight into Y (k-wide pieces of 8 * KV bytes) otherwise.  Results are
+ *     NOT bitwise reproducible from run to run (the atomics arrive in any
+ *     order); Y must be ordinary device memory, as for spmv_plan_run_t.
+ * Which to call (MI355X, cold, profiles/transpose/README.md): against k calls
+ * of spmv_plan_run_t on the same plan, one call was 1.9 / 2.2-2.8 / 2.2-3.8
+ * times faster at k = 2 / 4 / 8 in scatter mode on cant-like matrices, 1.2 /
+ * 2.4 / 5.5 times faster in scatter mode on a power-law R-MAT (every product
+ * a global atomic either way) and 1.2-1.4 / 1.9-2.1 / 2.3-3.0 times faster in
+ * copy mode on cant-like matrices.  In COPY mode on the power-law R-MAT one
+ * call was 5 to 20 times SLOWER than k calls (spmv_plan_run_multi has no
+ * entry-balanced kernel for the hub rows of A^T): call spmv_plan_run_t k times
+ * there.  One vector belongs to spmv_plan_run_t (k == 1 with ldx == ldy == 1 is
+ * that very launch in scatter mode; in copy mode spmv_plan_run_multi at k = 1
+ * is slower than spmv_plan_run).                                            */
+int spmv_plan_run_t_multi(const spmv_plan *p, int32_t k, const double *X, int64_t ldx,
+                          double *Y, int64_t ldy, void *stream);
+typedef struct spmv_transpose_multi_info {
+    int32_t mode;          /* enum spmv_transpose_mode */
+    int32_t reserved;
+    int32_t cap_cols[4];   /* scatter: widest column span of a row block that is summed in LDS by the
+                              kernel of width 1, 2, 4, 8; copy: 0 */
+    int64_t lds_blocks[4]; /* scatter: row blocks within that span, per width */
+    char kernel[64];       /* dominant kernel; copy: the inner plan's multi-vector kernel */
+} spmv_transpose_multi_info;
+int spmv_plan_get_transpose_multi_info(const spmv_plan *p, spmv_transpose_multi_info *info);
 int spmv_plan_get_info(const spmv_plan *p, spmv_plan_info *info);
 /* Frees what the plan allocated (never the caller's arrays). */
 int spmv_plan_destroy(spmv_plan *p);

@@ -295,6 +295,17 @@ int spmv_cpu_csr_multi(int64_t n_rows, const int64_t *row_ptr, const int32_t *co
  * read or written (nothing of y past a bad entry's row is touched).       */
 int spmv_cpu_csr_t(int64_t n_rows, int64_t n_cols, const int64_t *row_ptr,
                    const int32_t *col, const double *val, const double *x, double *y);
+/* Y = A^T X for k >= 1 vectors stored row-major, the layout of
+ * spmv_plan_run_t_multi (spmv.h): X[r*ldx + j], r < n_rows; Y[c*ldy + j],
+ * c < n_cols; j < k; ldx >= k, ldy >= k.  Serial: zeroes Y[c*ldy + j], j < k,
+ * then scatters row by row in CSR order, so column j has the bits of
+ * spmv_cpu_csr_t on column j.  Writes nothing for j >= k or at or past row
+ * n_cols and reads nothing of X outside [r*ldx, r*ldx + k).
+ * SPMV_OTHER_ERROR for negative sizes, k < 1, a leading dimension below k, a
+ * column outside [0, n_cols) or a NULL array that would be read or written. */
+int spmv_cpu_csr_t_multi(int64_t n_rows, int64_t n_cols, const int64_t *row_ptr,
+                         const int32_t *col, const double *val, int32_t k, const double *X,
+                         int64_t ldx, double *Y, int64_t ldy);
 int spmv_cpu_ell(int64_t n_rows, int32_t K, int64_t ld, int32_t ki,
                  const int32_t *col, const double *val, const double *x,
                  double *y, int threads);

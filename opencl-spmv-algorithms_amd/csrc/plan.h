@@ -44,6 +44,10 @@ struct spmv_plan {
     int32_t t_mode = 0;        // enum spmv_transpose_mode
     int32_t t_xcap = 0;        // scatter: LDS accumulator entries of a run (widest window that fits the cap)
     int64_t t_blocks = 0, t_lds_blocks = 0, t_flush = 0;
+    // scatter, multi-vector run (csr_t_multi_kernel of width 1, 2, 4, 8): the
+    // widest column span that fits the width's cap, and the blocks that fit
+    int32_t t_mxcap[4] = {0, 0, 0, 0};
+    int64_t t_mlds[4] = {0, 0, 0, 0};
     void *t_win = nullptr;     // scatter: int2 {lo, hi} column range per row block
     int64_t *t_ptr = nullptr;  // copy: A^T as CSR (t_ptr[n_cols+1], t_col/t_val[nnz])
     int32_t *t_col = nullptr;

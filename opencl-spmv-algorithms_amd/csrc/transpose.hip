@@ -17,6 +17,11 @@
 //       bitwise reproducible, 12 nnz + 8 (n_cols + 1) bytes more.
 // Both read the caller's row_ptr / col / val, never the plan's hot-renumbered
 // column copy.
+//
+// The multi-vector run Y = A^T X (spmv_plan_run_t_multi) works in whichever
+// mode was prepared: copy is spmv_plan_run_multi on the inner plan; scatter is
+// csr_t_multi_kernel<KV>, the window kernel's geometry with KV vectors per
+// pass and an LDS accumulator of span * KV sums (below).
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -136,6 +141,209 @@ __global__ __launch_bounds__(kBlock) void csr_t_window_kernel(int64_t n_rows, in
     }
 }
 
+// ------------------------------------------------- multi-vector scatter
+// Y = A^T X (spmv_plan_run_t_multi): the geometry of csr_t_window_kernel with
+// KV vectors per pass.  The LDS accumulator holds span * KV sums, word
+// (c - lo) * KV + j, so a block sums in LDS when span * KV <= kTMultiCap.
+#ifndef SPMV_T_MULTI_CAP
+#define SPMV_T_MULTI_CAP 8192  // an A/B build may override it (profiles/transpose/README.md)
+#endif
+constexpr int32_t kTMultiCap = SPMV_T_MULTI_CAP;  // LDS accumulator doubles per workgroup (64 KiB)
+constexpr int kTWidths[4] = {1, 2, 4, 8};
+
+// lanes that share one entry: two columns per lane from KV = 4 on, as
+// csr_multi_kernel; the P lanes of an entry are neighbours inside one quad
+template <int KV>
+constexpr int t_multi_p()
+{
+    return KV >= 4 ? KV / 2 : 1;
+}
+
+// The value of lane Q of every P-lane group (P = 2 or 4, groups aligned inside
+// a quad) by a DPP quad_perm move: a VALU operand modifier, no LDS traffic.
+// Called in uniform control flow only (every lane of the wave active).
+template <int P, int Q>
+constexpr int group_bcast_ctrl()
+{
+    static_assert((P == 2 || P == 4) && Q < P, "groups inside one quad");
+    return P == 4 ? Q * 0x55 : (Q | Q << 2 | (2 + Q) << 4 | (2 + Q) << 6);
+}
+
+template <int P, int Q>
+__device__ __forceinline__ int group_bcast(int v)
+{
+    return __builtin_amdgcn_mov_dpp(v, group_bcast_ctrl<P, Q>(), 0xF, 0xF, false);
+}
+
+template <int P, int Q>
+__device__ __forceinline__ double group_bcast(double v)
+{
+    const long long b = __double_as_longlong(v);
+    const int lo = group_bcast<P, Q>((int)b);
+    const int hi = group_bcast<P, Q>((int)(b >> 32));
+    return __longlong_as_double((long long)(((unsigned long long)(unsigned)hi << 32) | (unsigned)lo));
+}
+
+// One lane's CPL columns [j0, j0 + CPL) of one entry (column c, value v, block
+// row r): v * X[r][j] added to acc[(c - lo) * KV + j] (LDS = true, bound = the
+// block's span) or to Y[c * ldy + j] (false, bound = n_cols).  A column
+// outside the bound is dropped, never written; columns j >= live (a ragged
+// last block of vectors) are neither read nor added.
+template <int KV, bool LDS>
+__device__ __forceinline__ void t_multi_add(const double *s_x, double *acc, double *__restrict__ Y, int64_t ldy,
+                                            int32_t lo, uint32_t bound, int32_t live, int j0, int32_t c, double v,
+                                            int r)
+{
+    constexpr int CPL = KV / t_multi_p<KV>();
+    const uint32_t idx = LDS ? (uint32_t)c - (uint32_t)lo : (uint32_t)c;
+    if (idx >= bound)
+        return;
+#pragma unroll
+    for (int i = 0; i < CPL; ++i) {
+        const int j = j0 + i;
+        if (j < live) {
+            const double p = v * s_x[r * KV + j];
+            if constexpr (LDS)
+                atomicAdd(&acc[idx * KV + j], p);
+            else
+                unsafeAtomicAdd(&Y[(int64_t)idx * ldy + j], p);
+        }
+    }
+}
+
+// The P rounds of one step: round Q hands entry Q of every P-lane group (its
+// column, value and row, found ONCE by the lane that loaded it) to the group's
+// P lanes, which add their CPL columns of it.
+template <int KV, bool LDS, int Q = 0>
+__device__ __forceinline__ void t_multi_rounds(const double *s_x, double *acc, double *__restrict__ Y, int64_t ldy,
+                                               int32_t lo, uint32_t bound, int32_t live, int j0, int32_t c, double v,
+                                               int r)
+{
+    constexpr int P = t_multi_p<KV>();
+    if constexpr (P == 1) {
+        t_multi_add<KV, LDS>(s_x, acc, Y, ldy, lo, bound, live, j0, c, v, r);
+    } else if constexpr (Q < P) {
+        t_multi_add<KV, LDS>(s_x, acc, Y, ldy, lo, bound, live, j0, group_bcast<P, Q>(c), group_bcast<P, Q>(v),
+                             group_bcast<P, Q>(r));
+        t_multi_rounds<KV, LDS, Q + 1>(s_x, acc, Y, ldy, lo, bound, live, j0, c, v, r);
+    }
+}
+
+// t_scatter_block for KV vectors: the same coalesced non-temporal stream
+// (thread t loads entries t, t + 256, ... with kTU in flight; every lane its
+// own entry, so the matrix is loaded once) and the same 7-step row search,
+// done once per entry by the lane that loaded it.  The loops are uniform over
+// the workgroup (the DPP moves need whole waves): in the last partial step a
+// lane past the end carries column -1, which every bound check drops.
+template <int KV, bool LDS>
+__device__ __forceinline__ void t_multi_block(const int64_t *s_ptr, const double *s_x, int nr,
+                                              const int32_t *__restrict__ col, const double *__restrict__ val,
+                                              double *__restrict__ Y, int64_t ldy, double *acc, int32_t lo,
+                                              uint32_t bound, int32_t live)
+{
+    constexpr int P = t_multi_p<KV>();
+    constexpr int CPL = KV / P;
+    const int j0 = ((int)threadIdx.x % P) * CPL;
+    auto row_of = [&](int64_t e) {
+        int r = 0;
+#pragma unroll
+        for (int step = kTRows / 2; step > 0; step >>= 1)
+            if (r + step < nr && s_ptr[r + step] <= e)
+                r += step;
+        return r;
+    };
+    const int64_t end = s_ptr[nr];
+    int64_t e0 = s_ptr[0];  // uniform
+    for (; e0 + kTU * kBlock <= end; e0 += kTU * kBlock) {
+        const int64_t e = e0 + (int64_t)threadIdx.x;
+        int32_t c[kTU];
+        double v[kTU];
+#pragma unroll
+        for (int u = 0; u < kTU; ++u) {
+            c[u] = stream_load<true>(col + e + u * kBlock);
+            v[u] = stream_load<true>(val + e + u * kBlock);
+        }
+#pragma unroll
+        for (int u = 0; u < kTU; ++u)
+            t_multi_rounds<KV, LDS>(s_x, acc, Y, ldy, lo, bound, live, j0, c[u], v[u], row_of(e + u * kBlock));
+    }
+    for (; e0 < end; e0 += kBlock) {
+        const int64_t e = e0 + (int64_t)threadIdx.x;
+        int32_t c = -1;
+        double v = 0.0;
+        int r = 0;
+        if (e < end) {
+            c = stream_load<true>(col + e);
+            v = stream_load<true>(val + e);
+            r = row_of(e);
+        }
+        t_multi_rounds<KV, LDS>(s_x, acc, Y, ldy, lo, bound, live, j0, c, v, r);
+    }
+}
+
+// One workgroup per block of kTRows rows, one pass over the block's entries
+// for `live` <= KV vectors (X, Y: the pass's first column).  LDS: the block's
+// kTRows + 1 row offsets, its kTRows x KV values of X (8-byte loads: under 2 %
+// of the block's bytes), then the accumulator of span x KV sums when the
+// block's column range spans at most `cap` = kTMultiCap / KV columns.
+template <int KV>
+__global__ __launch_bounds__(kBlock) void csr_t_multi_kernel(int64_t n_rows, int64_t n_cols,
+                                                             const int64_t *__restrict__ ptr,
+                                                             const int32_t *__restrict__ col,
+                                                             const double *__restrict__ val,
+                                                             const double *__restrict__ X, int64_t ldx,
+                                                             double *__restrict__ Y, int64_t ldy,
+                                                             const int2 *__restrict__ win, int32_t cap, int32_t live)
+{
+    extern __shared__ double s_mem[];
+    int64_t *s_ptr = reinterpret_cast<int64_t *>(s_mem);
+    double *s_x = s_mem + kTPtr;
+    double *acc = s_x + kTRows * KV;
+    const int tid = (int)threadIdx.x;
+    const int2 w = win[blockIdx.x];
+    const int span = w.y - w.x + 1;  // <= 0: a block without entries
+    if (span <= 0)                   // uniform per workgroup
+        return;
+    const bool lds = span <= cap;
+    const int64_t r0 = (int64_t)blockIdx.x * kTRows;
+    const int nr = (int)(n_rows - r0 < kTRows ? n_rows - r0 : kTRows);
+    for (int i = tid; i <= nr; i += kBlock)
+        s_ptr[i] = ptr[r0 + i];
+    for (int i = tid; i < nr * KV; i += kBlock) {
+        const int j = i % KV;
+        if (j < live)
+            s_x[i] = X[(r0 + i / KV) * ldx + j];
+    }
+    if (lds)
+        for (int i = tid; i < span * KV; i += kBlock)
+            acc[i] = 0.0;
+    __syncthreads();
+    if (!lds) {
+        t_multi_block<KV, false>(s_ptr, s_x, nr, col, val, Y, ldy, acc, 0, (uint32_t)n_cols, live);
+        return;
+    }
+    t_multi_block<KV, true>(s_ptr, s_x, nr, col, val, Y, ldy, acc, w.x, (uint32_t)span, live);
+    __syncthreads();
+    // the flush: thread t takes accumulator words t, t + 256, ...: with
+    // ldy == KV a wave instruction covers 512 contiguous bytes of Y.  Sums
+    // still exactly 0.0 add nothing to the zeroed Y.
+    for (int i = tid; i < span * KV; i += kBlock) {
+        const int j = i % KV;
+        const double s = acc[i];
+        if (j < live && s != 0.0)
+            unsafeAtomicAdd(&Y[(int64_t)(w.x + i / KV) * ldy + j], s);
+    }
+}
+
+// Y[c*ldy + j] = 0 for c < n_cols, j < k (ldy > k: the gaps are not touched)
+__global__ __launch_bounds__(kBlock) void t_zero_cols_kernel(int64_t n_cols, int32_t k, double *__restrict__ Y,
+                                                             int64_t ldy)
+{
+    const int64_t n = n_cols * k;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock)
+        Y[i / k * ldy + i % k] = 0.0;
+}
+
 namespace {
 
 int t_alloc(spmv_plan *p, void **dst, size_t bytes)
@@ -146,6 +354,24 @@ int t_alloc(spmv_plan *p, void **dst, size_t bytes)
         return fail(SPMV_PROGRAM_ERROR, "spmv_plan_prepare_transpose: hipMalloc", e);
     p->t_owned += bytes;
     return SPMV_SUCCESS;
+}
+
+// dynamic LDS bytes of a csr_t_multi_kernel<kv> launch whose widest LDS block
+// spans `span` columns, and the most a plan can ask for
+constexpr size_t t_multi_lds(int kv, int64_t span)
+{
+    return (size_t)(kTPtr + kTRows * kv + span * kv) * sizeof(double);
+}
+
+constexpr size_t t_multi_lds_max(int kv) { return t_multi_lds(kv, kTMultiCap / kv); }
+
+template <typename F>
+void with_each_width(F &&f)
+{
+    f(std::integral_constant<int, 1>{});
+    f(std::integral_constant<int, 2>{});
+    f(std::integral_constant<int, 4>{});
+    f(std::integral_constant<int, 8>{});
 }
 
 int prepare_scatter(spmv_plan *p)
@@ -174,8 +400,24 @@ int prepare_scatter(spmv_plan *p)
             p->t_flush += span;
             p->t_xcap = span > p->t_xcap ? (int32_t)span : p->t_xcap;
         }
+        for (int w = 0; w < 4; ++w)  // the multi-vector kernels: span * KV sums per block
+            if (span > 0 && span <= kTMultiCap / kTWidths[w]) {
+                p->t_mlds[w]++;
+                p->t_mxcap[w] = span > p->t_mxcap[w] ? (int32_t)span : p->t_mxcap[w];
+            }
     }
     free(h);
+    // a launch of the widest fitting span may need more than the default 64 KiB
+    // of dynamic LDS: allowed here, once, so that a run only launches
+    hipError_t e = hipSuccess;
+    with_each_width([&](auto KV) {
+        constexpr int kv = decltype(KV)::value;
+        if (e == hipSuccess)
+            e = hipFuncSetAttribute(reinterpret_cast<const void *>(csr_t_multi_kernel<kv>),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)t_multi_lds_max(kv));
+    });
+    if (e != hipSuccess)
+        return fail(SPMV_PROGRAM_ERROR, "spmv_plan_prepare_transpose: dynamic LDS of csr_t_multi_kernel", e);
     return SPMV_SUCCESS;
 }
 
@@ -213,6 +455,40 @@ int launch_scatter(const spmv_plan *p, const double *x, double *y, hipStream_t s
     return SPMV_SUCCESS;
 }
 
+// Y zeroed once (columns j < k only), then ceil(k/8) passes of the narrowest
+// kernel that holds the pass's vectors
+int launch_scatter_multi(const spmv_plan *p, int32_t k, const double *X, int64_t ldx, double *Y, int64_t ldy,
+                         hipStream_t st)
+{
+    const spmv_dims &d = p->d;
+    if (k == 1 && ldx == 1 && ldy == 1)
+        return launch_scatter(p, X, Y, st);
+    if (d.n_cols > 0 && ldy == k) {
+        hipError_t e = hipMemsetAsync(Y, 0, (size_t)d.n_cols * k * sizeof(double), st);
+        if (e != hipSuccess)
+            return fail(SPMV_PROGRAM_ERROR, "spmv_plan_run_t_multi: memset", e);
+    } else if (d.n_cols > 0) {
+        const int64_t want = (d.n_cols * k + kBlock - 1) / kBlock;
+        hipLaunchKernelGGL(t_zero_cols_kernel, dim3((unsigned)(want < 65536 ? want : 65536)), dim3(kBlock), 0, st,
+                           d.n_cols, k, Y, ldy);
+        SPMV_CHECK_LAUNCH("t_zero_cols_kernel");
+    }
+    if (!p->t_win || d.n_cols == 0)
+        return SPMV_SUCCESS;
+    for (int32_t j0 = 0; j0 < k; j0 += 8) {
+        const int32_t live = k - j0 < 8 ? k - j0 : 8;
+        const int w = live > 4 ? 3 : live > 2 ? 2 : live - 1;  // width kTWidths[w] >= live
+        with_int<1, 2, 4, 8>(kTWidths[w], [&](auto KV) {
+            constexpr int kv = decltype(KV)::value;
+            hipLaunchKernelGGL(csr_t_multi_kernel<kv>, dim3((unsigned)p->t_blocks), dim3(kBlock),
+                               t_multi_lds(kv, p->t_mxcap[w]), st, d.n_rows, d.n_cols, p->ptr, p->col, p->val, X + j0,
+                               ldx, Y + j0, ldy, (const int2 *)p->t_win, kTMultiCap / kv, live);
+        });
+        SPMV_CHECK_LAUNCH("csr_t_multi_kernel");
+    }
+    return SPMV_SUCCESS;
+}
+
 }  // namespace
 
 void plan_transpose_free(spmv_plan *p)
@@ -230,6 +506,10 @@ void plan_transpose_free(spmv_plan *p)
     p->t_mode = SPMV_T_NONE;
     p->t_xcap = 0;
     p->t_blocks = p->t_lds_blocks = p->t_flush = 0;
+    for (int w = 0; w < 4; ++w) {
+        p->t_mxcap[w] = 0;
+        p->t_mlds[w] = 0;
+    }
     p->t_owned = 0;
 }
 
@@ -304,6 +584,44 @@ int spmv_plan_run_t(const spmv_plan *p, const double *x, double *y, void *stream
         return spmv_plan_run(p->t_inner, x, y, stream);
     SPMV_GUARD(p->d);
     return launch_scatter(p, x, y, (hipStream_t)stream);
+}
+
+int spmv_plan_get_transpose_multi_info(const spmv_plan *p, spmv_transpose_multi_info *info)
+{
+    if (!p || !info)
+        return fail_msg(SPMV_OTHER_ERROR, "spmv_plan_get_transpose_multi_info: NULL argument");
+    memset(info, 0, sizeof *info);
+    info->mode = p->t_mode;
+    if (p->t_mode == SPMV_T_SCATTER) {
+        for (int w = 0; w < 4; ++w) {
+            info->cap_cols[w] = kTMultiCap / kTWidths[w];
+            info->lds_blocks[w] = p->t_mlds[w];
+        }
+        snprintf(info->kernel, sizeof info->kernel, "csr_t_multi_kernel");
+    } else if (p->t_inner) {
+        snprintf(info->kernel, sizeof info->kernel, "csr_multi_kernel");  // every CSR path's multi-vector kernel
+    }
+    return SPMV_SUCCESS;
+}
+
+int spmv_plan_run_t_multi(const spmv_plan *p, int32_t k, const double *X, int64_t ldx, double *Y, int64_t ldy,
+                          void *stream)
+{
+    if (!p)
+        return fail_msg(SPMV_OTHER_ERROR, "spmv_plan_run_t_multi: plan is NULL");
+    if (p->t_mode == SPMV_T_NONE)
+        return fail_msg(SPMV_OTHER_ERROR,
+                        "spmv_plan_run_t_multi: the plan was not prepared (spmv_plan_prepare_transpose)");
+    if (k < 1)
+        return fail_msg(SPMV_OTHER_ERROR, "spmv_plan_run_t_multi: k must be at least 1");
+    if (ldx < k || ldy < k)
+        return fail_msg(SPMV_OTHER_ERROR, "spmv_plan_run_t_multi: ldx and ldy must be at least k");
+    if ((p->d.n_rows > 0 && !X) || (p->d.n_cols > 0 && !Y))
+        return fail_msg(SPMV_OTHER_ERROR, "spmv_plan_run_t_multi: X or Y is NULL");
+    if (p->t_mode == SPMV_T_COPY)
+        return spmv_plan_run_multi(p->t_inner, k, X, ldx, Y, ldy, stream);
+    SPMV_GUARD(p->d);
+    return launch_scatter_multi(p, k, X, ldx, Y, ldy, (hipStream_t)stream);
 }
 
 }  // extern "C"

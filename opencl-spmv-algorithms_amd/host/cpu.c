@@ -97,6 +97,35 @@ int spmv_cpu_csr_t(int64_t n_rows, int64_t n_cols, const int64_t *row_ptr,
     return SPMV_SUCCESS;
 }
 
+/* Y = A^T X for k vectors stored row-major (the layout of
+ * spmv_plan_run_t_multi, spmv.h): Y[c*ldy + j], j < k, zeroed, then one serial
+ * scatter row by row; column j is added in the order of spmv_cpu_csr_t, so it
+ * has that loop's bits.  Nothing is written for j >= k or at or past row
+ * n_cols, nothing of X is read outside [r*ldx, r*ldx + k).                  */
+int spmv_cpu_csr_t_multi(int64_t n_rows, int64_t n_cols, const int64_t *row_ptr,
+                         const int32_t *col, const double *val, int32_t k, const double *X,
+                         int64_t ldx, double *Y, int64_t ldy)
+{
+    if (n_rows < 0 || n_cols < 0 || k < 1 || ldx < k || ldy < k || !row_ptr || (n_cols > 0 && !Y))
+        return SPMV_OTHER_ERROR;
+    if (row_ptr[n_rows] > row_ptr[0] && (!col || !val || !X))
+        return SPMV_OTHER_ERROR;
+    for (int64_t c = 0; c < n_cols; ++c)
+        memset(Y + c * ldy, 0, (size_t)k * sizeof(double));
+    for (int64_t r = 0; r < n_rows; ++r) {
+        for (int64_t e = row_ptr[r]; e < row_ptr[r + 1]; ++e) {
+            if (col[e] < 0 || col[e] >= n_cols)
+                return SPMV_OTHER_ERROR;
+            const double *xr = X + r * ldx; /* X is not NULL here: the row has an entry */
+            double *yc = Y + (int64_t)col[e] * ldy;
+            const double v = val[e];
+            for (int32_t j = 0; j < k; ++j)
+                yc[j] += v * xr[j];
+        }
+    }
+    return SPMV_SUCCESS;
+}
+
 int spmv_cpu_ell(int64_t n_rows, int32_t K, int64_t ld, int32_t ki,
                  const int32_t *col, const double *val, const double *x,
                  double *y, int threads)

@@ -112,6 +112,13 @@ class TransposeInfo(ctypes.Structure):
                [("kernel", ctypes.c_char * 64)]
 
 
+class TransposeMultiInfo(ctypes.Structure):
+    """``spmv_transpose_multi_info`` (include/spmv.h)."""
+
+    _fields_ = [("mode", _c_i32), ("reserved", _c_i32), ("cap_cols", _c_i32 * 4), ("lds_blocks", _c_i64 * 4),
+                ("kernel", ctypes.c_char * 64)]
+
+
 TRANSPOSE_MODES = {None: 0, "scatter": 1, "copy": 2}  # enum spmv_transpose_mode
 
 _PP = ctypes.POINTER(_vp)
@@ -132,6 +139,8 @@ HIP_SYMBOLS = {
     "spmv_plan_prepare_transpose": (ctypes.c_int, [_vp, ctypes.c_int]),
     "spmv_plan_get_transpose_info": (ctypes.c_int, [_vp, ctypes.POINTER(TransposeInfo)]),
     "spmv_plan_run_t": (ctypes.c_int, [_vp, _vp, _vp, _vp]),
+    "spmv_plan_run_t_multi": (ctypes.c_int, [_vp, _c_i32, _vp, _c_i64, _vp, _c_i64, _vp]),
+    "spmv_plan_get_transpose_multi_info": (ctypes.c_int, [_vp, ctypes.POINTER(TransposeMultiInfo)]),
     "spmv_plan_get_info": (ctypes.c_int, [_vp, ctypes.POINTER(PlanInfo)]),
     "spmv_plan_destroy": (ctypes.c_int, [_vp]),
     "spmv_set_option": (ctypes.c_int, [ctypes.c_int, ctypes.c_int]),
@@ -315,6 +324,7 @@ HOST_SYMBOLS = {
     "spmv_cpu_csr": (ctypes.c_int, [_c_i64, _vp, _vp, _vp, _vp, _vp, ctypes.c_int]),
     "spmv_cpu_csr_multi": (ctypes.c_int, [_c_i64, _vp, _vp, _vp, _c_i32, _vp, _c_i64, _vp, _c_i64]),
     "spmv_cpu_csr_t": (ctypes.c_int, [_c_i64, _c_i64, _vp, _vp, _vp, _vp, _vp]),
+    "spmv_cpu_csr_t_multi": (ctypes.c_int, [_c_i64, _c_i64, _vp, _vp, _vp, _c_i32, _vp, _c_i64, _vp, _c_i64]),
     "spmv_cpu_ell": (ctypes.c_int, [_c_i64, _c_i32, _c_i64, _c_i32, _vp, _vp, _vp, _vp, ctypes.c_int]),
     "spmv_cpu_sell": (ctypes.c_int, [_c_i64, _c_i32, _c_i32, _c_i64, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_int]),
     "spmv_cpu_cmrs": (ctypes.c_int, [_c_i64, _c_i32, _c_i64, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_int]),
@@ -780,6 +790,27 @@ def cpu_csr_multi(n_rows: int, ptr, col, val, X: np.ndarray, Y: np.ndarray, k: i
     _check_host(rc, "spmv_cpu_csr_multi")
 
 
+def cpu_csr_t_multi(n_rows: int, n_cols: int, ptr, col, val, X: np.ndarray, Y: np.ndarray, k: int | None = None) -> None:
+    """Host Y = A^T X (spmv_cpu_csr_t_multi): X (>= n_rows rows) and Y
+    (>= n_cols rows) are 2-D float64 arrays with unit inner stride whose row
+    strides are ldx and ldy; k defaults to X's width.  Only Y[:n_cols, :k] is
+    written."""
+    for a, n in ((X, n_rows), (Y, n_cols)):
+        if not isinstance(a, np.ndarray) or a.dtype != np.float64 or a.ndim != 2:
+            raise SpmvError(OTHER_ERROR, "cpu_csr_t_multi", "X and Y must be 2-D float64 arrays")
+        if a.shape[1] > 1 and a.strides[1] != 8 or a.strides[0] % 8:
+            raise SpmvError(OTHER_ERROR, "cpu_csr_t_multi", "X and Y need unit inner stride")
+        if a.shape[0] < n:
+            raise SpmvError(OTHER_ERROR, "cpu_csr_t_multi", "X or Y has too few rows")
+    k = X.shape[1] if k is None else int(k)
+    if k > X.shape[1] or k > Y.shape[1]:
+        raise SpmvError(OTHER_ERROR, "cpu_csr_t_multi", "X or Y has fewer than k columns")
+    ldx, ldy = (a.strides[0] // 8 if a.shape[0] > 1 else k for a in (X, Y))  # one row: its stride is never used
+    rc = host_lib().spmv_cpu_csr_t_multi(n_rows, n_cols, _ptr(ptr), _ptr(col), _ptr(val), k, _ptr(X), ldx,
+                                         _ptr(Y), ldy)
+    _check_host(rc, "spmv_cpu_csr_t_multi")
+
+
 def check(m: Coo, x: np.ndarray, y: np.ndarray, rel_tol: float = 1e-6, abs_tol: float = 0.0):
     """Host check_result (reference inc/helper_functions.h:184-236)
     -> (bad_rows, first_bad)."""
@@ -997,6 +1028,52 @@ class DeviceMatrix:
         st = stream if stream is not None else torch.cuda.current_stream(here)
         _check(hip_lib().spmv_plan_run_t(self.plan, _ptr(x), _ptr(y), st.cuda_stream),
                f"spmv_plan_run_t ({self.fmt})")
+
+    @property
+    def transpose_multi_info(self) -> dict:
+        """spmv_transpose_multi_info as a dict (cap_cols and lds_blocks are
+        lists over the kernel widths 1, 2, 4, 8); mode as in transpose_info."""
+        if self.plan is None:
+            raise SpmvError(OTHER_ERROR, "transpose_multi_info", f"format {self.fmt} has no plan")
+        info = TransposeMultiInfo()
+        _check(hip_lib().spmv_plan_get_transpose_multi_info(self.plan, ctypes.byref(info)),
+               "spmv_plan_get_transpose_multi_info")
+        return {"mode": {v: k for k, v in TRANSPOSE_MODES.items()}[info.mode],
+                "cap_cols": [int(v) for v in info.cap_cols], "lds_blocks": [int(v) for v in info.lds_blocks],
+                "kernel": info.kernel.decode()}
+
+    def run_t_multi(self, X, Y, stream=None) -> None:
+        """Y = A^T X on `stream` for k vectors stored row-major
+        (spmv_plan_run_t_multi): X is (>= n_rows, k), Y is (>= n_cols, k),
+        float64 on the matrix's device with inner stride 1; their row strides
+        (>= k) are ldx and ldy.  Only Y[:n_cols, :k] is written.  Needs
+        prepare_transpose first."""
+        torch = _torch()
+        for t in (X, Y):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float64:
+                raise SpmvError(OTHER_ERROR, "run_t_multi", "X and Y must be float64 tensors")
+            if t.dim() != 2:
+                raise SpmvError(OTHER_ERROR, "run_t_multi", "X and Y must be 2-D (rows, k)")
+        k = X.shape[1]
+        if k < 1 or Y.shape[1] != k:
+            raise SpmvError(OTHER_ERROR, "run_t_multi", "X and Y must have the same number k >= 1 of columns")
+        if X.shape[0] < self.n_rows or Y.shape[0] < self.n_cols:
+            raise SpmvError(OTHER_ERROR, "run_t_multi", "X or Y has too few rows")
+        for t in (X, Y):  # as run_multi: raw data_ptr()s and strides go to the C-ABI
+            if (k > 1 and t.stride(1) != 1) or (t.shape[0] > 1 and t.stride(0) < k):
+                raise SpmvError(OTHER_ERROR, "run_t_multi", "X and Y need inner stride 1 and a row stride >= k")
+        here = torch.device(self.device)
+        idx = here.index or 0
+        for t in (X, Y):
+            if t.device.type != here.type or (t.device.index or 0) != idx:
+                raise SpmvError(OTHER_ERROR, "run_t_multi", f"X and Y must be on {here.type}:{idx}")
+        if self.plan is None:
+            raise SpmvError(OTHER_ERROR, "run_t_multi", f"format {self.fmt} has no plan: no transposed run")
+        ldx = X.stride(0) if X.shape[0] > 1 else k
+        ldy = Y.stride(0) if Y.shape[0] > 1 else k
+        st = stream if stream is not None else torch.cuda.current_stream(here)
+        _check(hip_lib().spmv_plan_run_t_multi(self.plan, k, _ptr(X), ldx, _ptr(Y), ldy, st.cuda_stream),
+               f"spmv_plan_run_t_multi ({self.fmt})")
 
 
 # the library's A/B switches (include/spmv_ext.h; placement and load policy only)

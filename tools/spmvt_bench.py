@@ -22,6 +22,16 @@ each mode's owned_bytes, scatter's blocks / lds_blocks / flush_entries and
 `flush_gbs` = flush_entries x 8 bytes / scatter time (the atomic bytes per
 second of the window flushes, a lower bound of their rate: the time also holds
 the matrix stream and the memset of y), and a markdown table on stderr.
+
+    timeout -k 10 900 python tools/spmvt_bench.py --vectors 2,4,8
+
+is the multi-vector leg instead: on the same matrices and in both modes, one
+run_t_multi of k vectors against k run_t calls on the same plan, measured by
+the same cold estimator.  A step of the yardstick is one flush followed by
+the k calls back to back, as a caller would issue them (on a matrix that
+fits the Infinity Cache the second to k-th call find it there).  One JSON
+line (per matrix, mode and k: both times with their spreads, `speedup` =
+k calls / one call, the byte-model GB/s of the one call) and a table on stderr.
 """
 from __future__ import annotations
 
@@ -76,11 +86,69 @@ def cold_ms(torch, flush, run, steps, reps):
     return statistics.median(diffs), max(diffs) - min(diffs)
 
 
+def vectors_leg(torch, dev, flush, a):
+    """--vectors: one run_t_multi against k run_t calls, same plan, mode and
+    process, both cold (one flush, then the k calls back to back)."""
+    ks = [int(k) for k in a.vectors.split(",")]
+    out = {"tool": "spmvt_bench --vectors", "device": sa.device_name(0), "steps": a.steps, "reps": a.reps,
+           "results": {}}
+    rng = np.random.default_rng(7)
+    for name in a.matrices.split(","):
+        m = matrix(name)
+        ptr, col, val = sa.csr_from_coo(m)
+        dm = sa.to_device(m, "csr", dev)
+        kmax = max(ks)
+        Xh = rng.uniform(-1, 1, (m.n_rows, kmax))
+        r = {"n_rows": m.n_rows, "n_cols": m.n_cols, "nnz": m.nnz}
+        for mode in ("scatter", "copy"):
+            dm.prepare_transpose(mode)
+            r[mode] = {"info": dm.transpose_multi_info}
+            for k in ks:
+                X = torch.from_numpy(np.ascontiguousarray(Xh[:, :k])).to(dev)
+                Y = torch.empty((m.n_cols, k), dtype=torch.float64, device=dev)
+                xs = [X[:, j].contiguous() for j in range(k)]
+                ys = [torch.empty(m.n_cols, dtype=torch.float64, device=dev) for _ in range(k)]
+
+                def k_calls():
+                    for x, y in zip(xs, ys):
+                        dm.run_t(x, y)
+
+                multi, m_spread = cold_ms(torch, flush, lambda: dm.run_t_multi(X, Y), a.steps, a.reps)
+                single, s_spread = cold_ms(torch, flush, k_calls, a.steps, a.reps)
+                torch.cuda.synchronize()
+                Yr = np.empty((m.n_cols, k))
+                sa.cpu_csr_t_multi(m.n_rows, m.n_cols, ptr, col, val, np.ascontiguousarray(Xh[:, :k]), Yr)
+                err = float(np.max(np.abs(Y.cpu().numpy() - Yr)))  # against spmv_cpu_csr_t_multi
+                r[mode][f"k{k}"] = {
+                    "multi_ms": round(multi, 5), "multi_spread_ms": round(m_spread, 5), "k_calls_ms": round(single, 5),
+                    "k_calls_spread_ms": round(s_spread, 5), "speedup": round(single / multi, 3),
+                    "gbs_alg": round(sa.bytes_alg_multi(m.n_cols, m.n_rows, m.nnz, k) / (multi * 1e-3) / 1e9, 1),
+                    "max_abs_diff_vs_cpu": err}
+                del X, Y, xs, ys
+        dm.prepare_transpose(None)
+        out["results"][name] = r
+        del dm
+    print(json.dumps(out))
+    e = sys.stderr
+    print("| matrix | mode | k | one run_t_multi ms (spread) | k run_t ms (spread) | k calls / one call | GB/s (byte model) |",
+          file=e)
+    print("|---|---|---|---|---|---|---|", file=e)
+    for name, r in out["results"].items():
+        for mode in ("scatter", "copy"):
+            for k in ks:
+                c = r[mode][f"k{k}"]
+                print(f"| {name} | {mode} | {k} | {c['multi_ms']:.4f} ({c['multi_spread_ms']:.4f}) | "
+                      f"{c['k_calls_ms']:.4f} ({c['k_calls_spread_ms']:.4f}) | {c['speedup']:.2f} | {c['gbs_alg']:.0f} |",
+                      file=e)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--matrices", default="cantlike,cantlike_x32,rmat")
     ap.add_argument("--steps", type=int, default=20, help="launches per timed region")
     ap.add_argument("--reps", type=int, default=5, help="timed regions per figure (their median is reported)")
+    ap.add_argument("--vectors", default=None, metavar="K[,K...]",
+                    help="the multi-vector leg instead: one run_t_multi against k run_t calls (e.g. 2,4,8)")
     a = ap.parse_args()
     import torch
 
@@ -95,6 +163,8 @@ def main():
 
     flush()  # allocates the scratch
     torch.cuda.synchronize()
+    if a.vectors:
+        return vectors_leg(torch, dev, flush, a)
     out = {"tool": "spmvt_bench", "device": sa.device_name(0), "steps": a.steps, "reps": a.reps, "results": {}}
     rng = np.random.default_rng(7)
     for name in a.matrices.split(","):
