@@ -35,7 +35,7 @@ LIB_HIP  := $(LIBDIR)/libspmv_hip.so
 LIB_HOST := $(LIBDIR)/libspmv_host.so
 ORACLE   := oracle/liboracle.so
 
-.PHONY: all default lib oracle probes lab test-san test-san-transpose test-san-transpose-multi test-cpu test-gpu clean $(TARGETS)
+.PHONY: all default lib oracle probes lab test-san test-san-transpose test-san-transpose-multi test-san-multi-plan test-cpu test-gpu clean $(TARGETS)
 
 default: all
 all: lib $(TARGETS) probes
@@ -150,6 +150,17 @@ build/san/transpose_multi_harness: tests/san/transpose_multi_harness.c $(HOST_SR
 
 test-san-transpose-multi: build/san/transpose_multi_harness
 	$(SANENV) ASAN_OPTIONS=detect_leaks=1:exitcode=99 build/san/transpose_multi_harness tests/golden/*.mtx
+
+# the host planner of the balanced multi-vector run (spmv_csr_multi_plan)
+# under ASan + UBSan: a stand-alone program over the fixtures, hand-made
+# offsets and the refused inputs with exactly-sized outputs
+# (tests/san/multi_plan_harness.c)
+build/san/multi_plan_harness: tests/san/multi_plan_harness.c $(HOST_SRC) include/spmv_host.h include/spmv_rc.h
+	@mkdir -p build/san
+	$(CC) -std=c11 -Wall -Wextra -Werror -fopenmp -Iinclude $(SANFLAGS) $< $(HOST_SRC) -o $@ -lm
+
+test-san-multi-plan: build/san/multi_plan_harness
+	$(SANENV) ASAN_OPTIONS=detect_leaks=1:exitcode=99 build/san/multi_plan_harness tests/golden/*.mtx
 
 test-gpu: all oracle
 	python -m pytest tests/ -x -q -m gpu

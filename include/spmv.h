@@ -217,6 +217,80 @@ int spmv_plan_run_multi(const spmv_plan *p, int32_t k, const double *X, int64_t 
                         double *Y, int64_t ldy, void *stream);
 /* 1 when spmv_plan_run_multi can run this plan, else 0 (also for NULL). */
 int spmv_plan_multi_supported(const spmv_plan *p);
+/* The balanced mode of spmv_plan_run_multi for CSR matrices with long rows
+ * (opt-in, built once like spmv_plan_prepare_transpose).  Without it every
+ * row is summed by one group of `lanes` entry lanes, so a hub row of 1e4-1e5
+ * entries is walked by a handful of lanes while the rest of the chip waits.
+ * SPMV_M_BALANCED splits the rows in two bins:
+ *   - rows of at most long_len entries: csr_multi_kernel as before, in the
+ *     same order and with the same bits as on a plan that was not prepared;
+ *   - longer rows: cut into segments of at most seg_len consecutive entries
+ *     (spmv_csr_multi_plan, spmv_host.h), each summed by 16 entry lanes
+ *     (csr_multi_long_kernel); a row of several segments gets its partial
+ *     sums added in segment order by csr_multi_finish_kernel.
+ * No atomics and a fixed order: results stay bitwise reproducible, and the
+ * bit rule of spmv_plan_run_multi holds (column j's bits do not depend on k,
+ * j's place, ldx / ldy or the access path); the bits of a long row differ
+ * from the unprepared run's (another summation order, the same 1e-6
+ * criterion and fp64 bound).  A plan without long rows launches nothing
+ * extra.
+ * Options (spmv_multi_opts_init: both -1 = the library's rule):
+ *   long_len   rows longer than this are long; rule 32 x the plan's lanes
+ *              per row; >= 0
+ *   seg_len    entries per segment; rule 512; >= 1
+ * spmv_plan_prepare_multi (build time) may allocate and synchronises the
+ * plan's d.stream: it copies row_ptr to the host (the matrix may exist only
+ * in device memory), runs the host planner, uploads its tables and
+ * allocates the partial workspace (slots x 8 doubles).  The same mode and
+ * options again is a no-op; other options rebuild; SPMV_M_NONE frees
+ * everything and restores the unprepared run; spmv_plan_destroy frees
+ * whatever was built.  CSR plans only (every path, with or without a
+ * hot-column table: the caller's col is read, never the hot copy).
+ * SPMV_OTHER_ERROR with a message, the plan left as it was: NULL plan, unknown
+ * mode, long_len < -1, seg_len < -1 or 0, a plan that is not CSR.
+ * With SPMV_T_COPY the mode and options extend to the inner plan over A^T
+ * (rule values resolved against the inner plan's own lanes), whichever of
+ * spmv_plan_prepare_multi / spmv_plan_prepare_transpose comes first, and
+ * end with either; scatter mode is not affected.
+ * spmv_plan_run_multi itself is unchanged: no allocation, no synchronisation,
+ * capturable.  The partial workspace belongs to the plan, so two balanced
+ * runs of ONE plan must not overlap in time, on different streams either
+ * (the tiled forward run's rule).  The new bytes are reported here only:
+ * spmv_plan_get_info, spmv_transpose_info and spmv_transpose_multi_info
+ * answer as before.
+ * Which to call (MI355X, profiles/spmm/README.md): on the 100,000-row /
+ * 1,000,000-entry power-law R-MAT a balanced run took 0.025 / 0.031 / 0.036 ms
+ * at k = 2 / 4 / 8 against 0.46 / 0.49 / 0.49 ms unprepared (14 to 18 times
+ * faster) and against 0.029 / 0.057 / 0.114 ms for k spmv_plan_run calls
+ * (level to 1.15 / 1.8 / 3.2 times faster).  On matrices without long rows
+ * (cant-like) nothing extra is launched and the two runs are within 5 % of
+ * each other.  The rule was picked by a sweep on that R-MAT (lanes = 2):
+ * long_len of 64 and 128 x lanes is 1.5 times slower, 16 x lanes a few
+ * microseconds faster there but would make ordinary 64-entry rows long at
+ * lanes = 4; seg_len 512 beats 256, 1,024 and 2,048.                      */
+enum spmv_multi_mode { SPMV_M_NONE = 0, SPMV_M_BALANCED = 1 };
+typedef struct spmv_multi_opts {
+    int32_t long_len;
+    int32_t seg_len;
+} spmv_multi_opts;
+typedef struct spmv_multi_info {
+    int32_t mode;          /* enum spmv_multi_mode */
+    int32_t long_len;      /* resolved thresholds (0 when not prepared) */
+    int32_t seg_len;
+    int32_t reserved;
+    int64_t long_rows;     /* rows of more than long_len entries */
+    int64_t segments;
+    int64_t slots;         /* partial slots (segments of rows with several) */
+    int64_t long_entries;  /* entries of the long rows */
+    int64_t owned_bytes;   /* device bytes of the tables and the workspace */
+    int64_t t_long_rows;   /* copy mode's inner plan over A^T; 0 without one */
+    int64_t t_segments;
+    int64_t t_owned_bytes;
+    char kernel[64];       /* the long rows' kernel ("" when not prepared) */
+} spmv_multi_info;
+void spmv_multi_opts_init(spmv_multi_opts *o);
+int spmv_plan_prepare_multi(spmv_plan *p, int mode, const spmv_multi_opts *o /* NULL: the rules */);
+int spmv_plan_get_multi_info(const spmv_plan *p, spmv_multi_info *info);
 /* The transposed product y = A^T x on the same plan: A is n_rows x n_cols,
  * x[n_rows], y[n_cols].  CSR plans only (every path); two modes, built by
  * spmv_plan_prepare_transpose:
@@ -236,7 +310,8 @@ int spmv_plan_multi_supported(const spmv_plan *p);
  *       plan-owned bytes) and run by an inner forward CSR plan with default
  *       options, whose rules pick its kernel from A^T's own row lengths.
  *       Bitwise reproducible: the bits of a forward CSR plan with default
- *       options on the same three arrays.
+ *       options on the same three arrays (prepared by
+ *       spmv_plan_prepare_multi as the outer plan is, if it is).
  * spmv_plan_prepare_transpose (build time) runs on the plan's d.stream and
  * synchronises it before returning, so runs may come on any stream.
  * Preparing the mode the plan already has is a no-op; preparing the other
@@ -297,7 +372,9 @@ int spmv_plan_run_t(const spmv_plan *p, const double *x, double *y, void *stream
  *     nothing else, so its bit rule carries over: the bits of column j are
  *     those of spmv_plan_run_multi on a default forward CSR plan over
  *     spmv_csr_transpose's arrays, independent of k, of j's place in its
- *     block of 8 and of ldx / ldy.
+ *     block of 8 and of ldx / ldy.  An outer plan prepared with
+ *     spmv_plan_prepare_multi runs the inner plan balanced too: the bits of
+ *     that forward plan prepared with the same options.
  * SPMV_T_SCATTER: csr_t_multi_kernel<KV>, KV in {1, 2, 4, 8}.  The matrix is
  *     streamed once per block of up to 8 vectors (ceil(k/8) passes, pass b on
  *     X + 8b, Y + 8b); a block of r remaining vectors runs the smallest
@@ -315,11 +392,15 @@ int spmv_plan_run_t(const spmv_plan *p, const double *x, double *y, void *stream
  * 2.4 / 5.5 times faster in scatter mode on a power-law R-MAT (every product
  * a global atomic either way) and 1.2-1.4 / 1.9-2.1 / 2.3-3.0 times faster in
  * copy mode on cant-like matrices.  In COPY mode on the power-law R-MAT one
- * call was 5 to 20 times SLOWER than k calls (spmv_plan_run_multi has no
- * entry-balanced kernel for the hub rows of A^T): call spmv_plan_run_t k times
- * there.  One vector belongs to spmv_plan_run_t (k == 1 with ldx == ldy == 1 is
- * that very launch in scatter mode; in copy mode spmv_plan_run_multi at k = 1
- * is slower than spmv_plan_run).                                            */
+ * call on an unprepared plan was 5 to 20 times SLOWER than k calls (the hub
+ * rows of A^T are walked by two lanes each): prepare the plan with
+ * spmv_plan_prepare_multi(SPMV_M_BALANCED) there, after which one call took
+ * 0.036 / 0.040 / 0.046 ms at k = 2 / 4 / 8, 13 to 16 times less than
+ * unprepared and 0.84 / 1.5 / 2.6 times the speed of k spmv_plan_run_t calls
+ * (at k = 2 the two calls are still the faster way).  One vector belongs to
+ * spmv_plan_run_t (k == 1 with ldx == ldy == 1 is that very launch in scatter
+ * mode; in copy mode spmv_plan_run_multi at k = 1 is slower than
+ * spmv_plan_run).                                                           */
 int spmv_plan_run_t_multi(const spmv_plan *p, int32_t k, const double *X, int64_t ldx,
                           double *Y, int64_t ldy, void *stream);
 typedef struct spmv_transpose_multi_info {

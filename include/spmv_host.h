@@ -128,6 +128,27 @@ int spmv_hot_columns_possible(int64_t n_cols, int64_t H_req);
 int64_t spmv_csr_tiled_bigplan(int64_t n_rows, const int64_t *row_ptr, int64_t tile, int32_t cap,
                                int32_t *plan);
 
+/* Long-row plan of the balanced multi-vector CSR run
+ * (spmv_plan_prepare_multi, spmv.h).  A row is long when it holds more than
+ * long_len entries; every long row, in increasing row order, is cut into
+ * segments of seg_len consecutive entries (the row's last segment holds the
+ * rest, 1..seg_len).  Segment s covers entries [seg_beg[s], seg_beg[s] +
+ * seg_cnt[s]).  A row of one segment has seg_dest[s] = the row (its sums go
+ * straight to Y); a row of more segments takes consecutive partial slots in
+ * segment order and seg_dest[s] = ~slot.  long_row[i] / long_first[i], i <
+ * n_long, are the long rows and the first slot of each; the slots of row i
+ * are [long_first[i], long_first[i+1]) (none for a row of one segment), and
+ * the closing entry i = n_long holds row -1 and n_slots.
+ * Two calls: with the five arrays NULL only the counts are written; then
+ * seg_beg[n_seg] (int64), seg_cnt / seg_dest[n_seg], long_row /
+ * long_first[n_long + 1] (int32).  SPMV_OTHER_ERROR with nothing written:
+ * n_rows < 0, NULL row_ptr or count pointer, decreasing row_ptr, long_len <
+ * 0, seg_len < 1, some but not all arrays NULL, a long row past INT32_MAX,
+ * more than INT32_MAX segments.                                          */
+int spmv_csr_multi_plan(int64_t n_rows, const int64_t *row_ptr, int32_t long_len, int32_t seg_len, int64_t *n_long,
+                        int64_t *n_seg, int64_t *n_slots, int64_t *seg_beg, int32_t *seg_cnt, int32_t *seg_dest,
+                        int32_t *long_row, int32_t *long_first);
+
 /* Degree-ordered column relabel (power-law columns, x replicated): the
  * columns ranked by decreasing entry count (ties: lower column first;
  * columns without entries last, in id order).  order[rank] = column,

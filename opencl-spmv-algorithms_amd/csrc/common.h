@@ -137,8 +137,25 @@ int launch_carry(int64_t tiles, const int32_t *carry_row, const double *carry_va
 
 // multi-vector runs Y = A X (spmm.hip; the contract is spmv_plan_run_multi's,
 // spmv.h): blocks of up to 8 vectors, one pass over the matrix each
+// the long-row tables of a balanced plan (spmv_plan_prepare_multi; device
+// pointers, laid out by spmv_csr_multi_plan) and its partial workspace of
+// n_slots x 8 doubles
+struct MultiBalance {
+    int32_t long_len = 0;
+    int64_t n_long = 0, n_seg = 0, n_slots = 0;
+    const int64_t *seg_beg = nullptr;
+    const int32_t *seg_cnt = nullptr, *seg_dest = nullptr, *long_row = nullptr, *long_first = nullptr;
+    double *part = nullptr;
+};
+// the library's rule (spmv_multi_opts of -1): a row is long past
+// kMultiLongPerLane entries per entry lane of the row kernel; segments of
+// kMultiSegLen entries (profiles/spmm/README.md has the sweep)
+constexpr int32_t kMultiLongPerLane = 32;
+constexpr int32_t kMultiSegLen = 512;
+// bal = NULL: every row by the row kernel (a plan that was not prepared)
 int launch_csr_multi(const spmv_dims &d, int L, const int64_t *row_ptr, const int32_t *col, const double *val,
-                     int32_t k, const double *X, int64_t ldx, double *Y, int64_t ldy);
+                     int32_t k, const double *X, int64_t ldx, double *Y, int64_t ldy,
+                     const MultiBalance *bal = nullptr);
 // SELL (sell: C, n_slices, slice_ptr, perm) or ELL (K, ld)
 int launch_slot_multi(const spmv_dims &d, bool sell, int32_t ki, int32_t C, int64_t n_slices, const int64_t *slice_ptr,
                       const int32_t *perm, int32_t K, int64_t ld, const int32_t *col, const double *val, int32_t k,

@@ -54,9 +54,19 @@ struct spmv_plan {
     double *t_val = nullptr;
     spmv_plan *t_inner = nullptr;  // copy: the forward CSR plan over A^T
     size_t t_owned = 0;
+    // the balanced multi-vector mode (spmv_plan_prepare_multi, plan.hip); its
+    // bytes are counted in m_owned, never in `owned` or t_owned
+    int32_t m_mode = 0;                // enum spmv_multi_mode
+    spmv_multi_opts m_req = {-1, -1};  // the options as asked for (-1: the rule)
+    int32_t m_seg_len = 0;             // resolved; the resolved long_len is m_bal.long_len
+    int64_t m_long_entries = 0;
+    spmv::MultiBalance m_bal;          // counts, device tables, partial workspace (plan-owned)
+    size_t m_owned = 0;
 };
 
 namespace spmv {
+// frees what spmv_plan_prepare_multi built on this plan (the plan's device is current)
+void plan_multi_free(spmv_plan *p);
 // frees what spmv_plan_prepare_transpose built (the plan's device is current)
 void plan_transpose_free(spmv_plan *p);
 }  // namespace spmv

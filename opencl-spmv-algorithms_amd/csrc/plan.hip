@@ -77,6 +77,25 @@ __global__ __launch_bounds__(kBlock) void max_len_kernel(int64_t n, const int64_
     }
 }
 
+static void multi_tables_free(MultiBalance &m)
+{
+    for (const void *q : {(const void *)m.seg_beg, (const void *)m.seg_cnt, (const void *)m.seg_dest,
+                          (const void *)m.long_row, (const void *)m.long_first, (const void *)m.part})
+        if (q)
+            (void)hipFree(const_cast<void *>(q));
+    m = MultiBalance();
+}
+
+void plan_multi_free(spmv_plan *p)
+{
+    multi_tables_free(p->m_bal);
+    p->m_mode = SPMV_M_NONE;
+    p->m_req = {-1, -1};
+    p->m_seg_len = 0;
+    p->m_long_entries = 0;
+    p->m_owned = 0;
+}
+
 }  // namespace spmv
 
 using namespace spmv;
@@ -259,6 +278,7 @@ int spmv_plan_destroy(spmv_plan *p)
     if (dev != p->d.device)
         (void)hipSetDevice(p->d.device);
     plan_transpose_free(p);
+    plan_multi_free(p);
     for (void *q : owned)
         if (q)
             (void)hipFree(q);
@@ -810,13 +830,176 @@ int spmv_plan_run_multi(const spmv_plan *p, int32_t k, const double *X, int64_t 
     // original column ids, no hot table and no LDS window)
     switch (p->fmt) {
     case SPMV_FMT_CSR:
-        return launch_csr_multi(d, p->lanes, p->ptr, p->col, p->val, k, X, ldx, Y, ldy);
+        return launch_csr_multi(d, p->lanes, p->ptr, p->col, p->val, k, X, ldx, Y, ldy,
+                                p->m_mode == SPMV_M_BALANCED ? &p->m_bal : nullptr);
     case SPMV_FMT_ELL:
         return launch_slot_multi(d, false, p->ki, 0, 0, nullptr, nullptr, p->K, p->ld, p->col, p->val, k, X, ldx, Y, ldy);
     default:
         return launch_slot_multi(d, true, p->ki, p->C, p->n_slices, p->ptr, p->perm, 0, 0, p->col, p->val, k, X, ldx, Y,
                                  ldy);
     }
+}
+
+// ------------------------------------------- balanced multi-vector mode
+void spmv_multi_opts_init(spmv_multi_opts *o)
+{
+    if (!o)
+        return;
+    o->long_len = -1;
+    o->seg_len = -1;
+}
+
+// one plan-owned table of the balanced mode: uploaded on the build stream
+// (synchronised by the caller), its bytes added to *owned
+static int multi_upload(const spmv_plan *p, const void **dst, const void *src, size_t bytes, size_t *owned)
+{
+    void *q = nullptr;
+    hipError_t e = hipMalloc(&q, bytes > 0 ? bytes : 16);
+    if (e != hipSuccess)
+        return fail(SPMV_PROGRAM_ERROR, "spmv_plan_prepare_multi: hipMalloc", e);
+    *dst = q;
+    *owned += bytes;
+    if (src && bytes > 0 &&
+        (e = hipMemcpyAsync(q, src, bytes, hipMemcpyHostToDevice, (hipStream_t)p->d.stream)) != hipSuccess)
+        return fail(SPMV_PROGRAM_ERROR, "spmv_plan_prepare_multi: upload", e);
+    return SPMV_SUCCESS;
+}
+
+// The tables of spmv_csr_multi_plan for (long_len, seg_len) on the device and
+// the partial workspace, into *m (freed by the caller on failure).
+static int multi_build(const spmv_plan *p, int32_t long_len, int32_t seg_len, MultiBalance *m, int64_t *long_entries,
+                       size_t *owned)
+{
+    int64_t *hp = nullptr;
+    int rc = download_offsets(p, p->ptr, p->d.n_rows, &hp);
+    if (rc != SPMV_SUCCESS)
+        return rc;
+    int64_t nl = 0, ns = 0, nsl = 0;
+    if (spmv_csr_multi_plan(p->d.n_rows, hp, long_len, seg_len, &nl, &ns, &nsl, nullptr, nullptr, nullptr, nullptr,
+                            nullptr) != SPMV_SUCCESS) {
+        free(hp);
+        return fail_msg(SPMV_OTHER_ERROR, "spmv_plan_prepare_multi: long-row plan refused (row_ptr not "
+                                          "nondecreasing, or more than 2^31 segments)");
+    }
+    int64_t *sb = (int64_t *)malloc((size_t)(ns + 1) * sizeof(int64_t));
+    int32_t *i32 = (int32_t *)malloc((size_t)(2 * ns + 2 * (nl + 1)) * sizeof(int32_t));
+    if (!sb || !i32) {
+        free(sb);
+        free(i32);
+        free(hp);
+        return fail_msg(SPMV_OTHER_ERROR, "spmv_plan_prepare_multi: out of host memory");
+    }
+    int32_t *sc = i32, *sd = i32 + ns, *lr = i32 + 2 * ns, *lf = lr + nl + 1;
+    rc = spmv_csr_multi_plan(p->d.n_rows, hp, long_len, seg_len, &nl, &ns, &nsl, sb, sc, sd, lr, lf);
+    free(hp);
+    if (rc != SPMV_SUCCESS)
+        rc = fail_msg(SPMV_OTHER_ERROR, "spmv_plan_prepare_multi: long-row plan refused");
+    *long_entries = 0;
+    for (int64_t s = 0; rc == SPMV_SUCCESS && s < ns; ++s)
+        *long_entries += sc[s];
+    m->long_len = long_len;
+    m->n_long = nl;
+    m->n_seg = ns;
+    m->n_slots = nsl;
+    if (rc == SPMV_SUCCESS && ns > 0) {  // without long rows a run launches the row kernel alone: no tables
+        const void *part = nullptr;
+        if ((rc = multi_upload(p, (const void **)&m->seg_beg, sb, (size_t)ns * sizeof(int64_t), owned)) ==
+                SPMV_SUCCESS &&
+            (rc = multi_upload(p, (const void **)&m->seg_cnt, sc, (size_t)ns * sizeof(int32_t), owned)) ==
+                SPMV_SUCCESS &&
+            (rc = multi_upload(p, (const void **)&m->seg_dest, sd, (size_t)ns * sizeof(int32_t), owned)) ==
+                SPMV_SUCCESS &&
+            (rc = multi_upload(p, (const void **)&m->long_row, lr, (size_t)(nl + 1) * sizeof(int32_t), owned)) ==
+                SPMV_SUCCESS &&
+            (rc = multi_upload(p, (const void **)&m->long_first, lf, (size_t)(nl + 1) * sizeof(int32_t), owned)) ==
+                SPMV_SUCCESS &&
+            (rc = multi_upload(p, &part, nullptr, (size_t)nsl * 8 * sizeof(double), owned)) == SPMV_SUCCESS)
+            m->part = (double *)const_cast<void *>(part);
+        // the uploads read sb / i32: complete before they are freed
+        if (hipStreamSynchronize((hipStream_t)p->d.stream) != hipSuccess && rc == SPMV_SUCCESS)
+            rc = fail_msg(SPMV_PROGRAM_ERROR, "spmv_plan_prepare_multi: synchronise");
+    }
+    free(sb);
+    free(i32);
+    return rc;
+}
+
+int spmv_plan_prepare_multi(spmv_plan *p, int mode, const spmv_multi_opts *o)
+{
+    if (!p)
+        return fail_msg(SPMV_OTHER_ERROR, "spmv_plan_prepare_multi: plan is NULL");
+    if (mode != SPMV_M_NONE && mode != SPMV_M_BALANCED)
+        return fail_msg(SPMV_OTHER_ERROR, "spmv_plan_prepare_multi: unknown mode");
+    if (p->fmt != SPMV_FMT_CSR)
+        return fail_msg(SPMV_OTHER_ERROR, "spmv_plan_prepare_multi: only CSR plans have a balanced multi-vector run");
+    spmv_multi_opts req = {-1, -1};
+    if (o)
+        req = *o;
+    if (req.long_len < -1 || req.seg_len < -1 || req.seg_len == 0)
+        return fail_msg(SPMV_OTHER_ERROR, "spmv_plan_prepare_multi: long_len must be -1 or >= 0, seg_len -1 or >= 1");
+    SPMV_GUARD(p->d);
+    const hipStream_t st = (hipStream_t)p->d.stream;
+    if (mode == SPMV_M_NONE) {
+        if (p->m_mode == SPMV_M_NONE)
+            return SPMV_SUCCESS;
+        // a balanced run may still be in flight on the build stream
+        if (hipStreamSynchronize(st) != hipSuccess)
+            return fail_msg(SPMV_PROGRAM_ERROR, "spmv_plan_prepare_multi: synchronise");
+        plan_multi_free(p);
+        return p->t_inner ? spmv_plan_prepare_multi(p->t_inner, SPMV_M_NONE, nullptr) : SPMV_SUCCESS;
+    }
+    if (mode == p->m_mode && req.long_len == p->m_req.long_len && req.seg_len == p->m_req.seg_len)
+        return SPMV_SUCCESS;
+    const int64_t rule_long = (int64_t)kMultiLongPerLane * p->lanes;
+    const int32_t long_len = req.long_len >= 0 ? req.long_len : (int32_t)rule_long;
+    const int32_t seg_len = req.seg_len >= 1 ? req.seg_len : kMultiSegLen;
+    MultiBalance m;
+    int64_t long_entries = 0;
+    size_t owned = 0;
+    int rc = multi_build(p, long_len, seg_len, &m, &long_entries, &owned);
+    // copy mode: the inner plan over A^T follows (it keeps its state when refused)
+    if (rc == SPMV_SUCCESS && p->t_inner)
+        rc = spmv_plan_prepare_multi(p->t_inner, mode, &req);
+    if (rc == SPMV_SUCCESS && hipStreamSynchronize(st) != hipSuccess)
+        rc = fail_msg(SPMV_PROGRAM_ERROR, "spmv_plan_prepare_multi: synchronise");
+    if (rc != SPMV_SUCCESS) {
+        char keep[512];
+        snprintf(keep, sizeof keep, "%s", spmv_last_error());
+        multi_tables_free(m);
+        return fail_msg(rc, keep);
+    }
+    plan_multi_free(p);  // the previous options' tables (the stream is idle)
+    p->m_mode = mode;
+    p->m_req = req;
+    p->m_seg_len = seg_len;
+    p->m_long_entries = long_entries;
+    p->m_bal = m;
+    p->m_owned = owned;
+    return SPMV_SUCCESS;
+}
+
+int spmv_plan_get_multi_info(const spmv_plan *p, spmv_multi_info *info)
+{
+    if (!p || !info)
+        return fail_msg(SPMV_OTHER_ERROR, "spmv_plan_get_multi_info: NULL argument");
+    memset(info, 0, sizeof *info);
+    info->mode = p->m_mode;
+    if (p->m_mode == SPMV_M_NONE)
+        return SPMV_SUCCESS;
+    info->long_len = p->m_bal.long_len;
+    info->seg_len = p->m_seg_len;
+    info->long_rows = p->m_bal.n_long;
+    info->segments = p->m_bal.n_seg;
+    info->slots = p->m_bal.n_slots;
+    info->long_entries = p->m_long_entries;
+    info->owned_bytes = (int64_t)p->m_owned;
+    if (p->t_inner) {
+        info->t_long_rows = p->t_inner->m_bal.n_long;
+        info->t_segments = p->t_inner->m_bal.n_seg;
+        info->t_owned_bytes = (int64_t)p->t_inner->m_owned;
+    }
+    snprintf(info->kernel, sizeof info->kernel, "%s", p->m_bal.n_seg > 0 ? "csr_multi_long_kernel" : "csr_multi_kernel");
+    return SPMV_SUCCESS;
 }
 
 int spmv_plan_get_info(const spmv_plan *p, spmv_plan_info *info)

@@ -22,6 +22,13 @@
 // ldy and alignment.  The loops below only batch LOADS (E entries in
 // flight); the fma order per column is always entry by entry.
 //
+// Balanced mode (spmv_plan_prepare_multi, CSR): csr_multi_kernel<.., BAL> leaves
+// the rows of more than long_len entries to csr_multi_long_kernel (16 entry
+// lanes per segment of at most seg_len entries, the same per-lane fma order
+// and butterfly) and csr_multi_finish_kernel (a split row's partial sums,
+// added in segment order).  No atomics: the order is fixed by the plan, so the
+// bit rule holds there too; rows up to long_len keep the unprepared bits.
+//
 // Access paths (VEC): 16-byte loads of X rows and stores of Y rows are used
 // only for a full block (r == KV >= 2) whose X (and, where Y is stored in
 // pairs, Y) rows the host has proven 16-byte aligned (base address and
@@ -86,38 +93,23 @@ __device__ __forceinline__ double entry_lane_sum(double v)
     }
 }
 
-// CSR: L entry lanes own one row (as csr_vector_kernel); entry lane l takes
-// entries beg+l, beg+l+L, ... in that order; each entry lane is P lanes with
-// CPL columns each (L·P <= 64).  The sums are reduced over the entry lanes;
-// entry lane 0's P lanes store the row.
+// The sums of one lane group over the entries e, e + L, ... < end (e = the
+// group's first entry + the entry lane l): one accumulator per column, fed by
+// one fma per entry in that order, E entries' loads in flight; then the
+// butterfly over the L entry lanes.  Whole waves call it (the butterfly moves
+// data between lanes); a group without work passes e >= end.  Shared by the
+// row kernel (L from the plan) and the segment kernel (L = 16).  The pointers
+// are the kernels' __restrict__ arguments; they are NOT qualified again here:
+// a second noalias scope changes the schedule of the instantiations with one
+// wave per row (unprepared lanes = 64 runs measured 7-11 % slower with it).
 template <int L, int KV, bool VEC>
-__global__ __launch_bounds__(kBlock) void csr_multi_kernel(
-    int64_t n_rows, const int64_t *__restrict__ row_ptr, const int32_t *__restrict__ col,
-    const double *__restrict__ val, const double *__restrict__ X, int64_t ldx, double *__restrict__ Y,
-    int64_t ldy, int32_t r)
+__device__ __forceinline__ void multi_group_sums(int64_t e, int64_t end, const int32_t *col, const double *val,
+                                                 const double *X, int64_t ldx, int j0, int32_t r,
+                                                 double (&acc)[KV / multi_p<KV, kWave / L>()])
 {
     constexpr int P = multi_p<KV, kWave / L>();
-    constexpr int CPL = KV / P;      // columns per lane
-    constexpr int G = L * P;         // lanes per row
-    constexpr int RPB = kBlock / G;  // rows per workgroup
+    constexpr int CPL = KV / P;
     constexpr int E = multi_inflight<CPL>();
-    __shared__ int64_t s_ptr[RPB + 1];
-
-    const int64_t row0 = (int64_t)blockIdx.x * RPB;
-    if (threadIdx.x <= RPB) {
-        const int64_t rr = row0 + threadIdx.x;
-        s_ptr[threadIdx.x] = row_ptr[rr < n_rows ? rr : n_rows];
-    }
-    __syncthreads();
-
-    const int g = threadIdx.x / G;
-    const int l = (threadIdx.x % G) / P;
-    const int j0 = (threadIdx.x % P) * CPL;
-    const int64_t row = row0 + g;
-    const int64_t end = s_ptr[g + 1];  // rows past n_rows are empty
-    int64_t e = s_ptr[g] + l;
-
-    double acc[CPL];
 #pragma unroll
     for (int i = 0; i < CPL; ++i)
         acc[i] = 0.0;
@@ -154,7 +146,50 @@ __global__ __launch_bounds__(kBlock) void csr_multi_kernel(
 #pragma unroll
     for (int i = 0; i < CPL; ++i)
         acc[i] = entry_lane_sum<L, P>(acc[i]);
-    if (row < n_rows && l == 0) {
+}
+
+// CSR: L entry lanes own one row (as csr_vector_kernel); entry lane l takes
+// entries beg+l, beg+l+L, ... in that order; each entry lane is P lanes with
+// CPL columns each (L·P <= 64).  The sums are reduced over the entry lanes;
+// entry lane 0's P lanes store the row.  BAL (a plan prepared with
+// SPMV_M_BALANCED): a row of more than long_len entries belongs to
+// csr_multi_long_kernel; this kernel sums nothing for it and stores nothing.
+template <int L, int KV, bool VEC, bool BAL>
+__global__ __launch_bounds__(kBlock) void csr_multi_kernel(
+    int64_t n_rows, const int64_t *__restrict__ row_ptr, const int32_t *__restrict__ col,
+    const double *__restrict__ val, const double *__restrict__ X, int64_t ldx, double *__restrict__ Y,
+    int64_t ldy, int32_t r, int32_t long_len)
+{
+    constexpr int P = multi_p<KV, kWave / L>();
+    constexpr int CPL = KV / P;      // columns per lane
+    constexpr int G = L * P;         // lanes per row
+    constexpr int RPB = kBlock / G;  // rows per workgroup
+    __shared__ int64_t s_ptr[RPB + 1];
+
+    const int64_t row0 = (int64_t)blockIdx.x * RPB;
+    if (threadIdx.x <= RPB) {
+        const int64_t rr = row0 + threadIdx.x;
+        s_ptr[threadIdx.x] = row_ptr[rr < n_rows ? rr : n_rows];
+    }
+    __syncthreads();
+
+    const int g = threadIdx.x / G;
+    const int l = (threadIdx.x % G) / P;
+    const int j0 = (threadIdx.x % P) * CPL;
+    const int64_t row = row0 + g;
+    const int64_t beg = s_ptr[g];
+    int64_t end = s_ptr[g + 1];  // rows past n_rows are empty
+    bool mine = true;
+    if constexpr (BAL) {
+        if (end - beg > long_len) {
+            mine = false;
+            end = beg;
+        }
+    }
+
+    double acc[CPL];
+    multi_group_sums<L, KV, VEC>(beg + l, end, col, val, X, ldx, j0, r, acc);
+    if (row < n_rows && l == 0 && mine) {
         double *yr = Y + row * ldy;
 #pragma unroll
         for (int i = 0; i < CPL; ++i) {
@@ -162,6 +197,79 @@ __global__ __launch_bounds__(kBlock) void csr_multi_kernel(
                 yr[j0 + i] = acc[i];
         }
     }
+}
+
+// The long rows of a balanced plan (spmv_csr_multi_plan, spmv_host.h): one
+// group of 16 entry lanes x P lanes per SEGMENT of at most seg_len consecutive
+// entries of one row, summed exactly as a row of csr_multi_kernel<16, KV>.
+// The entry-lane count is 16 for every KV, so a column's bits do not depend on
+// the width of its block.  dest >= 0: the segment is its row's only one and
+// the sums are Y[dest]; dest < 0: the sums go to partial slot ~dest (8 doubles,
+// column j at word j) for csr_multi_finish_kernel.  Every table value is
+// checked against the counts before it is used as an index.
+constexpr int kMultiLongL = 16;
+
+template <int KV, bool VEC>
+__global__ __launch_bounds__(kBlock) void csr_multi_long_kernel(
+    int64_t n_rows, int64_t nnz, int64_t n_seg, int64_t n_slots, const int64_t *__restrict__ seg_beg,
+    const int32_t *__restrict__ seg_cnt, const int32_t *__restrict__ seg_dest, const int32_t *__restrict__ col,
+    const double *__restrict__ val, const double *__restrict__ X, int64_t ldx, double *__restrict__ Y,
+    int64_t ldy, double *__restrict__ part, int32_t r)
+{
+    constexpr int L = kMultiLongL;
+    constexpr int P = multi_p<KV, kWave / L>();
+    constexpr int CPL = KV / P;
+    constexpr int G = L * P;         // lanes per segment
+    constexpr int SPB = kBlock / G;  // segments per workgroup
+
+    const int64_t seg = (int64_t)blockIdx.x * SPB + threadIdx.x / G;
+    const int l = (threadIdx.x % G) / P;
+    const int j0 = (threadIdx.x % P) * CPL;
+    int64_t beg = 0, cnt = 0, dest = 0;
+    bool own = false;
+    if (seg < n_seg) {
+        beg = seg_beg[seg];
+        cnt = seg_cnt[seg];
+        dest = seg_dest[seg];
+        own = beg >= 0 && cnt >= 0 && beg <= nnz - cnt && (dest >= 0 ? dest < n_rows : ~dest < n_slots);
+    }
+    if (!own)
+        cnt = 0;
+
+    double acc[CPL];
+    multi_group_sums<L, KV, VEC>(beg + l, beg + cnt, col, val, X, ldx, j0, r, acc);
+    if (own && l == 0) {
+        double *out = dest >= 0 ? Y + dest * ldy : part + ~dest * 8;
+#pragma unroll
+        for (int i = 0; i < CPL; ++i) {
+            if (j0 + i < r)
+                out[j0 + i] = acc[i];
+        }
+    }
+}
+
+// Y[row] of every split long row: slot0 + slot1 + ... in segment order, one
+// thread per (row, column j < r).  Always overwrites Y, stores nothing for
+// j >= r; a table entry outside the counts is skipped.
+template <int KV>
+__global__ __launch_bounds__(kBlock) void csr_multi_finish_kernel(
+    int64_t n_rows, int64_t n_long, int64_t n_slots, const int32_t *__restrict__ long_row,
+    const int32_t *__restrict__ long_first, const double *__restrict__ part, double *__restrict__ Y, int64_t ldy,
+    int32_t r)
+{
+    const int64_t t = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    const int64_t i = t / KV;
+    const int j = (int)(t % KV);
+    if (i >= n_long || j >= r)
+        return;
+    const int64_t row = long_row[i];
+    const int64_t first = long_first[i], last = long_first[i + 1];
+    if (row < 0 || row >= n_rows || first < 0 || last > n_slots || first >= last)
+        return;
+    double s = part[first * 8 + j];
+    for (int64_t q = first + 1; q < last; ++q)
+        s += part[q * 8 + j];
+    Y[row * ldy + j] = s;
 }
 
 // One KI-group of a slot-per-lane row: KI values and columns, non-temporal
@@ -336,17 +444,41 @@ MultiBlock multi_block(int32_t k, int32_t j0, const double *X, int64_t ldx, doub
 
 template <int L, int KV>
 void launch_csr_multi_kv(const spmv_dims &d, const int64_t *row_ptr, const int32_t *col, const double *val,
-                         const MultiBlock &b, int64_t ldx, int64_t ldy)
+                         const MultiBlock &b, int64_t ldx, int64_t ldy, const MultiBalance *bal)
 {
     constexpr int RPB = kBlock / (L * multi_p<KV, kWave / L>());  // rows per workgroup, >= 4
     const int64_t blocks = (d.n_rows + RPB - 1) / RPB;
-    auto kern = csr_multi_kernel<L, KV, false>;
+    with_bool(bal != nullptr, [&](auto BAL) {
+        constexpr bool bl = decltype(BAL)::value;
+        auto kern = csr_multi_kernel<L, KV, false, bl>;
+        if constexpr (KV >= 2) {
+            if (b.vec)
+                kern = csr_multi_kernel<L, KV, true, bl>;
+        }
+        hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(kBlock), 0, (hipStream_t)d.stream, d.n_rows, row_ptr,
+                           col, val, b.X, ldx, b.Y, ldy, b.r, bal ? bal->long_len : 0);
+    });
+}
+
+// the long rows of a balanced plan: their segments, then the split rows' sums
+template <int KV>
+void launch_csr_multi_long_kv(const spmv_dims &d, const int32_t *col, const double *val, const MultiBlock &b,
+                              int64_t ldx, int64_t ldy, const MultiBalance &m)
+{
+    constexpr int SPB = kBlock / (kMultiLongL * multi_p<KV, kWave / kMultiLongL>());  // segments per workgroup
+    const hipStream_t st = (hipStream_t)d.stream;
+    auto kern = csr_multi_long_kernel<KV, false>;
     if constexpr (KV >= 2) {
         if (b.vec)
-            kern = csr_multi_kernel<L, KV, true>;
+            kern = csr_multi_long_kernel<KV, true>;
     }
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(kBlock), 0, (hipStream_t)d.stream, d.n_rows, row_ptr, col,
-                       val, b.X, ldx, b.Y, ldy, b.r);
+    hipLaunchKernelGGL(kern, dim3((unsigned)((m.n_seg + SPB - 1) / SPB)), dim3(kBlock), 0, st, d.n_rows, d.nnz,
+                       m.n_seg, m.n_slots, m.seg_beg, m.seg_cnt, m.seg_dest, col, val, b.X, ldx, b.Y, ldy, m.part,
+                       b.r);
+    if (m.n_slots > 0)
+        hipLaunchKernelGGL(csr_multi_finish_kernel<KV>, dim3((unsigned)((m.n_long * KV + kBlock - 1) / kBlock)),
+                           dim3(kBlock), 0, st, d.n_rows, m.n_long, m.n_slots, m.long_row, m.long_first, m.part, b.Y,
+                           ldy, b.r);
 }
 
 template <int KI, int KV, bool SELL>
@@ -368,7 +500,7 @@ void launch_slot_multi_kv(const spmv_dims &d, int64_t slots, int32_t C, int64_t 
 }  // namespace
 
 int launch_csr_multi(const spmv_dims &d, int L, const int64_t *row_ptr, const int32_t *col, const double *val,
-                     int32_t k, const double *X, int64_t ldx, double *Y, int64_t ldy)
+                     int32_t k, const double *X, int64_t ldx, double *Y, int64_t ldy, const MultiBalance *bal)
 {
     if (L < 2 || L > 64 || (L & (L - 1)))
         return fail_msg(SPMV_OTHER_ERROR, "spmv_plan_run_multi: CSR lanes per row must be a power of two in [2,64]");
@@ -381,10 +513,16 @@ int launch_csr_multi(const spmv_dims &d, int L, const int64_t *row_ptr, const in
         const MultiBlock b = multi_block(k, j0, X, ldx, Y, ldy, false);
         with_int<2, 4, 8, 16, 32, 64>(L, [&](auto Lc) {
             with_int<1, 2, 4, 8>(b.kv, [&](auto KV) {
-                launch_csr_multi_kv<decltype(Lc)::value, decltype(KV)::value>(d, row_ptr, col, val, b, ldx, ldy);
+                launch_csr_multi_kv<decltype(Lc)::value, decltype(KV)::value>(d, row_ptr, col, val, b, ldx, ldy, bal);
             });
         });
         SPMV_CHECK_LAUNCH("csr_multi_kernel");
+        if (bal && bal->n_seg > 0) {  // a plan without long rows launches nothing more
+            with_int<1, 2, 4, 8>(b.kv, [&](auto KV) {
+                launch_csr_multi_long_kv<decltype(KV)::value>(d, col, val, b, ldx, ldy, *bal);
+            });
+            SPMV_CHECK_LAUNCH("csr_multi_long_kernel");
+        }
     }
     return SPMV_SUCCESS;
 }

@@ -14,7 +14,9 @@
 //       every product straight into y (global_atomic_add_f64).
 //   SPMV_T_COPY     A^T built once on the device as CSR (spmv_dev_csr_transpose)
 //       and run by a forward CSR plan with default options: forward speed,
-//       bitwise reproducible, 12 nnz + 8 (n_cols + 1) bytes more.
+//       bitwise reproducible, 12 nnz + 8 (n_cols + 1) bytes more.  The outer
+//       plan's balanced multi-vector mode (spmv_plan_prepare_multi, plan.hip)
+//       extends to that inner plan, whichever is prepared first.
 // Both read the caller's row_ptr / col / val, never the plan's hot-renumbered
 // column copy.
 //
@@ -435,7 +437,10 @@ int prepare_copy(spmv_plan *p)
     spmv_dims t = d;
     t.n_rows = d.n_cols;
     t.n_cols = d.n_rows;
-    return spmv_plan_csr(t, p->t_ptr, p->t_col, p->t_val, nullptr, &p->t_inner);
+    if ((rc = spmv_plan_csr(t, p->t_ptr, p->t_col, p->t_val, nullptr, &p->t_inner)) != SPMV_SUCCESS)
+        return rc;
+    // a balanced outer plan (spmv_plan_prepare_multi) extends to the inner one
+    return p->m_mode != SPMV_M_NONE ? spmv_plan_prepare_multi(p->t_inner, p->m_mode, &p->m_req) : SPMV_SUCCESS;
 }
 
 int launch_scatter(const spmv_plan *p, const double *x, double *y, hipStream_t st)

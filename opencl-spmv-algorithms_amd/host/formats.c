@@ -399,6 +399,57 @@ int64_t spmv_csr_tiled_bigplan(int64_t n_rows, const int64_t *row_ptr, int64_t t
     return len;
 }
 
+int spmv_csr_multi_plan(int64_t n_rows, const int64_t *row_ptr, int32_t long_len, int32_t seg_len, int64_t *n_long,
+                        int64_t *n_seg, int64_t *n_slots, int64_t *seg_beg, int32_t *seg_cnt, int32_t *seg_dest,
+                        int32_t *long_row, int32_t *long_first)
+{
+    const int outs = (seg_beg != NULL) + (seg_cnt != NULL) + (seg_dest != NULL) + (long_row != NULL) +
+                     (long_first != NULL);
+    if (n_rows < 0 || !row_ptr || long_len < 0 || seg_len < 1 || !n_long || !n_seg || !n_slots ||
+        (outs != 0 && outs != 5))
+        return SPMV_OTHER_ERROR;
+    /* pass 1: validate and count (nothing is written before every check passed) */
+    int64_t nl = 0, ns = 0, nsl = 0;
+    for (int64_t r = 0; r < n_rows; ++r) {
+        if (row_ptr[r + 1] < row_ptr[r])
+            return SPMV_OTHER_ERROR;
+        const int64_t len = row_ptr[r + 1] - row_ptr[r];
+        if (len <= long_len)
+            continue;
+        const int64_t segs = (len + seg_len - 1) / seg_len;
+        if (r > INT32_MAX || segs > INT32_MAX - ns)
+            return SPMV_OTHER_ERROR;
+        ++nl;
+        ns += segs;
+        nsl += segs > 1 ? segs : 0;
+    }
+    *n_long = nl;
+    *n_seg = ns;
+    *n_slots = nsl;
+    if (!outs)
+        return SPMV_SUCCESS;
+    /* pass 2: fill */
+    int64_t i = 0, s = 0, slot = 0;
+    for (int64_t r = 0; r < n_rows; ++r) {
+        const int64_t len = row_ptr[r + 1] - row_ptr[r];
+        if (len <= long_len)
+            continue;
+        const int split = len > seg_len;
+        long_row[i] = (int32_t)r;
+        long_first[i] = (int32_t)slot;
+        ++i;
+        for (int64_t b = row_ptr[r]; b < row_ptr[r + 1]; b += seg_len, ++s) {
+            const int64_t left = row_ptr[r + 1] - b;
+            seg_beg[s] = b;
+            seg_cnt[s] = (int32_t)(left < seg_len ? left : seg_len);
+            seg_dest[s] = split ? (int32_t)~slot++ : (int32_t)r;
+        }
+    }
+    long_row[i] = -1;
+    long_first[i] = (int32_t)slot;
+    return SPMV_SUCCESS;
+}
+
 /* Counting sort of the columns by entry count: ranks are handed out from
  * the largest count down, and inside one count in increasing column id, so
  * the order is the same whatever the thread count. */

@@ -121,6 +121,24 @@ class TransposeMultiInfo(ctypes.Structure):
 
 TRANSPOSE_MODES = {None: 0, "scatter": 1, "copy": 2}  # enum spmv_transpose_mode
 
+
+class MultiOpts(ctypes.Structure):
+    """``spmv_multi_opts`` (include/spmv.h); -1 = the library's rule."""
+
+    _fields_ = [("long_len", _c_i32), ("seg_len", _c_i32)]
+
+
+class MultiInfo(ctypes.Structure):
+    """``spmv_multi_info`` (include/spmv.h)."""
+
+    _fields_ = [(k, _c_i32) for k in ("mode", "long_len", "seg_len", "reserved")] + \
+               [(k, _c_i64) for k in ("long_rows", "segments", "slots", "long_entries", "owned_bytes", "t_long_rows",
+                                      "t_segments", "t_owned_bytes")] + \
+               [("kernel", ctypes.c_char * 64)]
+
+
+MULTI_MODES = {None: 0, "balanced": 1}  # enum spmv_multi_mode
+
 _PP = ctypes.POINTER(_vp)
 _PO = ctypes.POINTER(PlanOpts)
 
@@ -135,6 +153,9 @@ HIP_SYMBOLS = {
     "spmv_plan_run": (ctypes.c_int, [_vp, _vp, _vp, _vp]),
     "spmv_plan_run_multi": (ctypes.c_int, [_vp, _c_i32, _vp, _c_i64, _vp, _c_i64, _vp]),
     "spmv_plan_multi_supported": (ctypes.c_int, [_vp]),
+    "spmv_multi_opts_init": (None, [ctypes.POINTER(MultiOpts)]),
+    "spmv_plan_prepare_multi": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.POINTER(MultiOpts)]),
+    "spmv_plan_get_multi_info": (ctypes.c_int, [_vp, ctypes.POINTER(MultiInfo)]),
     "spmv_plan_transpose_supported": (ctypes.c_int, [_vp]),
     "spmv_plan_prepare_transpose": (ctypes.c_int, [_vp, ctypes.c_int]),
     "spmv_plan_get_transpose_info": (ctypes.c_int, [_vp, ctypes.POINTER(TransposeInfo)]),
@@ -298,6 +319,8 @@ HOST_SYMBOLS = {
     "spmv_column_relabel": (_c_i64, [_c_i64, _c_i64, _vp, _vp, _vp, _vp]),
     "spmv_column_relabel_ex": (_c_i64, [_c_i64, _c_i64, _vp, _vp, _vp, _vp, _c_i32]),
     "spmv_csr_tiled_bigplan": (_c_i64, [_c_i64, _vp, _c_i64, _c_i32, _vp]),
+    "spmv_csr_multi_plan": (ctypes.c_int, [_c_i64, _vp, _c_i32, _c_i32, ctypes.POINTER(_c_i64), ctypes.POINTER(_c_i64),
+                                           ctypes.POINTER(_c_i64), _vp, _vp, _vp, _vp, _vp]),
     "spmv_ell_plan": (ctypes.c_int, [_c_i64, _vp, _c_i32, ctypes.POINTER(_c_i32), ctypes.POINTER(_c_i64)]),
     "spmv_ell_fill": (ctypes.c_int, [_c_i64, _vp, _vp, _vp, _c_i32, _c_i64, _c_i32, _vp, _vp]),
     "spmv_sell_plan": (ctypes.c_int, [_c_i64, _vp, _c_i32, _c_i32, _c_i32, ctypes.POINTER(_c_i64), ctypes.POINTER(_c_i64)]),
@@ -630,6 +653,32 @@ def csr_tiled_bigplan(n_rows: int, ptr: np.ndarray, nnz: int, cap: int = TILED_R
     host_lib().spmv_csr_tiled_bigplan(n_rows, _ptr(ptr), tile, cap, _ptr(plan))
     tiles = (nnz + tile - 1) // tile
     return plan if tiles > 0 and np.any(plan[:tiles] >= 0) else None
+
+
+def csr_multi_plan(n_rows: int, ptr: np.ndarray, long_len: int, seg_len: int, counts_only: bool = False) -> dict:
+    """spmv_csr_multi_plan: the long-row plan of the balanced multi-vector
+    run -> {"n_long", "n_seg", "n_slots"} and, unless counts_only, the tables
+    seg_beg[n_seg] (int64), seg_cnt / seg_dest[n_seg], long_row /
+    long_first[n_long + 1] (int32)."""
+    ptr = np.ascontiguousarray(ptr, dtype=np.int64)
+    if ptr.size != n_rows + 1:
+        raise SpmvError(OTHER_ERROR, "csr_multi_plan", "row_ptr must hold n_rows + 1 offsets")
+    f = host_lib().spmv_csr_multi_plan
+    nl, ns, nsl = _c_i64(0), _c_i64(0), _c_i64(0)
+    refs = (ctypes.byref(nl), ctypes.byref(ns), ctypes.byref(nsl))
+    _check_host(f(n_rows, ptr.ctypes.data, long_len, seg_len, *refs, None, None, None, None, None), "csr_multi_plan")
+    out = {"n_long": nl.value, "n_seg": ns.value, "n_slots": nsl.value}
+    if counts_only:
+        return out
+    t = {"seg_beg": np.empty(max(ns.value, 1), np.int64), "seg_cnt": np.empty(max(ns.value, 1), np.int32),
+         "seg_dest": np.empty(max(ns.value, 1), np.int32), "long_row": np.empty(nl.value + 1, np.int32),
+         "long_first": np.empty(nl.value + 1, np.int32)}
+    _check_host(f(n_rows, ptr.ctypes.data, long_len, seg_len, *refs, *(a.ctypes.data for a in t.values())),
+                "csr_multi_plan")
+    assert (nl.value, ns.value, nsl.value) == (out["n_long"], out["n_seg"], out["n_slots"])
+    for k in ("seg_beg", "seg_cnt", "seg_dest"):
+        t[k] = t[k][: ns.value]
+    return {**out, **t}
 
 
 def relabel_columns(m: Coo):
@@ -977,6 +1026,32 @@ class DeviceMatrix:
         st = stream if stream is not None else torch.cuda.current_stream(here)
         _check(hip_lib().spmv_plan_run_multi(self.plan, k, _ptr(X), ldx, _ptr(Y), ldy, st.cuda_stream),
                f"spmv_plan_run_multi ({self.fmt})")
+
+    def prepare_multi(self, mode="balanced", long_len=None, seg_len=None) -> None:
+        """The balanced mode of run_multi (and of run_t_multi in copy mode) for
+        CSR matrices with long rows (spmv_plan_prepare_multi, build time):
+        rows of more than long_len entries are cut into segments of seg_len
+        entries with 16 entry lanes each; None = the library's rule.
+        mode None frees everything: the unprepared run again."""
+        if not isinstance(mode, (str, type(None))) or mode not in MULTI_MODES:
+            raise SpmvError(OTHER_ERROR, "prepare_multi", 'mode must be "balanced" or None')
+        if self.plan is None:
+            raise SpmvError(OTHER_ERROR, "prepare_multi", f"format {self.fmt} has no plan: no multi-vector run")
+        o = MultiOpts(-1 if long_len is None else int(long_len), -1 if seg_len is None else int(seg_len))
+        _check(hip_lib().spmv_plan_prepare_multi(self.plan, MULTI_MODES[mode], ctypes.byref(o)),
+               f"spmv_plan_prepare_multi ({self.fmt})")
+
+    @property
+    def multi_info(self) -> dict:
+        """spmv_multi_info as a dict; mode is None or "balanced"."""
+        if self.plan is None:
+            raise SpmvError(OTHER_ERROR, "multi_info", f"format {self.fmt} has no plan")
+        info = MultiInfo()
+        _check(hip_lib().spmv_plan_get_multi_info(self.plan, ctypes.byref(info)), "spmv_plan_get_multi_info")
+        out = {k: int(getattr(info, k)) for k, _ in MultiInfo._fields_ if k not in ("mode", "reserved", "kernel")}
+        out["mode"] = {v: k for k, v in MULTI_MODES.items()}[info.mode]
+        out["kernel"] = info.kernel.decode()
+        return out
 
     @property
     def transpose_supported(self) -> bool:

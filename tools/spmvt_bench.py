@@ -32,6 +32,10 @@ the k calls back to back, as a caller would issue them (on a matrix that
 fits the Infinity Cache the second to k-th call find it there).  One JSON
 line (per matrix, mode and k: both times with their spreads, `speedup` =
 k calls / one call, the byte-model GB/s of the one call) and a table on stderr.
+With --balanced the copy mode is also timed after prepare_multi("balanced",
+--long-len, --seg-len), which extends to the inner plan over A^T:
+`balanced_ms`, `balanced_vs_multi` = unprepared / balanced and
+`balanced_vs_k_calls` = k calls / balanced, in one more table.
 """
 from __future__ import annotations
 
@@ -124,6 +128,16 @@ def vectors_leg(torch, dev, flush, a):
                     "k_calls_spread_ms": round(s_spread, 5), "speedup": round(single / multi, 3),
                     "gbs_alg": round(sa.bytes_alg_multi(m.n_cols, m.n_rows, m.nnz, k) / (multi * 1e-3) / 1e9, 1),
                     "max_abs_diff_vs_cpu": err}
+                if a.balanced and mode == "copy":
+                    dm.prepare_multi("balanced", a.long_len, a.seg_len)
+                    r[mode]["balanced_info"] = dm.multi_info
+                    bal, b_spread = cold_ms(torch, flush, lambda: dm.run_t_multi(X, Y), a.steps, a.reps)
+                    torch.cuda.synchronize()
+                    r[mode][f"k{k}"].update({
+                        "balanced_ms": round(bal, 5), "balanced_spread_ms": round(b_spread, 5),
+                        "balanced_vs_multi": round(multi / bal, 3), "balanced_vs_k_calls": round(single / bal, 3),
+                        "balanced_max_abs_diff_vs_cpu": float(np.max(np.abs(Y.cpu().numpy() - Yr)))})
+                    dm.prepare_multi(None)
                 del X, Y, xs, ys
         dm.prepare_transpose(None)
         out["results"][name] = r
@@ -140,6 +154,14 @@ def vectors_leg(torch, dev, flush, a):
                 print(f"| {name} | {mode} | {k} | {c['multi_ms']:.4f} ({c['multi_spread_ms']:.4f}) | "
                       f"{c['k_calls_ms']:.4f} ({c['k_calls_spread_ms']:.4f}) | {c['speedup']:.2f} | {c['gbs_alg']:.0f} |",
                       file=e)
+    if a.balanced:
+        print("\n| matrix | k | balanced run_t_multi ms (spread) | unprepared / balanced | k run_t / balanced |", file=e)
+        print("|---|---|---|---|---|", file=e)
+        for name, r in out["results"].items():
+            for k in ks:
+                c = r["copy"][f"k{k}"]
+                print(f"| {name} | {k} | {c['balanced_ms']:.4f} ({c['balanced_spread_ms']:.4f}) | "
+                      f"{c['balanced_vs_multi']:.2f} | {c['balanced_vs_k_calls']:.2f} |", file=e)
 
 
 def main():
@@ -149,6 +171,10 @@ def main():
     ap.add_argument("--reps", type=int, default=5, help="timed regions per figure (their median is reported)")
     ap.add_argument("--vectors", default=None, metavar="K[,K...]",
                     help="the multi-vector leg instead: one run_t_multi against k run_t calls (e.g. 2,4,8)")
+    ap.add_argument("--balanced", action="store_true",
+                    help="--vectors: also time copy mode after prepare_multi(\"balanced\")")
+    ap.add_argument("--long-len", type=int, default=None, help="--balanced: long_len (default: the library's rule)")
+    ap.add_argument("--seg-len", type=int, default=None, help="--balanced: seg_len (default: the library's rule)")
     a = ap.parse_args()
     import torch
 
