@@ -82,7 +82,11 @@ typedef struct spmv_dims {
  *              slot groups; -1 default (on), 0 off
  *   index16    SELL: 1 = SELL16, 16-bit column offsets from each
  *              workgroup's window base (plan-owned copy; C = 64, refused
- *              when a window spans more than 65,536 columns)
+ *              when a window spans more than 65,536 columns).  CSR
+ *              ignores it: an x-window CSR plan builds its 16-bit
+ *              window-relative column copy by the library's rule
+ *              (SPMV_OPT_CSR_COL16, spmv_ext.h) wherever every window with
+ *              entries fits the LDS cap, and spmv_plan_info.index16 says so
  *   coo_pass   COO: -1 the single pass wherever every row ends within 80
  *              entries past its tile, else the carry pass; 0 carry pass;
  *              1 single pass or SPMV_OTHER_ERROR
@@ -129,14 +133,14 @@ typedef struct spmv_plan_info {
     int32_t xwin;        /* x windows built */
     int32_t head;        /* SELL head copy built */
     int32_t single_pass; /* COO without the carry kernel */
-    int32_t index16;     /* SELL16 */
+    int32_t index16;     /* SELL16; CSR: the plan streams its own 16-bit window column offsets */
     int32_t split_T;     /* SELL split width (0: none) */
     int32_t reserved;
     int64_t n_chunks;    /* SELL split chunks */
     int64_t big_tiles;   /* tiled CSR tiles with a listed row plan */
     int64_t head_bytes;
     int64_t ws_bytes;
-    int64_t owned_bytes; /* device bytes the plan allocated */
+    int64_t owned_bytes; /* device bytes the plan allocated (index16 copies included: 2 per entry) */
     int64_t H;
     char kernel[64];
     char desc[320];

@@ -69,6 +69,9 @@ bool xcd_remap_enabled();
 bool xwin_remap(bool dflt);
 // CSR x-window kernel: the first chunk prefetched in the prologue (MODE 4)
 bool csr_prefetch(bool dflt);
+// CSR x-window plans: the plan-owned 16-bit window-relative column copy
+// (read at plan creation)
+bool csr_col16(bool dflt);
 // small-matrix SELL geometry (sell.hip): C = 64 and fewer than 14 slices per CU
 bool sell_small(int32_t C, int64_t n_slices);
 
@@ -93,6 +96,18 @@ int64_t coo_tail_cap();
 // run, the widest window of at most `cap` entries.  `who` = the entry point.
 int windows_download(const void *win, int64_t n, hipStream_t st, int2 **host, const char *who);
 int windows_xcap(const void *win, int64_t n, int32_t cap, hipStream_t st, int32_t *xcap, const char *who);
+// The window-relative 16-bit column copy of a CSR x-window plan (csr.hip):
+// its size for nnz entries; whether it applies (nnz >= 2 and every window
+// with entries spans at most xcap columns; one synchronising copy); its
+// build on d.stream (not synchronised); the x-window run that reads it.
+size_t csr_col16_bytes(int64_t nnz);
+int csr_col16_fits(const spmv_dims &d, int lanes_per_row, int32_t rows_per_window, const void *win, int32_t xcap,
+                   bool *fits);
+int csr_col16_fill(const spmv_dims &d, const int64_t *row_ptr, const int32_t *col, int lanes_per_row,
+                   int32_t rows_per_window, const void *win, uint16_t *off);
+int csr_run_xwin_col16(spmv_dims d, const int64_t *row_ptr, const uint16_t *off, const double *val,
+                       const double *x, double *y, int lanes_per_row, int32_t rows_per_window, const void *win,
+                       int32_t xcap);
 // LDS entries of x a staged COO tile / CMRS strip run may stage (16 KiB)
 constexpr int32_t kStagedXwinCap = 2048;
 int64_t coo_staged_tile();

@@ -124,8 +124,11 @@ constexpr bool kCsrXwinNtDefault = true;
 // load depends on another), decode(raw, p) turns them into the column pair
 // (CSR16's escaped blocks load their int32 columns there, a second round
 // trip for those blocks only).
+// kWindowRelative: the source yields offsets into the running x window, not
+// columns (ColWin16 below); the x-window kernel then gathers with XWindowRel.
 template <bool NT>
 struct Col32 {
+    static constexpr bool kWindowRelative = false;
     const int32_t *__restrict__ col;
     using Raw = int2;
     __device__ __forceinline__ int2 pair(int64_t p) const { return stream_load2<NT>(col + p); }
@@ -136,6 +139,7 @@ struct Col32 {
 
 template <bool NT>
 struct Col16 {
+    static constexpr bool kWindowRelative = false;
     const int32_t *__restrict__ base;
     const uint16_t *__restrict__ off;
     const int32_t *__restrict__ esc;
@@ -167,6 +171,47 @@ struct Col16 {
         if (r.b >= 0)
             return int2{r.b + (int32_t)(r.w & 0xffffu), r.b + (int32_t)(r.w >> 16)};
         return stream_load2<NT>(esc + (int64_t)(-1 - r.b) * 64 + (p & 63));
+    }
+};
+
+// ColWin16 = the plan-owned window-relative copy (csr_col16_kernel, built
+// once per plan): off[p] = col[p] - win[w].x for the x window w that holds
+// entry p's row, so an offset indexes the LDS window directly.  10 bytes per
+// entry, no base array, no escapes and no subtraction in the run; a plan has
+// the copy only when every window with entries fits the LDS cap.  The values
+// gathered for the summed entries are exactly Col32's, hence the same bits.
+template <bool NT>
+struct ColWin16 {
+    static constexpr bool kWindowRelative = true;
+    const uint16_t *__restrict__ off;
+    using Raw = uint32_t;
+    // p even: one aligned 4-byte word holds the offsets of entries p, p+1
+    __device__ __forceinline__ Raw raw(int64_t p) const
+    {
+        return stream_load<NT>(reinterpret_cast<const uint32_t *>(off + p));
+    }
+    __device__ __forceinline__ int2 decode(Raw w, int64_t) const
+    {
+        return int2{(int32_t)(w & 0xffffu), (int32_t)(w >> 16)};
+    }
+    __device__ __forceinline__ int2 pair(int64_t p) const { return decode(raw(p), p); }
+    __device__ __forceinline__ int32_t one(int64_t p) const { return (int32_t)stream_load<NT>(off + p); }
+};
+
+// x source of ColWin16: s[o] for an offset o of the running window, no base
+// subtraction.  A window also LOADS entries of its neighbours (the lead-in
+// entries before its first chunk, the partner of a pair that straddles its
+// range end, the spare pair); those are never summed, but their offsets are
+// relative to another window's base and may be anything in [0, 65535], so
+// every gather is bounded to the window's last entry, hi = span - 1
+// (unsigned: o >= 0).
+struct XWindowRel {
+    const double *s;  // LDS
+    uint32_t hi;
+    __device__ __forceinline__ double operator()(int32_t o) const
+    {
+        const uint32_t u = (uint32_t)o;
+        return s[u < hi ? u : hi];
     }
 };
 
@@ -453,6 +498,29 @@ __global__ __launch_bounds__(kBlock) void csr_window_kernel(int64_t n_rows, int6
         win[g] = r;
 }
 
+// The window-relative 16-bit column copy (ColWin16) of a plan whose windows
+// all fit the LDS cap: off[e] = col[e] - win[w].x for the entries e of window
+// w's rows (win[w].x is at most every column the window loads, its own
+// entries included, and the window spans at most 2,048 columns, so the
+// difference fits 11 bits).  Two zero entries pad the array's end.  One pass
+// over row_ptr, col and win, build time.
+__global__ __launch_bounds__(kBlock) void csr_col16_kernel(int64_t n_rows, int64_t nnz, int64_t rpb,
+                                                           const int64_t *__restrict__ row_ptr,
+                                                           const int32_t *__restrict__ col,
+                                                           const int2 *__restrict__ win,
+                                                           uint16_t *__restrict__ off)
+{
+    const int64_t g = blockIdx.x;
+    const int64_t r1 = (g + 1) * rpb < n_rows ? (g + 1) * rpb : n_rows;
+    const int64_t b = row_ptr[g * rpb];
+    const int64_t e = row_ptr[r1] < nnz ? row_ptr[r1] : nnz;  // off holds nnz + 2 entries
+    const int32_t lo = win[g].x;
+    for (int64_t p = b + threadIdx.x; p < e; p += kBlock)
+        off[p] = (uint16_t)(col[p] - lo);
+    if (g == 0 && threadIdx.x < 2)
+        off[nnz + threadIdx.x] = 0;
+}
+
 // The staged kernel with x windows in LDS.  A window covers gpw consecutive
 // row groups (rows_per_window = gpw * 256/L rows), one workgroup per window:
 // the workgroup copies x[win.x .. win.y] into LDS (dynamic, xcap entries)
@@ -589,7 +657,14 @@ __global__ __launch_bounds__(kBlock) void csr_xwin_kernel(
         }
         __syncthreads();  // window and offsets visible
         CSR_STAMP(1);
-        if (staged)
+        // window-relative columns: every window with entries is staged (the
+        // plan's rule); a window without entries sums nothing and its
+        // never-summed gathers read s_x[0] (xcap >= 1)
+        if constexpr (Cols::kWindowRelative)
+            staged_window_pipelined<L, R, NT, XWindowRel, V, Cols>(r0, (int)(g_end - g_beg), s_off, s_prod, cols,
+                                                                  val, XWindowRel{s_x, staged ? (uint32_t)span - 1 : 0u},
+                                                                  y, n_rows, nz, st, pre);
+        else if (staged)
             staged_window_pipelined<L, R, NT, XWindow, V, Cols>(r0, (int)(g_end - g_beg), s_off, s_prod, cols, val,
                                                                XWindow{s_x, wnd.x}, y, n_rows, nz, st, pre);
         else
@@ -607,7 +682,10 @@ __global__ __launch_bounds__(kBlock) void csr_xwin_kernel(
         }
         __syncthreads();  // offsets (and, for the first group, the window) visible
         const int64_t row = grp * RPB + threadIdx.x / L;
-        if (staged)
+        if constexpr (Cols::kWindowRelative)
+            staged_group<L, R, NT, Cols, XWindowRel, V>(row, s_ptr, s_prod, cols, val,
+                                                        XWindowRel{s_x, staged ? (uint32_t)span - 1 : 0u}, y, n_rows);
+        else if (staged)
             staged_group<L, R, NT, Cols, XWindow, V>(row, s_ptr, s_prod, cols, val, XWindow{s_x, wnd.x}, y, n_rows);
         else
             staged_group<L, R, NT, Cols, XGlobal, V>(row, s_ptr, s_prod, cols, val, XGlobal{x}, y, n_rows);
@@ -898,6 +976,12 @@ struct MakeCol16 {
     Col16<NT> get() const { return Col16<NT>{base, off, esc}; }
 };
 
+struct MakeColWin16 {
+    const uint16_t *off;
+    template <bool NT>
+    ColWin16<NT> get() const { return ColWin16<NT>{off}; }
+};
+
 // One launcher per column source / value type: L as asked, R (3 or 4) and the
 // load policy from the rules above.
 template <typename V, typename MakeCols>
@@ -996,6 +1080,71 @@ extern "C" int spmv_csr_run_xwin(spmv_dims d, const int64_t *row_ptr, const int3
     if (rc != SPMV_SUCCESS)
         return rc;
     SPMV_CHECK_LAUNCH("csr_xwin_kernel");
+    return SPMV_SUCCESS;
+}
+
+// ---- the plan's window-relative 16-bit column copy (ColWin16; plan.hip)
+size_t spmv::csr_col16_bytes(int64_t nnz)
+{
+    return ((size_t)2 * (size_t)(nnz + 2) + 3) & ~(size_t)3;
+}
+
+// *fits = every window with entries spans at most xcap columns (a window
+// without entries is {0, -1}); one synchronising copy of the window table
+int spmv::csr_col16_fits(const spmv_dims &d, int lanes_per_row, int32_t rows_per_window, const void *win,
+                         int32_t xcap, bool *fits)
+{
+    *fits = false;
+    const int64_t n_win = (int64_t)(spmv_csr_xwin_bytes(d.n_rows, d.nnz, lanes_per_row, rows_per_window) / sizeof(int2));
+    if (d.nnz < 2 || n_win <= 0 || !win || xcap < 1 || xcap > kCsrXwinCap)
+        return SPMV_SUCCESS;
+    int2 *h = nullptr;
+    const int rc = windows_download(win, n_win, (hipStream_t)d.stream, &h, "spmv_plan_csr");
+    if (rc != SPMV_SUCCESS)
+        return rc;
+    bool ok = true;
+    for (int64_t w = 0; w < n_win && ok; ++w) {
+        const int64_t span = (int64_t)h[w].y - h[w].x + 1;
+        ok = span == 0 || (span > 0 && span <= xcap);
+    }
+    free(h);
+    *fits = ok;
+    return SPMV_SUCCESS;
+}
+
+// fills off (csr_col16_bytes(d.nnz) bytes) on d.stream; not synchronised
+int spmv::csr_col16_fill(const spmv_dims &d, const int64_t *row_ptr, const int32_t *col, int lanes_per_row,
+                         int32_t rows_per_window, const void *win, uint16_t *off)
+{
+    const int L = lanes_per_row > 0 ? lanes_per_row : spmv_csr_auto_lanes(d.n_rows, d.nnz);
+    if (!lanes_ok(L) || d.n_rows <= 0 || !win || !off)
+        return fail_msg(SPMV_OTHER_ERROR, "spmv_plan_csr: 16-bit column copy: bad arguments");
+    const int64_t rpw = csr_xwin_gpw(L, rows_per_window, d.n_rows) * (kBlock / L);
+    const int64_t n_win = (d.n_rows + rpw - 1) / rpw;
+    hipLaunchKernelGGL(csr_col16_kernel, dim3((unsigned)n_win), dim3(kBlock), 0, (hipStream_t)d.stream, d.n_rows,
+                       d.nnz, rpw, row_ptr, col, (const int2 *)win, off);
+    SPMV_CHECK_LAUNCH("csr_col16_kernel");
+    return SPMV_SUCCESS;
+}
+
+// spmv_csr_run_xwin with the columns read from the plan's copy: the same
+// kernel, load schedule, chunks and sums, hence the same bits
+int spmv::csr_run_xwin_col16(spmv_dims d, const int64_t *row_ptr, const uint16_t *off, const double *val,
+                             const double *x, double *y, int lanes_per_row, int32_t rows_per_window,
+                             const void *win, int32_t xcap)
+{
+    int L = 0;
+    int64_t gpw = 0;
+    int rc = xwin_args(d, rows_per_window, win, xcap, lanes_per_row, &L, &gpw, "spmv_plan_run");
+    if (rc != SPMV_SUCCESS || d.n_rows == 0)
+        return rc;
+    if (!off || xcap < 1 || d.nnz < 2)
+        return fail_msg(SPMV_OTHER_ERROR, "spmv_plan_run: corrupt 16-bit column copy");
+    SPMV_GUARD(d);
+    rc = launch_xwin_any(d, L, row_ptr, MakeColWin16{off}, val, x, y, (const int2 *)win, xcap, gpw);
+    if (rc != SPMV_SUCCESS)
+        return rc;
+    SPMV_CHECK_LAUNCH("csr_xwin_kernel (16-bit window offsets)");
     return SPMV_SUCCESS;
 }
 

@@ -32,7 +32,8 @@ struct spmv_plan {
     bool tiles_planned = false;  // tiled CMRS: the tile -> first-strip table filled at build
     int64_t n_chunks = 0;
     int32_t *chunk_slice = nullptr, *chunk_k0 = nullptr;
-    uint16_t *col16 = nullptr;
+    uint16_t *col16 = nullptr;  // SELL16: offsets from each workgroup's window base
+    uint16_t *cwin16 = nullptr;  // CSR x windows: col[e] - (the base of e's window), or NULL
     int32_t *hcol = nullptr;  // the columns with hot ids (plan-owned), or NULL
     int32_t *hot = nullptr;   // hot[H]: the hot columns in rank order
     int64_t H = 0;

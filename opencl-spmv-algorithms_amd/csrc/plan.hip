@@ -49,6 +49,13 @@ enum PlanPath {
     P_CMRS_TILED,
 };
 
+// CSR x-window plans build the 16-bit window-relative column copy by default
+// (SPMV_OPT_CSR_COL16 = -1): one cant-like matrix cold, the int32-column
+// library and this one interleaved on one box, 12.24 vs 10.86 us in-process
+// (three runs each, spreads 0.08 and 0.21 us), 11.63 vs 10.12 us by the
+// kernel trace (profiles/round7/ab_csr_col16.md).
+constexpr bool kCsrCol16Rule = true;
+
 // Largest difference of consecutive offsets off[1..n] - off[0..n-1] (a row
 // or strip length), per workgroup (the host takes the max of the
 // workgroups'): the skew rules of the CSR and CMRS plans, computed where
@@ -272,7 +279,7 @@ int spmv_plan_destroy(spmv_plan *p)
     if (!p)
         return SPMV_SUCCESS;
     void *owned[] = {p->win,    p->head,        p->tails,    p->ws,    p->own_lo, p->big,
-                     p->chunk_slice, p->chunk_k0, p->col16, p->hcol, p->hot};
+                     p->chunk_slice, p->chunk_k0, p->col16, p->cwin16, p->hcol, p->hot};
     int dev = -1;
     (void)hipGetDevice(&dev);
     if (dev != p->d.device)
@@ -445,9 +452,25 @@ int spmv_plan_csr(spmv_dims d, const int64_t *row_ptr, const int32_t *col, const
         const size_t wb = spmv_csr_xwin_bytes(d.n_rows, d.nnz, p->lanes, p->xwin_rows);
         if ((rc = plan_alloc(p, &p->win, wb)) == SPMV_SUCCESS)
             rc = spmv_csr_xwin_build(d, row_ptr, col, p->lanes, p->xwin_rows, p->win, wb, &p->xcap);
+        // The columns as 16-bit offsets from each window's base (plan-owned,
+        // 10 instead of 12 bytes per entry, same bits) wherever every window
+        // with entries fits the LDS cap; the caller's col stays the source of
+        // the multi-vector, transposed and balanced runs.
+        // SPMV_OPT_CSR_COL16, the rule: kCsrCol16Rule
+        // (profiles/round7/ab_csr_col16.md).
+        bool c16 = false;
+        if (rc == SPMV_SUCCESS && csr_col16(kCsrCol16Rule))
+            rc = csr_col16_fits(d, p->lanes, p->xwin_rows, p->win, p->xcap, &c16);
+        if (rc == SPMV_SUCCESS && c16 &&
+            (rc = plan_alloc(p, (void **)&p->cwin16, csr_col16_bytes(d.nnz))) == SPMV_SUCCESS &&
+            (rc = csr_col16_fill(d, row_ptr, col, p->lanes, p->xwin_rows, p->win, p->cwin16)) == SPMV_SUCCESS &&
+            // runs may come on any stream: the copy is complete when the plan is returned
+            hipStreamSynchronize((hipStream_t)d.stream) != hipSuccess)
+            rc = fail_msg(SPMV_PROGRAM_ERROR, "spmv_plan_csr: 16-bit column copy");
         snprintf(p->kernel, sizeof p->kernel, "csr_xwin_kernel");
-        snprintf(p->desc, sizeof p->desc, "CSR-vector: %d lanes per row, x windows of %d rows in LDS (xcap %d)",
-                 p->lanes, p->xwin_rows > 0 ? p->xwin_rows : 128, p->xcap);
+        snprintf(p->desc, sizeof p->desc, "CSR-vector: %d lanes per row, x windows of %d rows in LDS (xcap %d)%s",
+                 p->lanes, p->xwin_rows > 0 ? p->xwin_rows : 128, p->xcap,
+                 p->cwin16 ? ", 16-bit window column offsets (plan-owned)" : "");
         return finish(p, rc, out);
     }
     p->path = P_CSR_VARIANT;
@@ -741,6 +764,8 @@ int spmv_plan_run(const spmv_plan *p, const double *x, double *y, void *stream)
     case P_CSR_VARIANT:
         return spmv_csr_run_variant(d, p->ptr, p->col, p->val, x, y, p->lanes, p->variant);
     case P_CSR_XWIN:
+        if (p->cwin16)
+            return csr_run_xwin_col16(d, p->ptr, p->cwin16, p->val, x, y, p->lanes, p->xwin_rows, p->win, p->xcap);
         return spmv_csr_run_xwin(d, p->ptr, p->col, p->val, x, y, p->lanes, p->xwin_rows, p->win, p->xcap);
     case P_CSR_TILED:
         if (p->big)
@@ -1016,7 +1041,7 @@ int spmv_plan_get_info(const spmv_plan *p, spmv_plan_info *info)
     info->xwin = p->win != nullptr;
     info->head = p->head != nullptr;
     info->single_pass = p->path == P_COO_TAIL;
-    info->index16 = p->path == P_SELL16;
+    info->index16 = p->path == P_SELL16 || p->cwin16 != nullptr;
     info->split_T = p->split_T;
     info->n_chunks = p->n_chunks;
     info->big_tiles = p->big_tiles;

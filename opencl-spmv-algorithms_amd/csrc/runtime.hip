@@ -63,6 +63,7 @@ static std::atomic<int> g_opt_xwin_remap{env_switch("SPMV_XWIN_REMAP")};
 static std::atomic<int> g_opt_xcd_remap{env_switch("SPMV_XCD_REMAP")};
 static std::atomic<int> g_opt_stream_nt{env_switch("SPMV_STREAM_NT")};
 static std::atomic<int> g_opt_csr_prefetch{env_switch("SPMV_CSR_PREFETCH")};
+static std::atomic<int> g_opt_csr_col16{env_switch("SPMV_CSR_COL16")};
 
 static std::atomic<int> *option_slot(int option)
 {
@@ -75,6 +76,8 @@ static std::atomic<int> *option_slot(int option)
         return &g_opt_stream_nt;
     case SPMV_OPT_CSR_PREFETCH:
         return &g_opt_csr_prefetch;
+    case SPMV_OPT_CSR_COL16:
+        return &g_opt_csr_col16;
     default:
         return nullptr;
     }
@@ -94,6 +97,12 @@ bool xcd_remap_enabled() { return g_opt_xcd_remap.load(std::memory_order_relaxed
 bool csr_prefetch(bool dflt)
 {
     const int v = g_opt_csr_prefetch.load(std::memory_order_relaxed);
+    return v < 0 ? dflt : v == 1;
+}
+
+bool csr_col16(bool dflt)
+{
+    const int v = g_opt_csr_col16.load(std::memory_order_relaxed);
     return v < 0 ? dflt : v == 1;
 }
 
