@@ -416,6 +416,101 @@ typedef struct spmv_transpose_multi_info {
     char kernel[64];       /* dominant kernel; copy: the inner plan's multi-vector kernel */
 } spmv_transpose_multi_info;
 int spmv_plan_get_transpose_multi_info(const spmv_plan *p, spmv_transpose_multi_info *info);
+/* The symmetric product y = (S + S^T - diag S) x on a plan over the STORED
+ * HALF S of a symmetric matrix (Matrix Market `symmetric` files list one
+ * triangle: SuiteSparse cant.mtx lists 2,034,917 of its 4,007,383 entries).
+ * S is square, n x n, of any pattern (lower, upper or mixed); every stored
+ * off-diagonal entry (i, j, v) also stands for (j, i, v), diagonal entries
+ * count once, duplicates and entries stored on both sides each count as
+ * listed: A = the expansion spmv_coo_symmetrize (spmv_host.h) writes.
+ * Skew-symmetric (mirror -v) and hermitian complex meanings are out of scope:
+ * the reader's `symmetric` flag does not tell the banners apart.
+ * CSR plans only (every path), x[n], y[n]; two modes, built by
+ * spmv_plan_prepare_symmetric:
+ *   SPMV_S_FUSED   one pass over the half storage (12 bytes per stored
+ *       entry), no second copy.  One workgroup per block of 128 rows streams
+ *       the block's entries once.  The plan records, per block, the union
+ *       window {lo, hi} of the block's column range and its own rows: 8 bytes
+ *       per block, owned_bytes == 8 * ceil(n / 128) exactly.  A union of at
+ *       most `cap` (2,048) columns: x[lo..hi] and an accumulator of the same
+ *       span live in LDS, entry (r, c, v) adds v x[c] to acc[r - lo] and,
+ *       when c != r, v x[r] to acc[c - lo] (the row products of a wave's 64
+ *       consecutive entries are summed per row across the wave and added
+ *       once per run, measured faster); the accumulator is added to the
+ *       zeroed y with one fp64 atomic per touched entry, consecutive lanes on
+ *       consecutive columns.  A wider union: a 128-entry LDS accumulator for
+ *       the rows' sums, x[c] gathered from global memory, every mirrored
+ *       product added straight into y with a global fp64 atomic.  Every
+ *       destination is bounds-checked (against the window or n).  A run is a
+ *       memset of y plus one kernel.  Results are NOT bitwise reproducible
+ *       from run to run (the atomics arrive in any order); y must be ordinary
+ *       device memory (hipMalloc, torch), as for SPMV_T_SCATTER.
+ *       flush_entries counts the y entries the flushes address per run: the
+ *       window blocks' spans plus the rows of the wide blocks.
+ *   SPMV_S_EXPAND  A built once on the device as CSR: the symmetrized COO of
+ *       the plan's CSR entries in spmv_coo_symmetrize's order, then
+ *       spmv_dev_csr_from_coo (spmv_ext.h), element for element
+ *       spmv_csr_from_coo of spmv_coo_symmetrize of the CSR-ordered entries;
+ *       run by an inner forward CSR plan with default options.  Bitwise
+ *       reproducible: the bits of a default forward CSR plan over those
+ *       arrays.  Owned bytes: 12 nnz_A + 8 (n + 1) plus the inner plan's own;
+ *       the transient buffers are freed before prepare returns.
+ * spmv_plan_prepare_symmetric (build time) runs on the plan's d.stream and
+ * synchronises it before returning, so runs may come on any stream.
+ * Preparing the mode the plan already has is a no-op; preparing the other
+ * mode frees the first mode's buffers (after the new ones are built);
+ * SPMV_S_NONE frees everything; spmv_plan_destroy frees whatever was built.
+ * On failure the plan is left as it was.  SPMV_OTHER_ERROR with a message:
+ * NULL plan, unknown mode, a plan that is not CSR, a matrix that is not
+ * square, (expand) a column outside [0, n).  It is independent of
+ * spmv_plan_prepare_transpose and spmv_plan_prepare_multi: the three keep
+ * separate buffers and separate byte reports, and spmv_plan_get_info is
+ * unchanged.
+ * spmv_plan_run_sym follows the run conventions: asynchronous on `stream`,
+ * no allocation and no synchronisation (it can be captured into a graph on
+ * one stream), codes of spmv_rc.h.
+ *   - y[0 .. n) is FULLY overwritten (rows and columns without entries get
+ *     0.0); NO byte of y at or past n is written.
+ *   - NO value outside x[0 .. n) enters a result; x and y need 8-byte
+ *     alignment only.
+ *   - x and y must not overlap; runs of one plan must be serialised.
+ *   - Reads the caller's row_ptr, col and val, never the plan's
+ *     hot-renumbered column copy.
+ *   - SPMV_OTHER_ERROR with a message, before any device work: NULL plan, a
+ *     plan that was not prepared, NULL x or y with n > 0.
+ * Which to call (MI355X, cold, profiles/symmetric/README.md; the yardstick is
+ * the forward run of a default CSR plan over the host-expanded matrix): on the
+ * cant-like lower triangle (2,034,917 stored entries of 4,007,383) the yardstick
+ * took 0.0107 ms, SPMV_S_EXPAND 0.0108 ms (1.01 x) and SPMV_S_FUSED 0.0259 ms
+ * (2.42 x); on the 32-copy batch 0.2161, 0.2211 (1.02 x) and 0.3019 ms (1.40 x).
+ * FUSED is SLOWER than the expanded forward run at both sizes although it
+ * streams half the bytes (25.7 against 49.3 MB): call it for memory (3,904
+ * plan-owned bytes against 56.6 MB on one matrix, 125 KB against 1.81 GB on
+ * the batch) or when the matrix changes too often for A to be rebuilt, and
+ * SPMV_S_EXPAND wherever A fits beside the stored half.  Not measured:
+ * matrices on the wide path (power-law columns: every mirrored product is a
+ * scattered global atomic there), build times, upper-triangle storage.       */
+enum spmv_symmetric_mode { SPMV_S_NONE = 0, SPMV_S_FUSED = 1, SPMV_S_EXPAND = 2 };
+typedef struct spmv_symmetric_info {
+    int32_t mode;          /* enum spmv_symmetric_mode */
+    int32_t cap;           /* fused: widest union window (columns) summed in LDS */
+    int64_t blocks;        /* fused: row blocks */
+    int64_t window_blocks; /* fused: row blocks whose union window fits cap */
+    int64_t flush_entries; /* fused: y entries addressed by the flushes per run */
+    int64_t nnz_expanded;  /* expand: entries of A */
+    int64_t owned_bytes;   /* device bytes the symmetric path allocated */
+    char kernel[64];       /* dominant kernel, as spmv_plan_info.kernel */
+} spmv_symmetric_info;
+/* 1: CSR plans with n_rows == n_cols; 0 otherwise and for NULL */
+int spmv_plan_symmetric_supported(const spmv_plan *p);
+int spmv_plan_prepare_symmetric(spmv_plan *p, int mode);
+int spmv_plan_get_symmetric_info(const spmv_plan *p, spmv_symmetric_info *info);
+int spmv_plan_run_sym(const spmv_plan *p, const double *x, double *y, void *stream);
+/* SPMV_S_EXPAND only: the plan-owned CSR of A on the device, row_ptr[n + 1],
+ * col / val[*nnz]; valid until the mode changes or the plan is destroyed.
+ * SPMV_OTHER_ERROR for a NULL argument or a plan in another mode.          */
+int spmv_plan_get_symmetric_arrays(const spmv_plan *p, const int64_t **row_ptr, const int32_t **col,
+                                   const double **val, int64_t *nnz);
 int spmv_plan_get_info(const spmv_plan *p, spmv_plan_info *info);
 /* Frees what the plan allocated (never the caller's arrays). */
 int spmv_plan_destroy(spmv_plan *p);

@@ -83,6 +83,22 @@ int spmv_csr_from_coo(int64_t n_rows, int64_t nnz, const int32_t *row,
 int spmv_csr_transpose(int64_t n_rows, int64_t n_cols, const int64_t *row_ptr,
                        const int32_t *col, const double *val,
                        int64_t *t_ptr, int32_t *t_col, double *t_val);
+/* The matrix a half-stored symmetric COO describes, A = S + S^T - diag(S), for
+ * a square n x n S of any pattern (lower, upper or mixed): every off-diagonal
+ * entry (i, j, v) also stands for (j, i, v), diagonal entries count once,
+ * duplicates and entries stored on both sides each count as listed (the
+ * Matrix Market expansion).  Skew-symmetric and hermitian meanings are not
+ * covered: spmv_mtx_info.symmetric does not tell the banners apart.
+ * Output: the nnz input entries in input order, then (col, row, val) of every
+ * off-diagonal input entry in input order; *nnz_out = their count.  With
+ * row_out == NULL only the count is written.  spmv_csr_from_coo of the output
+ * (stable) defines the expanded CSR, element for element what
+ * spmv_plan_prepare_symmetric(SPMV_S_EXPAND) builds on the device (spmv.h).
+ * SPMV_OTHER_ERROR for negative sizes, an index outside [0, n) or a NULL
+ * array that would be read or written.                                     */
+int spmv_coo_symmetrize(int64_t n, int64_t nnz, const int32_t *row, const int32_t *col,
+                        const double *val, int64_t *nnz_out, int32_t *row_out,
+                        int32_t *col_out, double *val_out);
 /* Entries of every CSR row reordered by increasing column (stable).  With
  * degree-relabelled columns (spmv_column_relabel) a long row then reads x
  * from its dense hot prefix in address order.  Changes each row's
@@ -316,6 +332,15 @@ int spmv_cpu_csr_multi(int64_t n_rows, const int64_t *row_ptr, const int32_t *co
  * read or written (nothing of y past a bad entry's row is touched).       */
 int spmv_cpu_csr_t(int64_t n_rows, int64_t n_cols, const int64_t *row_ptr,
                    const int32_t *col, const double *val, const double *x, double *y);
+/* y = (S + S^T - diag S) x on the half storage S (n x n CSR, any pattern;
+ * spmv_coo_symmetrize has the definition): zeroes y[0 .. n), then one serial
+ * pass in which entry (r, c, v) adds v x[c] to y[r] and, when c != r, v x[r]
+ * to y[c].  The CPU statement of spmv_plan_run_sym (spmv.h) and the CPU
+ * baseline of ./bin/csr --symmetric, never a device fallback.
+ * SPMV_OTHER_ERROR for a negative size, a column outside [0, n) or a NULL
+ * array that would be read or written.                                     */
+int spmv_cpu_csr_sym(int64_t n, const int64_t *row_ptr, const int32_t *col, const double *val,
+                     const double *x, double *y);
 /* Y = A^T X for k >= 1 vectors stored row-major, the layout of
  * spmv_plan_run_t_multi (spmv.h): X[r*ldx + j], r < n_rows; Y[c*ldy + j],
  * c < n_cols; j < k; ldx >= k, ldy >= k.  Serial: zeroes Y[c*ldy + j], j < k,

@@ -4,6 +4,24 @@
 
 #include "common.h"
 
+namespace spmv {
+// What spmv_plan_prepare_symmetric built (symmetric.hip).  A new mode is
+// built into a fresh SymState and swapped in on success, so a failed prepare
+// leaves the plan as it was.
+struct SymState {
+    int32_t mode = 0;         // enum spmv_symmetric_mode
+    int32_t xcap = 0;         // fused: widest union window that fits the cap
+    int64_t blocks = 0, win_blocks = 0, flush = 0;
+    void *win = nullptr;      // fused: int2 {lo, hi} union window per row block
+    int64_t nnz_a = 0;        // expand: entries of A = S + S^T - diag S
+    int64_t *ptr = nullptr;   // expand: A as CSR (ptr[n+1], col/val[nnz_a])
+    int32_t *col = nullptr;
+    double *val = nullptr;
+    spmv_plan *inner = nullptr;  // expand: the forward CSR plan over A
+    size_t owned = 0;
+};
+}  // namespace spmv
+
 struct spmv_plan {
     int fmt;  // SPMV_FMT_*
     int path; // PlanPath (plan.hip)
@@ -63,6 +81,9 @@ struct spmv_plan {
     int64_t m_long_entries = 0;
     spmv::MultiBalance m_bal;          // counts, device tables, partial workspace (plan-owned)
     size_t m_owned = 0;
+    // the symmetric product (spmv_plan_prepare_symmetric, symmetric.hip); its
+    // bytes are counted in sym.owned, never in `owned`, t_owned or m_owned
+    spmv::SymState sym;
 };
 
 namespace spmv {
@@ -70,4 +91,6 @@ namespace spmv {
 void plan_multi_free(spmv_plan *p);
 // frees what spmv_plan_prepare_transpose built (the plan's device is current)
 void plan_transpose_free(spmv_plan *p);
+// frees what spmv_plan_prepare_symmetric built (the plan's device is current)
+void plan_symmetric_free(spmv_plan *p);
 }  // namespace spmv

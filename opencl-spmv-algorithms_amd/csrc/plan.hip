@@ -286,6 +286,7 @@ int spmv_plan_destroy(spmv_plan *p)
         (void)hipSetDevice(p->d.device);
     plan_transpose_free(p);
     plan_multi_free(p);
+    plan_symmetric_free(p);
     for (void *q : owned)
         if (q)
             (void)hipFree(q);

@@ -1,0 +1,601 @@
+// symmetric.hip — the symmetric product y = (S + S^T - diag S) x of a square
+// CSR plan that stores one half of a symmetric matrix
+// (spmv_plan_prepare_symmetric / spmv_plan_run_sym, include/spmv.h).
+//
+// Every stored off-diagonal entry (i, j, v) also stands for (j, i, v); the
+// diagonal counts once; duplicates and entries stored on both sides count as
+// listed (spmv_coo_symmetrize, spmv_host.h).  Skew-symmetric and hermitian
+// meanings are out of scope.  Two modes, chosen at build time:
+//   SPMV_S_FUSED   one pass over the half storage, no second copy.  The
+//       geometry of csr_t_window_kernel (transpose.hip): one workgroup per
+//       block of 128 rows streams the block's entries once.  The block's
+//       UNION window {lo, hi}, its column range joined with its own rows, is
+//       recorded at build time.  A union of at most 2,048 columns: x[lo..hi]
+//       is staged in LDS beside an accumulator of the same span; entry
+//       (r, c, v) adds v x[c] to acc[r - lo] and, when c != r, v x[r] to
+//       acc[c - lo] (ds_add_f64, both x values from LDS; the row products of
+//       a wave's consecutive entries are summed per row across the wave first
+//       and added once per run); the accumulator is added to the zeroed y
+//       once, consecutive lanes on consecutive columns.
+//       A wider union (power-law columns): the rows' sums go through a
+//       128-entry LDS accumulator, x[c] is gathered from global memory and
+//       every mirrored product is added straight into y
+//       (global_atomic_add_f64).
+//   SPMV_S_EXPAND  A built once on the device as CSR: the symmetrized COO in
+//       spmv_coo_symmetrize's order (the plan's CSR entries, then the mirror
+//       of every off-diagonal one, placed by a prefix sum of the off-diagonal
+//       flags), spmv_dev_csr_from_coo over it, and a forward CSR plan with
+//       default options over the result.
+// Both read the caller's row_ptr / col / val, never the plan's hot-renumbered
+// column copy, and are independent of the transposed and multi-vector modes.
+#include <hipcub/hipcub.hpp>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include "common.h"
+#include "plan.h"
+
+namespace spmv {
+
+constexpr int kSRows = 128;       // rows per block
+constexpr int32_t kSCap = 2048;   // widest union window summed in LDS (x + accumulator: 32 KiB)
+constexpr int kSPtr = kSRows + 2; // LDS slots of the block's kSRows + 1 row offsets (a 16-byte multiple)
+constexpr int kSU = 4;            // entries in flight per thread
+
+// Union window {lo, hi} of every block of kSRows rows: the range of its
+// columns inside [0, n) joined with its own rows ({0, -1}: no such entry).  A
+// column outside [0, n) is left out here and dropped by the run's checks.
+__global__ __launch_bounds__(kBlock) void csr_sym_range_kernel(int64_t n, int64_t nnz,
+                                                               const int64_t *__restrict__ ptr,
+                                                               const int32_t *__restrict__ col,
+                                                               int2 *__restrict__ win)
+{
+    const int64_t r0 = (int64_t)blockIdx.x * kSRows;
+    const int64_t r1 = r0 + kSRows < n ? r0 + kSRows : n;
+    int lo = INT32_MAX, hi = INT32_MIN;
+    if (nnz > 0)
+        for (int64_t e = ptr[r0] + threadIdx.x, e1 = ptr[r1]; e < e1; e += kBlock) {
+            const int c = col[e];
+            if (c >= 0 && c < n) {
+                lo = c < lo ? c : lo;
+                hi = c > hi ? c : hi;
+            }
+        }
+    int2 r = block_minmax(lo, hi);
+    if (threadIdx.x == 0) {
+        if (r.y >= r.x) {
+            r.x = r0 < r.x ? (int)r0 : r.x;
+            r.y = r1 - 1 > r.y ? (int)(r1 - 1) : r.y;
+        }
+        win[blockIdx.x] = r;
+    }
+}
+
+// The block's entries [s_ptr[0], s_ptr[nr]) as one coalesced non-temporal
+// stream (thread t takes entries t, t + 256, ... with kSU in flight); the row
+// of an entry is the last r with s_ptr[r] <= e, a 7-step search in LDS.
+// WIN = true: xs = x[lo .. lo + bound) and acc of the same span, both LDS;
+// an entry whose row or column lies outside the window is dropped whole.
+// WIN = false: xs = x of the block's rows and acc their 128 sums, both LDS;
+// x[c] comes from global memory, the mirrored product goes straight into
+// y[c]; bound = n, a column outside [0, n) is dropped whole.
+// SPMV_SYM_ROW_REDUCE = 1 (the default): the row products of a wave's 64
+// consecutive entries are summed per row across the wave before they reach the
+// accumulator; 0 (an A/B build, -DSPMV_SYM_ROW_REDUCE=0): every entry adds its
+// own row product.  Measured cold on the cant-like lower triangle
+// (profiles/symmetric/README.md): 0.0259 against 0.0268 ms on one matrix,
+// 0.302 against 0.379 ms on the 32-copy batch.
+#ifndef SPMV_SYM_ROW_REDUCE
+#define SPMV_SYM_ROW_REDUCE 1
+#endif
+
+#if SPMV_SYM_ROW_REDUCE
+// A wave's 64 consecutive entries belong to few rows (32 entries per stored
+// cant-like row), so their row products would meet at few accumulator words
+// and the LDS adds of one instruction would run one after another.  Each run
+// of equal keys (lanes in entry order; -1: nothing to add) is summed across
+// the wave by a segmented scan and its last lane alone adds the sum.  Called
+// in uniform control flow (every lane of the wave active).
+__device__ __forceinline__ void wave_run_add(double *acc, int key, double p)
+{
+    const int lane = (int)threadIdx.x % kWave;
+#pragma unroll
+    for (int off = 1; off < kWave; off <<= 1) {
+        const double t = __shfl_up(p, off);
+        const int k = __shfl_up(key, off);
+        if (lane >= off && k == key)
+            p += t;
+    }
+    const int next = __shfl_down(key, 1);
+    if (key >= 0 && (lane == kWave - 1 || next != key))
+        atomicAdd(&acc[key], p);
+}
+
+// sym_block with uniform loops over the workgroup (the shuffles need whole
+// waves): in the last partial step a lane past the end carries key -1.
+template <bool WIN>
+__device__ __forceinline__ void sym_block(const int64_t *s_ptr, int nr, int64_t r0, const int32_t *__restrict__ col,
+                                          const double *__restrict__ val, const double *__restrict__ x,
+                                          double *__restrict__ y, const double *xs, double *acc, int32_t lo,
+                                          uint32_t bound)
+{
+    auto add = [&](bool live, int64_t e, int32_t c, double v) {
+        int r = 0;
+#pragma unroll
+        for (int step = kSRows / 2; step > 0; step >>= 1)
+            if (r + step < nr && s_ptr[r + step] <= e)
+                r += step;
+        int key = -1;
+        double p = 0.0;
+        if constexpr (WIN) {
+            const uint32_t jr = (uint32_t)(r0 + r) - (uint32_t)lo;
+            const uint32_t jc = (uint32_t)c - (uint32_t)lo;
+            if (live && jr < bound && jc < bound) {
+                key = (int)jr;
+                p = v * xs[jc];
+                if (jc != jr)
+                    atomicAdd(&acc[jc], v * xs[jr]);
+            }
+        } else {
+            if (live && (uint32_t)c < bound) {
+                key = r;
+                p = v * x[c];
+                if ((int64_t)c != r0 + r)
+                    unsafeAtomicAdd(&y[c], v * xs[r]);
+            }
+        }
+        wave_run_add(acc, key, p);
+    };
+    const int64_t end = s_ptr[nr];
+    int64_t e0 = s_ptr[0];  // uniform
+    for (; e0 + kSU * kBlock <= end; e0 += kSU * kBlock) {
+        const int64_t e = e0 + (int64_t)threadIdx.x;
+        int32_t c[kSU];
+        double v[kSU];
+#pragma unroll
+        for (int u = 0; u < kSU; ++u) {
+            c[u] = stream_load<true>(col + e + u * kBlock);
+            v[u] = stream_load<true>(val + e + u * kBlock);
+        }
+#pragma unroll
+        for (int u = 0; u < kSU; ++u)
+            add(true, e + u * kBlock, c[u], v[u]);
+    }
+    for (; e0 < end; e0 += kBlock) {
+        const int64_t e = e0 + (int64_t)threadIdx.x;
+        const bool live = e < end;
+        int32_t c = -1;
+        double v = 0.0;
+        if (live) {
+            c = stream_load<true>(col + e);
+            v = stream_load<true>(val + e);
+        }
+        add(live, e, c, v);
+    }
+}
+#else
+template <bool WIN>
+__device__ __forceinline__ void sym_block(const int64_t *s_ptr, int nr, int64_t r0, const int32_t *__restrict__ col,
+                                          const double *__restrict__ val, const double *__restrict__ x,
+                                          double *__restrict__ y, const double *xs, double *acc, int32_t lo,
+                                          uint32_t bound)
+{
+    auto add = [&](int64_t e, int32_t c, double v) {
+        int r = 0;
+#pragma unroll
+        for (int step = kSRows / 2; step > 0; step >>= 1)
+            if (r + step < nr && s_ptr[r + step] <= e)
+                r += step;
+        if constexpr (WIN) {
+            const uint32_t jr = (uint32_t)(r0 + r) - (uint32_t)lo;
+            const uint32_t jc = (uint32_t)c - (uint32_t)lo;
+            if (jr < bound && jc < bound) {
+                atomicAdd(&acc[jr], v * xs[jc]);
+                if (jc != jr)
+                    atomicAdd(&acc[jc], v * xs[jr]);
+            }
+        } else {
+            if ((uint32_t)c < bound) {
+                atomicAdd(&acc[r], v * x[c]);
+                if ((int64_t)c != r0 + r)
+                    unsafeAtomicAdd(&y[c], v * xs[r]);
+            }
+        }
+    };
+    const int64_t end = s_ptr[nr];
+    int64_t e = s_ptr[0] + (int64_t)threadIdx.x;
+    for (; e + (kSU - 1) * kBlock < end; e += kSU * kBlock) {
+        int32_t c[kSU];
+        double v[kSU];
+#pragma unroll
+        for (int u = 0; u < kSU; ++u) {
+            c[u] = stream_load<true>(col + e + u * kBlock);
+            v[u] = stream_load<true>(val + e + u * kBlock);
+        }
+#pragma unroll
+        for (int u = 0; u < kSU; ++u)
+            add(e + u * kBlock, c[u], v[u]);
+    }
+    for (; e < end; e += kBlock)
+        add(e, stream_load<true>(col + e), stream_load<true>(val + e));
+}
+#endif
+
+// One workgroup per block of kSRows rows.  LDS: the block's kSRows + 1 row
+// offsets, then two arrays of the union's span (x window, accumulator) when
+// it is at most `cap`, else two arrays of kSRows (the rows' x, their sums).
+// The launch provides kSPtr + 2 * max(widest fitting span, kSRows) doubles.
+__global__ __launch_bounds__(kBlock) void csr_sym_window_kernel(int64_t n, const int64_t *__restrict__ ptr,
+                                                                const int32_t *__restrict__ col,
+                                                                const double *__restrict__ val,
+                                                                const double *__restrict__ x, double *__restrict__ y,
+                                                                const int2 *__restrict__ win, int32_t cap)
+{
+    extern __shared__ double s_mem[];
+    int64_t *s_ptr = reinterpret_cast<int64_t *>(s_mem);
+    double *xs = s_mem + kSPtr;
+    const int tid = (int)threadIdx.x;
+    const int2 w = win[blockIdx.x];
+    const int span = w.y - w.x + 1;  // <= 0: a block without entries
+    if (span <= 0)                   // uniform per workgroup
+        return;
+    const int64_t r0 = (int64_t)blockIdx.x * kSRows;
+    const int nr = (int)(n - r0 < kSRows ? n - r0 : kSRows);
+    // a window that does not hold the block's rows or leaves [0, n) is not one
+    // this plan recorded: nothing is read or written through it
+    if (w.x < 0 || w.y >= n || w.x > r0 || w.y < r0 + nr - 1)
+        return;
+    for (int i = tid; i <= nr; i += kBlock)
+        s_ptr[i] = ptr[r0 + i];
+    if (span <= cap) {
+        double *acc = xs + span;
+        copy_window(xs, x, w.x, span);
+        for (int j = tid; j < span; j += kBlock)
+            acc[j] = 0.0;
+        __syncthreads();
+        sym_block<true>(s_ptr, nr, r0, col, val, x, y, xs, acc, w.x, (uint32_t)span);
+        __syncthreads();
+        // the flush: consecutive lanes, consecutive columns; sums still exactly
+        // 0.0 add nothing to the zeroed y
+        for (int j = tid; j < span; j += kBlock) {
+            const double s = acc[j];
+            if (s != 0.0)
+                unsafeAtomicAdd(&y[w.x + j], s);
+        }
+        return;
+    }
+    double *acc = xs + kSRows;
+    if (tid < nr) {
+        xs[tid] = x[r0 + tid];
+        acc[tid] = 0.0;
+    }
+    __syncthreads();
+    sym_block<false>(s_ptr, nr, r0, col, val, x, y, xs, acc, 0, (uint32_t)n);
+    __syncthreads();
+    if (tid < nr) {
+        const double s = acc[tid];
+        if (s != 0.0)
+            unsafeAtomicAdd(&y[r0 + tid], s);
+    }
+}
+
+// ------------------------------------------------------------ expand mode
+// Entry e of the CSR: its row (the last r with ptr[r] <= e) and whether it is
+// off the diagonal; flag[nnz] = 0 closes the prefix sum.  A column outside
+// [0, n) sets *bad.
+__global__ void sym_flag_kernel(int64_t nnz, int64_t n, const int64_t *__restrict__ ptr,
+                                const int32_t *__restrict__ col, int32_t *__restrict__ rowid,
+                                int64_t *__restrict__ flag, int *__restrict__ bad)
+{
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e <= nnz; e += stride) {
+        if (e == nnz) {
+            flag[e] = 0;
+            continue;
+        }
+        int64_t lo = 0, hi = n;  // ptr[lo] <= e < ptr[hi]
+        while (hi - lo > 1) {
+            const int64_t mid = lo + (hi - lo) / 2;
+            if (ptr[mid] <= e)
+                lo = mid;
+            else
+                hi = mid;
+        }
+        const int32_t c = col[e];
+        if (c < 0 || c >= n)
+            *bad = 1;
+        rowid[e] = (int32_t)lo;
+        flag[e] = c != (int32_t)lo ? 1 : 0;
+    }
+}
+
+// The symmetrized COO in spmv_coo_symmetrize's order: entry e at e, its mirror
+// (off-diagonal entries only) at nnz + pos[e], pos = the exclusive prefix sum
+// of the flags.
+__global__ void sym_write_kernel(int64_t nnz, const int32_t *__restrict__ rowid, const int32_t *__restrict__ col,
+                                 const double *__restrict__ val, const int64_t *__restrict__ pos,
+                                 int32_t *__restrict__ row_out, int32_t *__restrict__ col_out,
+                                 double *__restrict__ val_out)
+{
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < nnz; e += stride) {
+        const int32_t r = rowid[e], c = col[e];
+        const double v = val[e];
+        row_out[e] = r;
+        col_out[e] = c;
+        val_out[e] = v;
+        if (c != r) {
+            const int64_t k = nnz + pos[e];
+            row_out[k] = c;
+            col_out[k] = r;
+            val_out[k] = v;
+        }
+    }
+}
+
+namespace {
+
+unsigned grid_for(int64_t n)
+{
+    const int64_t g = (n + kBlock - 1) / kBlock;
+    return (unsigned)(g < 1 ? 1 : (g > 65536 ? 65536 : g));
+}
+
+// transient device memory of a prepare: freed when it leaves scope (every
+// user synchronises the stream first)
+struct Scratch {
+    void *p = nullptr;
+    hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 16); }
+    void release()
+    {
+        if (p)
+            (void)hipFree(p);
+        p = nullptr;
+    }
+    ~Scratch() { release(); }
+};
+
+int s_alloc(SymState *s, void **dst, size_t bytes)
+{
+    *dst = nullptr;
+    hipError_t e = hipMalloc(dst, bytes > 0 ? bytes : 16);
+    if (e != hipSuccess)
+        return fail(SPMV_PROGRAM_ERROR, "spmv_plan_prepare_symmetric: hipMalloc", e);
+    s->owned += bytes;
+    return SPMV_SUCCESS;
+}
+
+void state_free(SymState *s)
+{
+    if (s->inner)
+        spmv_plan_destroy(s->inner);
+    for (void *q : {s->win, (void *)s->ptr, (void *)s->col, (void *)s->val})
+        if (q)
+            (void)hipFree(q);
+    *s = SymState{};
+}
+
+size_t fused_lds(int32_t xcap)
+{
+    return (size_t)(kSPtr + 2 * (xcap > kSRows ? xcap : kSRows)) * sizeof(double);
+}
+
+int prepare_fused(const spmv_plan *p, SymState *s)
+{
+    const spmv_dims &d = p->d;
+    const hipStream_t st = (hipStream_t)d.stream;
+    const int64_t blocks = (d.n_rows + kSRows - 1) / kSRows;
+    s->blocks = blocks;
+    if (blocks == 0)  // a run does nothing
+        return SPMV_SUCCESS;
+    int rc = s_alloc(s, &s->win, (size_t)blocks * sizeof(int2));
+    if (rc != SPMV_SUCCESS)
+        return rc;
+    hipLaunchKernelGGL(csr_sym_range_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, st, d.n_rows, d.nnz, p->ptr,
+                       p->col, (int2 *)s->win);
+    SPMV_CHECK_LAUNCH("csr_sym_range_kernel");
+    int2 *h = nullptr;
+    if ((rc = windows_download(s->win, blocks, st, &h, "spmv_plan_prepare_symmetric")) != SPMV_SUCCESS)
+        return rc;
+    for (int64_t b = 0; b < blocks; ++b) {
+        const int64_t span = (int64_t)h[b].y - h[b].x + 1;
+        if (span <= 0)
+            continue;
+        if (span <= kSCap) {
+            s->win_blocks++;
+            s->flush += span;
+            s->xcap = span > s->xcap ? (int32_t)span : s->xcap;
+        } else {
+            const int64_t r0 = b * kSRows;
+            s->flush += d.n_rows - r0 < kSRows ? d.n_rows - r0 : kSRows;
+        }
+    }
+    free(h);
+    return SPMV_SUCCESS;
+}
+
+int prepare_expand(const spmv_plan *p, SymState *s)
+{
+    const spmv_dims &d = p->d;
+    const hipStream_t st = (hipStream_t)d.stream;
+    const int64_t n = d.n_rows, nnz = d.nnz;
+    int rc;
+    hipError_t e;
+    int64_t off = 0;
+    Scratch rowid, flag, pos, bad, tmp, c_row, c_col, c_val;
+    if (nnz > 0) {
+        if ((e = rowid.alloc((size_t)nnz * 4)) != hipSuccess || (e = flag.alloc((size_t)(nnz + 1) * 8)) != hipSuccess ||
+            (e = pos.alloc((size_t)(nnz + 1) * 8)) != hipSuccess || (e = bad.alloc(sizeof(int))) != hipSuccess)
+            return fail(SPMV_PROGRAM_ERROR, "spmv_plan_prepare_symmetric: scratch", e);
+        if ((e = hipMemsetAsync(bad.p, 0, sizeof(int), st)) != hipSuccess)
+            return fail(SPMV_PROGRAM_ERROR, "spmv_plan_prepare_symmetric: memset", e);
+        hipLaunchKernelGGL(sym_flag_kernel, dim3(grid_for(nnz + 1)), dim3(kBlock), 0, st, nnz, n, p->ptr, p->col,
+                           (int32_t *)rowid.p, (int64_t *)flag.p, (int *)bad.p);
+        SPMV_CHECK_LAUNCH("sym_flag_kernel");
+        size_t tbytes = 0;
+        e = hipcub::DeviceScan::ExclusiveSum(nullptr, tbytes, (const int64_t *)flag.p, (int64_t *)pos.p, nnz + 1, st);
+        if (e == hipSuccess)
+            e = tmp.alloc(tbytes);
+        if (e == hipSuccess)
+            e = hipcub::DeviceScan::ExclusiveSum(tmp.p, tbytes, (const int64_t *)flag.p, (int64_t *)pos.p, nnz + 1, st);
+        if (e != hipSuccess)
+            return fail(SPMV_PROGRAM_ERROR, "spmv_plan_prepare_symmetric: prefix sum", e);
+        int h_bad = 0;
+        if ((e = hipMemcpyAsync(&off, (int64_t *)pos.p + nnz, sizeof off, hipMemcpyDeviceToHost, st)) != hipSuccess ||
+            (e = hipMemcpyAsync(&h_bad, bad.p, sizeof h_bad, hipMemcpyDeviceToHost, st)) != hipSuccess ||
+            (e = hipStreamSynchronize(st)) != hipSuccess)
+            return fail(SPMV_PROGRAM_ERROR, "spmv_plan_prepare_symmetric: sync", e);
+        if (h_bad)
+            return fail_msg(SPMV_OTHER_ERROR, "spmv_plan_prepare_symmetric: column index out of range");
+        flag.release();  // the stream is idle: only rowid and pos are still needed
+        tmp.release();
+    }
+    const int64_t nnz_a = nnz + off;
+    s->nnz_a = nnz_a;
+    if ((rc = s_alloc(s, (void **)&s->ptr, (size_t)(n + 1) * sizeof(int64_t))) != SPMV_SUCCESS ||
+        (rc = s_alloc(s, (void **)&s->col, (size_t)nnz_a * sizeof(int32_t))) != SPMV_SUCCESS ||
+        (rc = s_alloc(s, (void **)&s->val, (size_t)nnz_a * sizeof(double))) != SPMV_SUCCESS)
+        return rc;
+    spmv_dims da = d;
+    da.nnz = nnz_a;
+    if (nnz > 0) {
+        if ((e = c_row.alloc((size_t)nnz_a * 4)) != hipSuccess || (e = c_col.alloc((size_t)nnz_a * 4)) != hipSuccess ||
+            (e = c_val.alloc((size_t)nnz_a * 8)) != hipSuccess)
+            return fail(SPMV_PROGRAM_ERROR, "spmv_plan_prepare_symmetric: scratch", e);
+        hipLaunchKernelGGL(sym_write_kernel, dim3(grid_for(nnz)), dim3(kBlock), 0, st, nnz, (const int32_t *)rowid.p,
+                           p->col, p->val, (const int64_t *)pos.p, (int32_t *)c_row.p, (int32_t *)c_col.p,
+                           (double *)c_val.p);
+        SPMV_CHECK_LAUNCH("sym_write_kernel");
+    }
+    // synchronises the stream: the transient buffers are idle when they go
+    if ((rc = spmv_dev_csr_from_coo(da, (const int32_t *)c_row.p, (const int32_t *)c_col.p, (const double *)c_val.p,
+                                    s->ptr, s->col, s->val)) != SPMV_SUCCESS)
+        return rc;
+    return spmv_plan_csr(da, s->ptr, s->col, s->val, nullptr, &s->inner);
+}
+
+int launch_fused(const spmv_plan *p, const double *x, double *y, hipStream_t st)
+{
+    const spmv_dims &d = p->d;
+    const SymState &s = p->sym;
+    if (d.n_rows == 0)
+        return SPMV_SUCCESS;
+    hipError_t e = hipMemsetAsync(y, 0, (size_t)d.n_rows * sizeof(double), st);
+    if (e != hipSuccess)
+        return fail(SPMV_PROGRAM_ERROR, "spmv_plan_run_sym: memset", e);
+    if (!s.win || d.nnz == 0)
+        return SPMV_SUCCESS;
+    hipLaunchKernelGGL(csr_sym_window_kernel, dim3((unsigned)s.blocks), dim3(kBlock), fused_lds(s.xcap), st, d.n_rows,
+                       p->ptr, p->col, p->val, x, y, (const int2 *)s.win, kSCap);
+    SPMV_CHECK_LAUNCH("csr_sym_window_kernel");
+    return SPMV_SUCCESS;
+}
+
+}  // namespace
+
+void plan_symmetric_free(spmv_plan *p) { state_free(&p->sym); }
+
+}  // namespace spmv
+
+using namespace spmv;
+
+extern "C" {
+
+int spmv_plan_symmetric_supported(const spmv_plan *p)
+{
+    return p && p->fmt == SPMV_FMT_CSR && p->d.n_rows == p->d.n_cols ? 1 : 0;
+}
+
+int spmv_plan_prepare_symmetric(spmv_plan *p, int mode)
+{
+    if (!p)
+        return fail_msg(SPMV_OTHER_ERROR, "spmv_plan_prepare_symmetric: plan is NULL");
+    if (mode != SPMV_S_NONE && mode != SPMV_S_FUSED && mode != SPMV_S_EXPAND)
+        return fail_msg(SPMV_OTHER_ERROR, "spmv_plan_prepare_symmetric: unknown mode");
+    if (p->fmt != SPMV_FMT_CSR)
+        return fail_msg(SPMV_OTHER_ERROR, "spmv_plan_prepare_symmetric: only CSR plans have a symmetric run");
+    if (p->d.n_rows != p->d.n_cols)
+        return fail_msg(SPMV_OTHER_ERROR, "spmv_plan_prepare_symmetric: the matrix is not square");
+    if (mode == p->sym.mode)
+        return SPMV_SUCCESS;
+    if (p->d.n_rows > INT32_MAX)
+        return fail_msg(SPMV_OTHER_ERROR, "spmv_plan_prepare_symmetric: row ids are int32");
+    SPMV_GUARD(p->d);
+    const hipStream_t st = (hipStream_t)p->d.stream;
+    SymState next;
+    int rc = SPMV_SUCCESS;
+    if (mode != SPMV_S_NONE) {
+        rc = mode == SPMV_S_FUSED ? prepare_fused(p, &next) : prepare_expand(p, &next);
+        // runs may come on any stream: everything is complete when this returns
+        if (rc == SPMV_SUCCESS && hipStreamSynchronize(st) != hipSuccess)
+            rc = fail_msg(SPMV_PROGRAM_ERROR, "spmv_plan_prepare_symmetric: synchronise");
+        if (rc != SPMV_SUCCESS) {  // the plan stays as it was
+            char keep[512];
+            snprintf(keep, sizeof keep, "%s", spmv_last_error());
+            (void)hipStreamSynchronize(st);
+            state_free(&next);
+            return fail_msg(rc, keep);
+        }
+        next.mode = mode;
+    }
+    // a run of the old mode may still be in flight on the build stream
+    if (p->sym.mode != SPMV_S_NONE && hipStreamSynchronize(st) != hipSuccess) {
+        state_free(&next);
+        return fail_msg(SPMV_PROGRAM_ERROR, "spmv_plan_prepare_symmetric: synchronise");
+    }
+    state_free(&p->sym);
+    p->sym = next;
+    return SPMV_SUCCESS;
+}
+
+int spmv_plan_get_symmetric_info(const spmv_plan *p, spmv_symmetric_info *info)
+{
+    if (!p || !info)
+        return fail_msg(SPMV_OTHER_ERROR, "spmv_plan_get_symmetric_info: NULL argument");
+    memset(info, 0, sizeof *info);
+    const SymState &s = p->sym;
+    info->mode = s.mode;
+    info->owned_bytes = (int64_t)(s.owned + (s.inner ? s.inner->owned : 0));
+    if (s.mode == SPMV_S_FUSED) {
+        info->cap = kSCap;
+        info->blocks = s.blocks;
+        info->window_blocks = s.win_blocks;
+        info->flush_entries = s.flush;
+        snprintf(info->kernel, sizeof info->kernel, "csr_sym_window_kernel");
+    } else if (s.inner) {
+        info->nnz_expanded = s.nnz_a;
+        snprintf(info->kernel, sizeof info->kernel, "%s", s.inner->kernel);
+    }
+    return SPMV_SUCCESS;
+}
+
+int spmv_plan_get_symmetric_arrays(const spmv_plan *p, const int64_t **row_ptr, const int32_t **col,
+                                   const double **val, int64_t *nnz)
+{
+    if (!p || !row_ptr || !col || !val || !nnz)
+        return fail_msg(SPMV_OTHER_ERROR, "spmv_plan_get_symmetric_arrays: NULL argument");
+    if (p->sym.mode != SPMV_S_EXPAND)
+        return fail_msg(SPMV_OTHER_ERROR, "spmv_plan_get_symmetric_arrays: the plan is not in SPMV_S_EXPAND mode");
+    *row_ptr = p->sym.ptr;
+    *col = p->sym.col;
+    *val = p->sym.val;
+    *nnz = p->sym.nnz_a;
+    return SPMV_SUCCESS;
+}
+
+int spmv_plan_run_sym(const spmv_plan *p, const double *x, double *y, void *stream)
+{
+    if (!p)
+        return fail_msg(SPMV_OTHER_ERROR, "spmv_plan_run_sym: plan is NULL");
+    if (p->sym.mode == SPMV_S_NONE)
+        return fail_msg(SPMV_OTHER_ERROR, "spmv_plan_run_sym: the plan was not prepared (spmv_plan_prepare_symmetric)");
+    if (p->d.n_rows > 0 && (!x || !y))
+        return fail_msg(SPMV_OTHER_ERROR, "spmv_plan_run_sym: x or y is NULL");
+    if (p->sym.mode == SPMV_S_EXPAND)
+        return spmv_plan_run(p->sym.inner, x, y, stream);
+    SPMV_GUARD(p->d);
+    return launch_fused(p, x, y, (hipStream_t)stream);
+}
+
+}  // extern "C"

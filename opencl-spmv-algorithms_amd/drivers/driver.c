@@ -29,6 +29,16 @@
  *          --C C --sigma S --ki K --h H --lanes L  --threads T
  *          --cpu / --no-cpu  --strict  --write-mtx PATH  --cache  --no-xwin  --gpus N
  *          --relabel auto|yes|no  --write-y PATH  --help
+ *          --expand-symmetric  --symmetric fused|expand (csr only)
+ *   --expand-symmetric: the input holds one half of a symmetric matrix (a
+ *   Matrix Market `symmetric` file, --gen cantlike2); after reading or
+ *   generating it is expanded on the host (spmv_coo_symmetrize: every
+ *   off-diagonal entry mirrored, no skew or hermitian signs) and everything
+ *   proceeds on the expanded entries: the printed Z, the format, the check.
+ *   --symmetric fused|expand (./bin/csr only, one GPU): the plan is built over
+ *   the half storage as read and timed with spmv_plan_run_sym in that mode
+ *   (spmv.h); the check runs against the host-expanded entries, the CPU
+ *   baseline is spmv_cpu_csr_sym on the half storage.
  *   --cache keeps a binary copy of the parsed file at PATH.bin (SURVEY.md
  *   §8f row 1) and reads it instead of the text whenever it is at least as
  *   new as PATH; the entries, their order and the result are unchanged.
@@ -78,6 +88,8 @@ typedef struct {
     int64_t copies;
     int reps, warmup, warm, device, C, sigma, ki, h, lanes, threads, cpu, strict, cache, xwin, gpus, index16, single_pass;
     int relabel; /* -1 auto, 0 no, 1 yes */
+    int expand_symmetric;
+    int symmetric; /* 0, SPMV_S_FUSED or SPMV_S_EXPAND */
 } opts_t;
 
 static void usage(const char *prog)
@@ -88,7 +100,8 @@ static void usage(const char *prog)
            "          [--threads T] [--cpu|--no-cpu] [--strict] [--write-mtx PATH] [--cache]\n"
            "          [--no-xwin] [--gpus N] [--index16 (sigma_c: SELL16)]\n"
            "          [--carry-pass (coo: the carry kernel even where rows allow one pass)]\n"
-           "          [--relabel auto|yes|no] [--write-y PATH]\n",
+           "          [--relabel auto|yes|no] [--write-y PATH]\n"
+           "          [--expand-symmetric] [--symmetric fused|expand (csr only)]\n",
            prog);
 }
 
@@ -130,6 +143,15 @@ static int parse_opts(int argc, char **argv, spmv_format fmt, opts_t *o)
                 return SPMV_OTHER_ERROR;
             }
         }
+        else if (!strcmp(a, "--symmetric")) {
+            NEEDV();
+            o->symmetric = !strcmp(v, "fused") ? SPMV_S_FUSED : !strcmp(v, "expand") ? SPMV_S_EXPAND : -1;
+            if (o->symmetric < 0) {
+                fprintf(stderr, "--symmetric takes fused or expand\n");
+                return SPMV_OTHER_ERROR;
+            }
+        }
+        else if (!strcmp(a, "--expand-symmetric")) o->expand_symmetric = 1;
         else if (!strcmp(a, "--copies")) { NEEDV(); o->copies = atoll(v); }
         else if (!strcmp(a, "--reps")) { NEEDV(); o->reps = atoi(v); }
         else if (!strcmp(a, "--warmup")) { NEEDV(); o->warmup = atoi(v); }
@@ -162,6 +184,11 @@ static int parse_opts(int argc, char **argv, spmv_format fmt, opts_t *o)
         return SPMV_OTHER_ERROR;
     if (o->index16 && (fmt != FMT_SELL || !o->xwin || o->gpus > 0)) {
         fprintf(stderr, "--index16 is SELL16: sigma_c, one GPU, with x windows\n");
+        return SPMV_OTHER_ERROR;
+    }
+    if (o->symmetric && (fmt != FMT_CSR || o->gpus > 0 || o->relabel == 1 || o->expand_symmetric)) {
+        fprintf(stderr, "--symmetric is the CSR plan's symmetric run: csr, one GPU, without --relabel yes or "
+                        "--expand-symmetric\n");
         return SPMV_OTHER_ERROR;
     }
     return SPMV_SUCCESS;
@@ -298,6 +325,40 @@ static int load_input(const opts_t *o, spmv_format fmt, coo_t *m)
     return rc;
 }
 
+/* --expand-symmetric / --symmetric: m becomes the matrix its half storage
+ * describes (spmv_coo_symmetrize).  keep: the old arrays stay alive (the
+ * caller still plans over them), else they are freed. */
+static int expand_input(coo_t *m, int keep)
+{
+    if (m->n_rows != m->n_cols) {
+        printf("symmetric expansion needs a square matrix (%lld x %lld)\n", (long long)m->n_rows, (long long)m->n_cols);
+        return SPMV_OTHER_ERROR;
+    }
+    int64_t z = 0;
+    int rc = spmv_coo_symmetrize(m->n_rows, m->nnz, m->row, m->col, m->val, &z, NULL, NULL, NULL);
+    if (rc != SPMV_SUCCESS)
+        return rc;
+    int32_t *row = malloc((size_t)(z + 1) * sizeof(int32_t));
+    int32_t *col = malloc((size_t)(z + 1) * sizeof(int32_t));
+    double *val = malloc((size_t)(z + 1) * sizeof(double));
+    if (!row || !col || !val)
+        return SPMV_OTHER_ERROR;
+    if ((rc = spmv_coo_symmetrize(m->n_rows, m->nnz, m->row, m->col, m->val, &z, row, col, val)) != SPMV_SUCCESS)
+        return rc;
+    printf("  [symmetric] %lld stored entries expanded to %lld (every off-diagonal entry mirrored)\n",
+           (long long)m->nnz, (long long)z);
+    if (!keep) {
+        free(m->row);
+        free(m->col);
+        free(m->val);
+    }
+    m->row = row;
+    m->col = col;
+    m->val = val;
+    m->nnz = z;
+    return SPMV_SUCCESS;
+}
+
 /* ----------------------------------------------------- device format */
 
 typedef struct {
@@ -309,6 +370,7 @@ typedef struct {
     uint8_t *d_rin;
     double *d_val, *d_x, *d_y;
     spmv_plan *plan; /* the library's kernel path for this matrix (spmv.h) */
+    int sym;         /* --symmetric: the plan holds the stored half, runs are spmv_plan_run_sym */
     int32_t K, C, sigma, ki, h;
     int64_t ld, n_slices, n_strips;
     /* host copies for the CPU loop */
@@ -469,6 +531,8 @@ static int build_format(const opts_t *o, spmv_format fmt, const coo_t *m, dev_fm
 static int launch(void *arg)
 {
     const dev_fmt_t *f = (const dev_fmt_t *)arg;
+    if (f->sym)
+        return spmv_plan_run_sym(f->plan, f->d_x, f->d_y, f->d.stream);
     return spmv_plan_run(f->plan, f->d_x, f->d_y, f->d.stream);
 }
 
@@ -581,6 +645,8 @@ static int run_cpu(const dev_fmt_t *f, const double *x, double *y, int threads)
     case FMT_COO:
         return spmv_cpu_coo(N, f->d.nnz, f->h_row, f->h_col, f->h_val, x, y, threads);
     case FMT_CSR:
+        if (f->sym)
+            return spmv_cpu_csr_sym(N, f->h_ptr, f->h_col, f->h_val, x, y);
         return spmv_cpu_csr(N, f->h_ptr, f->h_col, f->h_val, x, y, threads);
     case FMT_ELL:
         return spmv_cpu_ell(N, f->K, f->ld, f->ki, f->h_col, f->h_val, x, y, threads);
@@ -846,6 +912,9 @@ int spmv_driver_main(int argc, char **argv, spmv_format fmt)
     int rc = load_input(&o, fmt, &m);
     if (rc != SPMV_SUCCESS)
         return rc;
+    coo_t half = m; /* --symmetric: the stored half the plan is built over */
+    if ((o.expand_symmetric || o.symmetric) && (rc = expand_input(&m, o.symmetric != 0)) != SPMV_SUCCESS)
+        return rc;
     if (o.write_mtx)
         spmv_mtx_write(o.write_mtx, m.n_rows, m.n_cols, m.nnz, m.row, m.col, m.val, 0);
 
@@ -860,7 +929,7 @@ int spmv_driver_main(int argc, char **argv, spmv_format fmt)
     /* --relabel: the degree-ordered layout bench.py measures configs[3] on */
     coo_t mr = m;
     double *xr = x;
-    int relabel = o.relabel;
+    int relabel = o.symmetric ? 0 : o.relabel;
     if (relabel < 0) { /* auto: when the CSR skew rule picks the entry-balanced kernel */
         int64_t *ptr = malloc((size_t)(m.n_rows + 1) * sizeof(int64_t));
         int32_t *tc = malloc((size_t)(m.nnz + 1) * sizeof(int32_t));
@@ -884,7 +953,11 @@ int spmv_driver_main(int argc, char **argv, spmv_format fmt)
         return run_multi(&o, fmt, &m, x, y, y_cpu, &mr, xr);
 
     dev_fmt_t f;
-    rc = build_format(&o, fmt, &mr, &f, relabel);
+    rc = build_format(&o, fmt, o.symmetric ? &half : &mr, &f, relabel);
+    if (rc == SPMV_SUCCESS && o.symmetric) {
+        rc = spmv_plan_prepare_symmetric(f.plan, o.symmetric);
+        f.sym = 1;
+    }
     if (rc != SPMV_SUCCESS) {
         printf("format build/upload failed: %s %s\n", spmv_strerror(rc), spmv_last_error());
         return rc == SPMV_OTHER_ERROR ? SPMV_OTHER_ERROR : SPMV_PROGRAM_ERROR;
@@ -922,8 +995,9 @@ int spmv_driver_main(int argc, char **argv, spmv_format fmt)
     print_performance(ms, m.nnz);
     print_speed(ms, m.nnz);
 
-    const double bytes_alg = 12.0 * (double)m.nnz + 4.0 * (double)(m.n_rows + 1) +
-                             8.0 * (double)m.n_cols + 8.0 * (double)m.n_rows;
+    /* --symmetric fused streams the stored half; every other run the entries it multiplies */
+    const double bytes_alg = 12.0 * (double)(o.symmetric == SPMV_S_FUSED ? half.nnz : m.nnz) +
+                             4.0 * (double)(m.n_rows + 1) + 8.0 * (double)m.n_cols + 8.0 * (double)m.n_rows;
     char dev[128] = "";
     spmv_device_name(o.device, dev, sizeof dev);
     printf("  [%s] %s | N=%lld M=%lld Z=%lld | %s, %d reps (per-launch event median %.4f ms)\n",
@@ -937,6 +1011,14 @@ int spmv_driver_main(int argc, char **argv, spmv_format fmt)
            100.0 * bytes_alg / ms * 1e-6 / HBM_PEAK_GBS, HBM_PEAK_GBS,
            (double)f.stored_bytes * 1e-6, dev);
     print_plan(&f, "");
+    if (o.symmetric) {
+        spmv_symmetric_info si;
+        if (spmv_plan_get_symmetric_info(f.plan, &si) == SPMV_SUCCESS)
+            printf("  [symmetric] %s over %lld stored entries: kernel %s, %lld of %lld row blocks in LDS windows "
+                   "(cap %d), %lld plan-owned bytes\n",
+                   o.symmetric == SPMV_S_FUSED ? "fused" : "expand", (long long)half.nnz, si.kernel,
+                   (long long)si.window_blocks, (long long)si.blocks, (int)si.cap, (long long)si.owned_bytes);
+    }
 
     if (spmv_download(y, f.d_y, (size_t)m.n_rows * 8, NULL) != SPMV_SUCCESS) {
         printf("read back error: %s\n", spmv_last_error());

@@ -252,10 +252,17 @@ class DistOperator:
 
 
 def build_operator(m: sa.Coo, rank: int = 0, world: int = 1, fmt: str = "csr", device="cuda:0", align: int = 1024,
-                   split: bool = False, overlap: bool = False, **fmt_kw) -> DistOperator:
+                   split: bool = False, overlap: bool = False, expand_symmetric: bool = False,
+                   **fmt_kw) -> DistOperator:
     """Partition, renumber and upload this rank's shard (HIP kernels).
     split (implied by overlap): local / remote column parts
-    (split_local_remote), each its own device matrix."""
+    (split_local_remote), each its own device matrix.
+    expand_symmetric: m holds one half of a symmetric matrix (a Matrix Market
+    `symmetric` file); sa.expand_symmetric turns it into the matrix it
+    describes before sharding, which is what CG needs.  Default: the entries
+    as listed."""
+    if expand_symmetric:
+        m = sa.expand_symmetric(m)
     counts = np.bincount(m.row, minlength=m.n_rows).astype(np.int64)
     layout = layout_for(m.n_rows, counts, world, align)
     loc = local_shard(m, layout, rank)

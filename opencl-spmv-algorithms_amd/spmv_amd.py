@@ -122,6 +122,17 @@ class TransposeMultiInfo(ctypes.Structure):
 TRANSPOSE_MODES = {None: 0, "scatter": 1, "copy": 2}  # enum spmv_transpose_mode
 
 
+class SymmetricInfo(ctypes.Structure):
+    """``spmv_symmetric_info`` (include/spmv.h)."""
+
+    _fields_ = [("mode", _c_i32), ("cap", _c_i32)] + \
+               [(k, _c_i64) for k in ("blocks", "window_blocks", "flush_entries", "nnz_expanded", "owned_bytes")] + \
+               [("kernel", ctypes.c_char * 64)]
+
+
+SYMMETRIC_MODES = {None: 0, "fused": 1, "expand": 2}  # enum spmv_symmetric_mode
+
+
 class MultiOpts(ctypes.Structure):
     """``spmv_multi_opts`` (include/spmv.h); -1 = the library's rule."""
 
@@ -162,6 +173,11 @@ HIP_SYMBOLS = {
     "spmv_plan_run_t": (ctypes.c_int, [_vp, _vp, _vp, _vp]),
     "spmv_plan_run_t_multi": (ctypes.c_int, [_vp, _c_i32, _vp, _c_i64, _vp, _c_i64, _vp]),
     "spmv_plan_get_transpose_multi_info": (ctypes.c_int, [_vp, ctypes.POINTER(TransposeMultiInfo)]),
+    "spmv_plan_symmetric_supported": (ctypes.c_int, [_vp]),
+    "spmv_plan_prepare_symmetric": (ctypes.c_int, [_vp, ctypes.c_int]),
+    "spmv_plan_get_symmetric_info": (ctypes.c_int, [_vp, ctypes.POINTER(SymmetricInfo)]),
+    "spmv_plan_run_sym": (ctypes.c_int, [_vp, _vp, _vp, _vp]),
+    "spmv_plan_get_symmetric_arrays": (ctypes.c_int, [_vp, _PP, _PP, _PP, ctypes.POINTER(_c_i64)]),
     "spmv_plan_get_info": (ctypes.c_int, [_vp, ctypes.POINTER(PlanInfo)]),
     "spmv_plan_destroy": (ctypes.c_int, [_vp]),
     "spmv_set_option": (ctypes.c_int, [ctypes.c_int, ctypes.c_int]),
@@ -309,6 +325,8 @@ HOST_SYMBOLS = {
     "spmv_coo_sort_by_row": (ctypes.c_int, [_c_i64, _c_i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "spmv_csr_from_coo": (ctypes.c_int, [_c_i64, _c_i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "spmv_csr_transpose": (ctypes.c_int, [_c_i64, _c_i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "spmv_coo_symmetrize": (ctypes.c_int, [_c_i64, _c_i64, _vp, _vp, _vp, ctypes.POINTER(_c_i64), _vp, _vp, _vp]),
+    "spmv_cpu_csr_sym": (ctypes.c_int, [_c_i64, _vp, _vp, _vp, _vp, _vp]),
     "spmv_csr_sort_rows": (ctypes.c_int, [_c_i64, _vp, _vp, _vp]),
     "spmv_csr_row_stats": (ctypes.c_int, [_c_i64, _vp, ctypes.POINTER(_c_i64), ctypes.POINTER(_c_i64), ctypes.POINTER(ctypes.c_double)]),
     "spmv_csr_pick_variant": (ctypes.c_int, [_c_i64, _vp]),
@@ -539,6 +557,36 @@ def cpu_csr_t(n_rows: int, n_cols: int, ptr, col, val, x: np.ndarray, y: np.ndar
             raise SpmvError(OTHER_ERROR, "cpu_csr_t", "x or y too short")
     _check_host(host_lib().spmv_cpu_csr_t(n_rows, n_cols, _ptr(ptr), _ptr(col), _ptr(val), _ptr(x), _ptr(y)),
                 "spmv_cpu_csr_t")
+
+
+def expand_symmetric(m: Coo) -> Coo:
+    """The matrix a half-stored symmetric COO describes, A = S + S^T - diag S
+    (spmv_coo_symmetrize): m's entries in their order, then the mirror of every
+    off-diagonal one.  The result has symmetric = False: nothing is left to
+    mirror."""
+    if m.n_rows != m.n_cols:
+        raise SpmvError(OTHER_ERROR, "expand_symmetric", "the matrix is not square")
+    lib = host_lib()
+    z = _c_i64()
+    _check_host(lib.spmv_coo_symmetrize(m.n_rows, m.nnz, _ptr(m.row), _ptr(m.col), _ptr(m.val), ctypes.byref(z),
+                                        None, None, None), "spmv_coo_symmetrize")
+    row = np.empty(z.value, np.int32)
+    col = np.empty(z.value, np.int32)
+    val = np.empty(z.value, np.float64)
+    _check_host(lib.spmv_coo_symmetrize(m.n_rows, m.nnz, _ptr(m.row), _ptr(m.col), _ptr(m.val), ctypes.byref(z),
+                                        _ptr(row), _ptr(col), _ptr(val)), "spmv_coo_symmetrize")
+    return Coo(m.n_rows, m.n_cols, row, col, val, False, (m.label + " (symmetric, expanded)").strip())
+
+
+def cpu_csr_sym(n: int, ptr, col, val, x: np.ndarray, y: np.ndarray) -> None:
+    """Host y = (S + S^T - diag S) x on the half storage (spmv_cpu_csr_sym):
+    x has n entries; y[:n] is overwritten, nothing past it."""
+    for a in (x, y):
+        if not isinstance(a, np.ndarray) or a.dtype != np.float64 or a.ndim != 1 or not a.flags.c_contiguous:
+            raise SpmvError(OTHER_ERROR, "cpu_csr_sym", "x and y must be contiguous 1-D float64 arrays")
+        if a.size < n:
+            raise SpmvError(OTHER_ERROR, "cpu_csr_sym", "x or y too short")
+    _check_host(host_lib().spmv_cpu_csr_sym(n, _ptr(ptr), _ptr(col), _ptr(val), _ptr(x), _ptr(y)), "spmv_cpu_csr_sym")
 
 
 def csr_sort_rows(n_rows: int, ptr, col, val) -> None:
@@ -1103,6 +1151,79 @@ class DeviceMatrix:
         st = stream if stream is not None else torch.cuda.current_stream(here)
         _check(hip_lib().spmv_plan_run_t(self.plan, _ptr(x), _ptr(y), st.cuda_stream),
                f"spmv_plan_run_t ({self.fmt})")
+
+    @property
+    def symmetric_supported(self) -> bool:
+        """prepare_symmetric / run_sym can run this matrix (spmv_plan_symmetric_supported):
+        a CSR plan over a square matrix."""
+        return self.plan is not None and bool(hip_lib().spmv_plan_symmetric_supported(self.plan))
+
+    def prepare_symmetric(self, mode="fused") -> None:
+        """Build what run_sym needs (spmv_plan_prepare_symmetric, build time):
+        "fused" (one pass over the stored half, no second copy, fp64 atomics,
+        not bitwise reproducible), "expand" (A = S + S^T - diag S built on the
+        device and run by the forward kernels, reproducible) or None (free
+        everything)."""
+        if mode not in SYMMETRIC_MODES:
+            raise SpmvError(OTHER_ERROR, "prepare_symmetric", 'mode must be "fused", "expand" or None')
+        if self.plan is None:
+            raise SpmvError(OTHER_ERROR, "prepare_symmetric", f"format {self.fmt} has no plan: no symmetric run")
+        _check(hip_lib().spmv_plan_prepare_symmetric(self.plan, SYMMETRIC_MODES[mode]),
+               f"spmv_plan_prepare_symmetric ({self.fmt})")
+
+    @property
+    def symmetric_info(self) -> dict:
+        """spmv_symmetric_info as a dict; mode is None, "fused" or "expand"."""
+        if self.plan is None:
+            raise SpmvError(OTHER_ERROR, "symmetric_info", f"format {self.fmt} has no plan")
+        info = SymmetricInfo()
+        _check(hip_lib().spmv_plan_get_symmetric_info(self.plan, ctypes.byref(info)), "spmv_plan_get_symmetric_info")
+        out = {k: int(getattr(info, k)) for k in ("cap", "blocks", "window_blocks", "flush_entries", "nnz_expanded",
+                                                  "owned_bytes")}
+        out["mode"] = {v: k for k, v in SYMMETRIC_MODES.items()}[info.mode]
+        out["kernel"] = info.kernel.decode()
+        return out
+
+    def symmetric_arrays(self):
+        """Expand mode: host copies (row_ptr[n+1], col, val) of the CSR of A
+        the plan built on the device (spmv_plan_get_symmetric_arrays)."""
+        if self.plan is None:
+            raise SpmvError(OTHER_ERROR, "symmetric_arrays", f"format {self.fmt} has no plan")
+        lib = hip_lib()
+        p_ptr, p_col, p_val, z = _vp(), _vp(), _vp(), _c_i64()
+        _check(lib.spmv_plan_get_symmetric_arrays(self.plan, ctypes.byref(p_ptr), ctypes.byref(p_col),
+                                                  ctypes.byref(p_val), ctypes.byref(z)),
+               "spmv_plan_get_symmetric_arrays")
+        out = (np.empty(self.n_rows + 1, np.int64), np.empty(z.value, np.int32), np.empty(z.value, np.float64))
+        for host, dptr in zip(out, (p_ptr, p_col, p_val)):
+            if host.nbytes:
+                _check(lib.spmv_download(_ptr(host), dptr, host.nbytes, None), "spmv_download")
+        return out
+
+    def run_sym(self, x, y, stream=None) -> None:
+        """y = (S + S^T - diag S) x on `stream` (spmv_plan_run_sym), S the
+        stored half this matrix holds: x has >= n entries, y[:n] is
+        overwritten.  Needs prepare_symmetric first."""
+        torch = _torch()
+        for t in (x, y):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float64:
+                raise SpmvError(OTHER_ERROR, "run_sym", "x and y must be float64 tensors")
+        if self.n_rows != self.n_cols:
+            raise SpmvError(OTHER_ERROR, "run_sym", "the matrix is not square")
+        if x.numel() < self.n_cols or y.numel() < self.n_rows:
+            raise SpmvError(OTHER_ERROR, "run_sym", "x or y too short")
+        if not (x.is_contiguous() and y.is_contiguous()):
+            raise SpmvError(OTHER_ERROR, "run_sym", "x and y must be contiguous")
+        here = torch.device(self.device)
+        idx = here.index or 0
+        for t in (x, y):
+            if t.device.type != here.type or (t.device.index or 0) != idx:
+                raise SpmvError(OTHER_ERROR, "run_sym", f"x and y must be on {here.type}:{idx}")
+        if self.plan is None:
+            raise SpmvError(OTHER_ERROR, "run_sym", f"format {self.fmt} has no plan: no symmetric run")
+        st = stream if stream is not None else torch.cuda.current_stream(here)
+        _check(hip_lib().spmv_plan_run_sym(self.plan, _ptr(x), _ptr(y), st.cuda_stream),
+               f"spmv_plan_run_sym ({self.fmt})")
 
     @property
     def transpose_multi_info(self) -> dict:
