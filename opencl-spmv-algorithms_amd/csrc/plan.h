@@ -1,10 +1,47 @@
 // plan.h — struct spmv_plan, private to the library: built and run by
-// plan.hip, extended with the transposed path (y = A^T x) by transpose.hip.
+// plan.hip, which also holds the balanced multi-vector mode
+// (spmv_plan_prepare_multi); extended with the transposed product y = A^T x by
+// transpose.hip and with the symmetric product by symmetric.hip.  Each of the
+// three modes keeps what its prepare built in one state struct, freed by
+// "free the pointers, destroy the inner plan, assign a fresh struct", and
+// counts its bytes in that struct's `owned`, never in the plan's.
 #pragma once
+
+#include <stdio.h>
 
 #include "common.h"
 
 namespace spmv {
+// What spmv_plan_prepare_transpose built (transpose.hip).  The old mode is
+// freed before the new one is built (peak memory: one mode), so a failed
+// prepare leaves SPMV_T_NONE.
+struct TransposeState {
+    int32_t mode = 0;         // enum spmv_transpose_mode
+    int32_t xcap = 0;         // scatter: LDS accumulator entries of a run (widest window that fits the cap)
+    int64_t blocks = 0, lds_blocks = 0, flush = 0;
+    // scatter, multi-vector run (csr_t_multi_kernel of width 1, 2, 4, 8): the
+    // widest column span that fits the width's cap, and the blocks that fit
+    int32_t mxcap[4] = {0, 0, 0, 0};
+    int64_t mlds[4] = {0, 0, 0, 0};
+    void *win = nullptr;      // scatter: int2 {lo, hi} column range per row block
+    int64_t *ptr = nullptr;   // copy: A^T as CSR (ptr[n_cols+1], col/val[nnz])
+    int32_t *col = nullptr;
+    double *val = nullptr;
+    spmv_plan *inner = nullptr;  // copy: the forward CSR plan over A^T
+    size_t owned = 0;
+};
+
+// What spmv_plan_prepare_multi built (plan.hip): built aside and swapped in
+// on success, so a failed prepare leaves the plan as it was.
+struct MultiState {
+    int32_t mode = 0;                // enum spmv_multi_mode
+    spmv_multi_opts req = {-1, -1};  // the options as asked for (-1: the rule)
+    int32_t seg_len = 0;             // resolved; the resolved long_len is bal.long_len
+    int64_t long_entries = 0;
+    MultiBalance bal;                // counts, device tables, partial workspace (plan-owned)
+    size_t owned = 0;
+};
+
 // What spmv_plan_prepare_symmetric built (symmetric.hip).  A new mode is
 // built into a fresh SymState and swapped in on success, so a failed prepare
 // leaves the plan as it was.
@@ -58,32 +95,9 @@ struct spmv_plan {
     size_t owned = 0;
     char kernel[64] = "";
     char desc[320] = "";
-    // the transposed path (spmv_plan_prepare_transpose, transpose.hip); its
-    // bytes are counted in t_owned, never in `owned`
-    int32_t t_mode = 0;        // enum spmv_transpose_mode
-    int32_t t_xcap = 0;        // scatter: LDS accumulator entries of a run (widest window that fits the cap)
-    int64_t t_blocks = 0, t_lds_blocks = 0, t_flush = 0;
-    // scatter, multi-vector run (csr_t_multi_kernel of width 1, 2, 4, 8): the
-    // widest column span that fits the width's cap, and the blocks that fit
-    int32_t t_mxcap[4] = {0, 0, 0, 0};
-    int64_t t_mlds[4] = {0, 0, 0, 0};
-    void *t_win = nullptr;     // scatter: int2 {lo, hi} column range per row block
-    int64_t *t_ptr = nullptr;  // copy: A^T as CSR (t_ptr[n_cols+1], t_col/t_val[nnz])
-    int32_t *t_col = nullptr;
-    double *t_val = nullptr;
-    spmv_plan *t_inner = nullptr;  // copy: the forward CSR plan over A^T
-    size_t t_owned = 0;
-    // the balanced multi-vector mode (spmv_plan_prepare_multi, plan.hip); its
-    // bytes are counted in m_owned, never in `owned` or t_owned
-    int32_t m_mode = 0;                // enum spmv_multi_mode
-    spmv_multi_opts m_req = {-1, -1};  // the options as asked for (-1: the rule)
-    int32_t m_seg_len = 0;             // resolved; the resolved long_len is m_bal.long_len
-    int64_t m_long_entries = 0;
-    spmv::MultiBalance m_bal;          // counts, device tables, partial workspace (plan-owned)
-    size_t m_owned = 0;
-    // the symmetric product (spmv_plan_prepare_symmetric, symmetric.hip); its
-    // bytes are counted in sym.owned, never in `owned`, t_owned or m_owned
-    spmv::SymState sym;
+    spmv::TransposeState t;  // the transposed product (spmv_plan_prepare_transpose)
+    spmv::MultiState m;      // the balanced multi-vector mode (spmv_plan_prepare_multi)
+    spmv::SymState sym;      // the symmetric product (spmv_plan_prepare_symmetric)
 };
 
 namespace spmv {
@@ -93,4 +107,42 @@ void plan_multi_free(spmv_plan *p);
 void plan_transpose_free(spmv_plan *p);
 // frees what spmv_plan_prepare_symmetric built (the plan's device is current)
 void plan_symmetric_free(spmv_plan *p);
+
+// ---- the lifecycle vocabulary of the plans and their three modes (plan.hip)
+// One counted device allocation: hipMalloc of `bytes` (16 at the least) into
+// *dst, `bytes` added to *owned; `who` = the entry point, for the message.
+int owned_alloc(void **dst, size_t bytes, size_t *owned, const char *who);
+
+// A step failed with rc: runs `cleanup`, which may overwrite the last error,
+// and returns rc with the step's own message.
+template <typename F>
+int fail_after(int rc, F &&cleanup)
+{
+    char keep[512];
+    snprintf(keep, sizeof keep, "%s", spmv_last_error());
+    cleanup();
+    return fail_msg(rc, keep);
+}
+
+// A TransposeState or SymState: the device arrays freed, the inner plan
+// destroyed, a fresh struct assigned.
+template <typename S>
+void mode_state_free(S *s)
+{
+    if (s->inner)
+        spmv_plan_destroy(s->inner);
+    for (void *q : {s->win, (void *)s->ptr, (void *)s->col, (void *)s->val})
+        if (q)
+            (void)hipFree(q);
+    *s = S{};
+}
+
+// The blocks of a downloaded {lo, hi} table (windows_download) that have
+// entries and span at most `cap` columns: their number, the sum of their spans
+// and the widest of them.
+struct WindowTally {
+    int64_t blocks = 0, spans = 0;
+    int32_t widest = 0;
+};
+WindowTally windows_tally(const int2 *h, int64_t n, int32_t cap);
 }  // namespace spmv

@@ -95,12 +95,35 @@ static void multi_tables_free(MultiBalance &m)
 
 void plan_multi_free(spmv_plan *p)
 {
-    multi_tables_free(p->m_bal);
-    p->m_mode = SPMV_M_NONE;
-    p->m_req = {-1, -1};
-    p->m_seg_len = 0;
-    p->m_long_entries = 0;
-    p->m_owned = 0;
+    multi_tables_free(p->m.bal);
+    p->m = MultiState{};
+}
+
+int owned_alloc(void **dst, size_t bytes, size_t *owned, const char *who)
+{
+    *dst = nullptr;
+    hipError_t e = hipMalloc(dst, bytes > 0 ? bytes : 16);
+    if (e != hipSuccess) {
+        char where[96];
+        snprintf(where, sizeof where, "%s: hipMalloc", who);
+        return fail(SPMV_PROGRAM_ERROR, where, e);
+    }
+    *owned += bytes;
+    return SPMV_SUCCESS;
+}
+
+WindowTally windows_tally(const int2 *h, int64_t n, int32_t cap)
+{
+    WindowTally t;
+    for (int64_t b = 0; b < n; ++b) {
+        const int64_t span = (int64_t)h[b].y - h[b].x + 1;
+        if (span > 0 && span <= cap) {
+            t.blocks++;
+            t.spans += span;
+            t.widest = span > t.widest ? (int32_t)span : t.widest;
+        }
+    }
+    return t;
 }
 
 }  // namespace spmv
@@ -109,15 +132,7 @@ using namespace spmv;
 
 namespace {
 
-int plan_alloc(spmv_plan *p, void **dst, size_t bytes)
-{
-    *dst = nullptr;
-    hipError_t e = hipMalloc(dst, bytes > 0 ? bytes : 16);
-    if (e != hipSuccess)
-        return fail(SPMV_PROGRAM_ERROR, "spmv_plan: hipMalloc", e);
-    p->owned += bytes;
-    return SPMV_SUCCESS;
-}
+int plan_alloc(spmv_plan *p, void **dst, size_t bytes) { return owned_alloc(dst, bytes, &p->owned, "spmv_plan"); }
 
 int plan_upload(spmv_plan *p, void **dst, const void *src, size_t bytes)
 {
@@ -234,14 +249,11 @@ spmv_plan *new_plan(int fmt, spmv_dims d, const spmv_plan_opts *o)
 
 int finish(spmv_plan *p, int rc, spmv_plan **out)
 {
-    if (rc != SPMV_SUCCESS) {
-        const char *msg = spmv_last_error();
-        char keep[512];
-        snprintf(keep, sizeof keep, "%s", msg);
-        spmv_plan_destroy(p);
-        *out = nullptr;
-        return fail_msg(rc, keep);
-    }
+    if (rc != SPMV_SUCCESS)
+        return fail_after(rc, [&] {
+            spmv_plan_destroy(p);
+            *out = nullptr;
+        });
     *out = p;
     return SPMV_SUCCESS;
 }
@@ -857,7 +869,7 @@ int spmv_plan_run_multi(const spmv_plan *p, int32_t k, const double *X, int64_t 
     switch (p->fmt) {
     case SPMV_FMT_CSR:
         return launch_csr_multi(d, p->lanes, p->ptr, p->col, p->val, k, X, ldx, Y, ldy,
-                                p->m_mode == SPMV_M_BALANCED ? &p->m_bal : nullptr);
+                                p->m.mode == SPMV_M_BALANCED ? &p->m.bal : nullptr);
     case SPMV_FMT_ELL:
         return launch_slot_multi(d, false, p->ki, 0, 0, nullptr, nullptr, p->K, p->ld, p->col, p->val, k, X, ldx, Y, ldy);
     default:
@@ -880,11 +892,11 @@ void spmv_multi_opts_init(spmv_multi_opts *o)
 static int multi_upload(const spmv_plan *p, const void **dst, const void *src, size_t bytes, size_t *owned)
 {
     void *q = nullptr;
-    hipError_t e = hipMalloc(&q, bytes > 0 ? bytes : 16);
-    if (e != hipSuccess)
-        return fail(SPMV_PROGRAM_ERROR, "spmv_plan_prepare_multi: hipMalloc", e);
+    const int rc = owned_alloc(&q, bytes, owned, "spmv_plan_prepare_multi");
+    if (rc != SPMV_SUCCESS)
+        return rc;
     *dst = q;
-    *owned += bytes;
+    hipError_t e;
     if (src && bytes > 0 &&
         (e = hipMemcpyAsync(q, src, bytes, hipMemcpyHostToDevice, (hipStream_t)p->d.stream)) != hipSuccess)
         return fail(SPMV_PROGRAM_ERROR, "spmv_plan_prepare_multi: upload", e);
@@ -966,41 +978,33 @@ int spmv_plan_prepare_multi(spmv_plan *p, int mode, const spmv_multi_opts *o)
     SPMV_GUARD(p->d);
     const hipStream_t st = (hipStream_t)p->d.stream;
     if (mode == SPMV_M_NONE) {
-        if (p->m_mode == SPMV_M_NONE)
+        if (p->m.mode == SPMV_M_NONE)
             return SPMV_SUCCESS;
         // a balanced run may still be in flight on the build stream
         if (hipStreamSynchronize(st) != hipSuccess)
             return fail_msg(SPMV_PROGRAM_ERROR, "spmv_plan_prepare_multi: synchronise");
         plan_multi_free(p);
-        return p->t_inner ? spmv_plan_prepare_multi(p->t_inner, SPMV_M_NONE, nullptr) : SPMV_SUCCESS;
+        return p->t.inner ? spmv_plan_prepare_multi(p->t.inner, SPMV_M_NONE, nullptr) : SPMV_SUCCESS;
     }
-    if (mode == p->m_mode && req.long_len == p->m_req.long_len && req.seg_len == p->m_req.seg_len)
+    if (mode == p->m.mode && req.long_len == p->m.req.long_len && req.seg_len == p->m.req.seg_len)
         return SPMV_SUCCESS;
     const int64_t rule_long = (int64_t)kMultiLongPerLane * p->lanes;
     const int32_t long_len = req.long_len >= 0 ? req.long_len : (int32_t)rule_long;
     const int32_t seg_len = req.seg_len >= 1 ? req.seg_len : kMultiSegLen;
-    MultiBalance m;
-    int64_t long_entries = 0;
-    size_t owned = 0;
-    int rc = multi_build(p, long_len, seg_len, &m, &long_entries, &owned);
+    MultiState next;
+    int rc = multi_build(p, long_len, seg_len, &next.bal, &next.long_entries, &next.owned);
     // copy mode: the inner plan over A^T follows (it keeps its state when refused)
-    if (rc == SPMV_SUCCESS && p->t_inner)
-        rc = spmv_plan_prepare_multi(p->t_inner, mode, &req);
+    if (rc == SPMV_SUCCESS && p->t.inner)
+        rc = spmv_plan_prepare_multi(p->t.inner, mode, &req);
     if (rc == SPMV_SUCCESS && hipStreamSynchronize(st) != hipSuccess)
         rc = fail_msg(SPMV_PROGRAM_ERROR, "spmv_plan_prepare_multi: synchronise");
-    if (rc != SPMV_SUCCESS) {
-        char keep[512];
-        snprintf(keep, sizeof keep, "%s", spmv_last_error());
-        multi_tables_free(m);
-        return fail_msg(rc, keep);
-    }
+    if (rc != SPMV_SUCCESS)  // the plan stays as it was
+        return fail_after(rc, [&] { multi_tables_free(next.bal); });
+    next.mode = mode;
+    next.req = req;
+    next.seg_len = seg_len;
     plan_multi_free(p);  // the previous options' tables (the stream is idle)
-    p->m_mode = mode;
-    p->m_req = req;
-    p->m_seg_len = seg_len;
-    p->m_long_entries = long_entries;
-    p->m_bal = m;
-    p->m_owned = owned;
+    p->m = next;
     return SPMV_SUCCESS;
 }
 
@@ -1009,22 +1013,23 @@ int spmv_plan_get_multi_info(const spmv_plan *p, spmv_multi_info *info)
     if (!p || !info)
         return fail_msg(SPMV_OTHER_ERROR, "spmv_plan_get_multi_info: NULL argument");
     memset(info, 0, sizeof *info);
-    info->mode = p->m_mode;
-    if (p->m_mode == SPMV_M_NONE)
+    const MultiState &m = p->m;
+    info->mode = m.mode;
+    if (m.mode == SPMV_M_NONE)
         return SPMV_SUCCESS;
-    info->long_len = p->m_bal.long_len;
-    info->seg_len = p->m_seg_len;
-    info->long_rows = p->m_bal.n_long;
-    info->segments = p->m_bal.n_seg;
-    info->slots = p->m_bal.n_slots;
-    info->long_entries = p->m_long_entries;
-    info->owned_bytes = (int64_t)p->m_owned;
-    if (p->t_inner) {
-        info->t_long_rows = p->t_inner->m_bal.n_long;
-        info->t_segments = p->t_inner->m_bal.n_seg;
-        info->t_owned_bytes = (int64_t)p->t_inner->m_owned;
+    info->long_len = m.bal.long_len;
+    info->seg_len = m.seg_len;
+    info->long_rows = m.bal.n_long;
+    info->segments = m.bal.n_seg;
+    info->slots = m.bal.n_slots;
+    info->long_entries = m.long_entries;
+    info->owned_bytes = (int64_t)m.owned;
+    if (p->t.inner) {
+        info->t_long_rows = p->t.inner->m.bal.n_long;
+        info->t_segments = p->t.inner->m.bal.n_seg;
+        info->t_owned_bytes = (int64_t)p->t.inner->m.owned;
     }
-    snprintf(info->kernel, sizeof info->kernel, "%s", p->m_bal.n_seg > 0 ? "csr_multi_long_kernel" : "csr_multi_kernel");
+    snprintf(info->kernel, sizeof info->kernel, "%s", m.bal.n_seg > 0 ? "csr_multi_long_kernel" : "csr_multi_kernel");
     return SPMV_SUCCESS;
 }
 

@@ -7,8 +7,8 @@
 // listed (spmv_coo_symmetrize, spmv_host.h).  Skew-symmetric and hermitian
 // meanings are out of scope.  Two modes, chosen at build time:
 //   SPMV_S_FUSED   one pass over the half storage, no second copy.  The
-//       geometry of csr_t_window_kernel (transpose.hip): one workgroup per
-//       block of 128 rows streams the block's entries once.  The block's
+//       row-block core (rowblock.h): one workgroup per block of 128 rows
+//       streams the block's entries once.  The block's
 //       UNION window {lo, hi}, its column range joined with its own rows, is
 //       recorded at build time.  A union of at most 2,048 columns: x[lo..hi]
 //       is staged in LDS beside an accumulator of the same span; entry
@@ -35,15 +35,13 @@
 
 #include "common.h"
 #include "plan.h"
+#include "rowblock.h"
 
 namespace spmv {
 
-constexpr int kSRows = 128;       // rows per block
 constexpr int32_t kSCap = 2048;   // widest union window summed in LDS (x + accumulator: 32 KiB)
-constexpr int kSPtr = kSRows + 2; // LDS slots of the block's kSRows + 1 row offsets (a 16-byte multiple)
-constexpr int kSU = 4;            // entries in flight per thread
 
-// Union window {lo, hi} of every block of kSRows rows: the range of its
+// Union window {lo, hi} of every block of kRbRows rows: the range of its
 // columns inside [0, n) joined with its own rows ({0, -1}: no such entry).  A
 // column outside [0, n) is left out here and dropped by the run's checks.
 __global__ __launch_bounds__(kBlock) void csr_sym_range_kernel(int64_t n, int64_t nnz,
@@ -51,8 +49,8 @@ __global__ __launch_bounds__(kBlock) void csr_sym_range_kernel(int64_t n, int64_
                                                                const int32_t *__restrict__ col,
                                                                int2 *__restrict__ win)
 {
-    const int64_t r0 = (int64_t)blockIdx.x * kSRows;
-    const int64_t r1 = r0 + kSRows < n ? r0 + kSRows : n;
+    const int64_t r0 = (int64_t)blockIdx.x * kRbRows;
+    const int64_t r1 = r0 + kRbRows < n ? r0 + kRbRows : n;
     int lo = INT32_MAX, hi = INT32_MIN;
     if (nnz > 0)
         for (int64_t e = ptr[r0] + threadIdx.x, e1 = ptr[r1]; e < e1; e += kBlock) {
@@ -72,25 +70,6 @@ __global__ __launch_bounds__(kBlock) void csr_sym_range_kernel(int64_t n, int64_
     }
 }
 
-// The block's entries [s_ptr[0], s_ptr[nr]) as one coalesced non-temporal
-// stream (thread t takes entries t, t + 256, ... with kSU in flight); the row
-// of an entry is the last r with s_ptr[r] <= e, a 7-step search in LDS.
-// WIN = true: xs = x[lo .. lo + bound) and acc of the same span, both LDS;
-// an entry whose row or column lies outside the window is dropped whole.
-// WIN = false: xs = x of the block's rows and acc their 128 sums, both LDS;
-// x[c] comes from global memory, the mirrored product goes straight into
-// y[c]; bound = n, a column outside [0, n) is dropped whole.
-// SPMV_SYM_ROW_REDUCE = 1 (the default): the row products of a wave's 64
-// consecutive entries are summed per row across the wave before they reach the
-// accumulator; 0 (an A/B build, -DSPMV_SYM_ROW_REDUCE=0): every entry adds its
-// own row product.  Measured cold on the cant-like lower triangle
-// (profiles/symmetric/README.md): 0.0259 against 0.0268 ms on one matrix,
-// 0.302 against 0.379 ms on the 32-copy batch.
-#ifndef SPMV_SYM_ROW_REDUCE
-#define SPMV_SYM_ROW_REDUCE 1
-#endif
-
-#if SPMV_SYM_ROW_REDUCE
 // A wave's 64 consecutive entries belong to few rows (32 entries per stored
 // cant-like row), so their row products would meet at few accumulator words
 // and the LDS adds of one instruction would run one after another.  Each run
@@ -112,20 +91,24 @@ __device__ __forceinline__ void wave_run_add(double *acc, int key, double p)
         atomicAdd(&acc[key], p);
 }
 
-// sym_block with uniform loops over the workgroup (the shuffles need whole
-// waves): in the last partial step a lane past the end carries key -1.
+// The per-entry body of the fused run over the block's stream (rb_stream,
+// uniform loops: the shuffles need whole waves; in the last partial step a
+// lane past the end carries key -1).
+// WIN = true: xs = x[lo .. lo + bound) and acc of the same span, both LDS;
+// an entry whose row or column lies outside the window is dropped whole.
+// WIN = false: xs = x of the block's rows and acc their 128 sums, both LDS;
+// x[c] comes from global memory, the mirrored product goes straight into
+// y[c]; bound = n, a column outside [0, n) is dropped whole.
+// The row products of a wave's 64 consecutive entries are summed per row
+// across the wave before they reach the accumulator (wave_run_add).
 template <bool WIN>
 __device__ __forceinline__ void sym_block(const int64_t *s_ptr, int nr, int64_t r0, const int32_t *__restrict__ col,
                                           const double *__restrict__ val, const double *__restrict__ x,
                                           double *__restrict__ y, const double *xs, double *acc, int32_t lo,
                                           uint32_t bound)
 {
-    auto add = [&](bool live, int64_t e, int32_t c, double v) {
-        int r = 0;
-#pragma unroll
-        for (int step = kSRows / 2; step > 0; step >>= 1)
-            if (r + step < nr && s_ptr[r + step] <= e)
-                r += step;
+    rb_stream<true>(s_ptr, nr, col, val, [&](bool live, int64_t e, int32_t c, double v) {
+        const int r = rb_row_of(s_ptr, nr, e);
         int key = -1;
         double p = 0.0;
         if constexpr (WIN) {
@@ -146,86 +129,13 @@ __device__ __forceinline__ void sym_block(const int64_t *s_ptr, int nr, int64_t 
             }
         }
         wave_run_add(acc, key, p);
-    };
-    const int64_t end = s_ptr[nr];
-    int64_t e0 = s_ptr[0];  // uniform
-    for (; e0 + kSU * kBlock <= end; e0 += kSU * kBlock) {
-        const int64_t e = e0 + (int64_t)threadIdx.x;
-        int32_t c[kSU];
-        double v[kSU];
-#pragma unroll
-        for (int u = 0; u < kSU; ++u) {
-            c[u] = stream_load<true>(col + e + u * kBlock);
-            v[u] = stream_load<true>(val + e + u * kBlock);
-        }
-#pragma unroll
-        for (int u = 0; u < kSU; ++u)
-            add(true, e + u * kBlock, c[u], v[u]);
-    }
-    for (; e0 < end; e0 += kBlock) {
-        const int64_t e = e0 + (int64_t)threadIdx.x;
-        const bool live = e < end;
-        int32_t c = -1;
-        double v = 0.0;
-        if (live) {
-            c = stream_load<true>(col + e);
-            v = stream_load<true>(val + e);
-        }
-        add(live, e, c, v);
-    }
+    });
 }
-#else
-template <bool WIN>
-__device__ __forceinline__ void sym_block(const int64_t *s_ptr, int nr, int64_t r0, const int32_t *__restrict__ col,
-                                          const double *__restrict__ val, const double *__restrict__ x,
-                                          double *__restrict__ y, const double *xs, double *acc, int32_t lo,
-                                          uint32_t bound)
-{
-    auto add = [&](int64_t e, int32_t c, double v) {
-        int r = 0;
-#pragma unroll
-        for (int step = kSRows / 2; step > 0; step >>= 1)
-            if (r + step < nr && s_ptr[r + step] <= e)
-                r += step;
-        if constexpr (WIN) {
-            const uint32_t jr = (uint32_t)(r0 + r) - (uint32_t)lo;
-            const uint32_t jc = (uint32_t)c - (uint32_t)lo;
-            if (jr < bound && jc < bound) {
-                atomicAdd(&acc[jr], v * xs[jc]);
-                if (jc != jr)
-                    atomicAdd(&acc[jc], v * xs[jr]);
-            }
-        } else {
-            if ((uint32_t)c < bound) {
-                atomicAdd(&acc[r], v * x[c]);
-                if ((int64_t)c != r0 + r)
-                    unsafeAtomicAdd(&y[c], v * xs[r]);
-            }
-        }
-    };
-    const int64_t end = s_ptr[nr];
-    int64_t e = s_ptr[0] + (int64_t)threadIdx.x;
-    for (; e + (kSU - 1) * kBlock < end; e += kSU * kBlock) {
-        int32_t c[kSU];
-        double v[kSU];
-#pragma unroll
-        for (int u = 0; u < kSU; ++u) {
-            c[u] = stream_load<true>(col + e + u * kBlock);
-            v[u] = stream_load<true>(val + e + u * kBlock);
-        }
-#pragma unroll
-        for (int u = 0; u < kSU; ++u)
-            add(e + u * kBlock, c[u], v[u]);
-    }
-    for (; e < end; e += kBlock)
-        add(e, stream_load<true>(col + e), stream_load<true>(val + e));
-}
-#endif
 
-// One workgroup per block of kSRows rows.  LDS: the block's kSRows + 1 row
+// One workgroup per block of kRbRows rows.  LDS: the block's kRbRows + 1 row
 // offsets, then two arrays of the union's span (x window, accumulator) when
-// it is at most `cap`, else two arrays of kSRows (the rows' x, their sums).
-// The launch provides kSPtr + 2 * max(widest fitting span, kSRows) doubles.
+// it is at most `cap`, else two arrays of kRbRows (the rows' x, their sums).
+// The launch provides kRbPtr + 2 * max(widest fitting span, kRbRows) doubles.
 __global__ __launch_bounds__(kBlock) void csr_sym_window_kernel(int64_t n, const int64_t *__restrict__ ptr,
                                                                 const int32_t *__restrict__ col,
                                                                 const double *__restrict__ val,
@@ -234,20 +144,18 @@ __global__ __launch_bounds__(kBlock) void csr_sym_window_kernel(int64_t n, const
 {
     extern __shared__ double s_mem[];
     int64_t *s_ptr = reinterpret_cast<int64_t *>(s_mem);
-    double *xs = s_mem + kSPtr;
+    double *xs = s_mem + kRbPtr;
     const int tid = (int)threadIdx.x;
-    const int2 w = win[blockIdx.x];
-    const int span = w.y - w.x + 1;  // <= 0: a block without entries
-    if (span <= 0)                   // uniform per workgroup
+    RowBlock b;
+    if (!rb_open(n, ptr, win, s_ptr, &b))
         return;
-    const int64_t r0 = (int64_t)blockIdx.x * kSRows;
-    const int nr = (int)(n - r0 < kSRows ? n - r0 : kSRows);
+    const int2 w = b.w;
+    const int span = b.span, nr = b.nr;
+    const int64_t r0 = b.r0;
     // a window that does not hold the block's rows or leaves [0, n) is not one
     // this plan recorded: nothing is read or written through it
     if (w.x < 0 || w.y >= n || w.x > r0 || w.y < r0 + nr - 1)
         return;
-    for (int i = tid; i <= nr; i += kBlock)
-        s_ptr[i] = ptr[r0 + i];
     if (span <= cap) {
         double *acc = xs + span;
         copy_window(xs, x, w.x, span);
@@ -256,16 +164,10 @@ __global__ __launch_bounds__(kBlock) void csr_sym_window_kernel(int64_t n, const
         __syncthreads();
         sym_block<true>(s_ptr, nr, r0, col, val, x, y, xs, acc, w.x, (uint32_t)span);
         __syncthreads();
-        // the flush: consecutive lanes, consecutive columns; sums still exactly
-        // 0.0 add nothing to the zeroed y
-        for (int j = tid; j < span; j += kBlock) {
-            const double s = acc[j];
-            if (s != 0.0)
-                unsafeAtomicAdd(&y[w.x + j], s);
-        }
+        rb_flush(acc, span, y, w.x);
         return;
     }
-    double *acc = xs + kSRows;
+    double *acc = xs + kRbRows;
     if (tid < nr) {
         xs[tid] = x[r0 + tid];
         acc[tid] = 0.0;
@@ -358,34 +260,19 @@ struct Scratch {
 
 int s_alloc(SymState *s, void **dst, size_t bytes)
 {
-    *dst = nullptr;
-    hipError_t e = hipMalloc(dst, bytes > 0 ? bytes : 16);
-    if (e != hipSuccess)
-        return fail(SPMV_PROGRAM_ERROR, "spmv_plan_prepare_symmetric: hipMalloc", e);
-    s->owned += bytes;
-    return SPMV_SUCCESS;
-}
-
-void state_free(SymState *s)
-{
-    if (s->inner)
-        spmv_plan_destroy(s->inner);
-    for (void *q : {s->win, (void *)s->ptr, (void *)s->col, (void *)s->val})
-        if (q)
-            (void)hipFree(q);
-    *s = SymState{};
+    return owned_alloc(dst, bytes, &s->owned, "spmv_plan_prepare_symmetric");
 }
 
 size_t fused_lds(int32_t xcap)
 {
-    return (size_t)(kSPtr + 2 * (xcap > kSRows ? xcap : kSRows)) * sizeof(double);
+    return (size_t)(kRbPtr + 2 * (xcap > kRbRows ? xcap : kRbRows)) * sizeof(double);
 }
 
 int prepare_fused(const spmv_plan *p, SymState *s)
 {
     const spmv_dims &d = p->d;
     const hipStream_t st = (hipStream_t)d.stream;
-    const int64_t blocks = (d.n_rows + kSRows - 1) / kSRows;
+    const int64_t blocks = (d.n_rows + kRbRows - 1) / kRbRows;
     s->blocks = blocks;
     if (blocks == 0)  // a run does nothing
         return SPMV_SUCCESS;
@@ -398,19 +285,15 @@ int prepare_fused(const spmv_plan *p, SymState *s)
     int2 *h = nullptr;
     if ((rc = windows_download(s->win, blocks, st, &h, "spmv_plan_prepare_symmetric")) != SPMV_SUCCESS)
         return rc;
-    for (int64_t b = 0; b < blocks; ++b) {
-        const int64_t span = (int64_t)h[b].y - h[b].x + 1;
-        if (span <= 0)
-            continue;
-        if (span <= kSCap) {
-            s->win_blocks++;
-            s->flush += span;
-            s->xcap = span > s->xcap ? (int32_t)span : s->xcap;
-        } else {
-            const int64_t r0 = b * kSRows;
-            s->flush += d.n_rows - r0 < kSRows ? d.n_rows - r0 : kSRows;
+    const WindowTally fit = windows_tally(h, blocks, kSCap);
+    s->win_blocks = fit.blocks;
+    s->flush = fit.spans;
+    s->xcap = fit.widest;
+    for (int64_t b = 0; b < blocks; ++b)  // a wider union flushes the sums of the block's rows
+        if ((int64_t)h[b].y - h[b].x + 1 > kSCap) {
+            const int64_t r0 = b * kRbRows;
+            s->flush += d.n_rows - r0 < kRbRows ? d.n_rows - r0 : kRbRows;
         }
-    }
     free(h);
     return SPMV_SUCCESS;
 }
@@ -494,7 +377,7 @@ int launch_fused(const spmv_plan *p, const double *x, double *y, hipStream_t st)
 
 }  // namespace
 
-void plan_symmetric_free(spmv_plan *p) { state_free(&p->sym); }
+void plan_symmetric_free(spmv_plan *p) { mode_state_free(&p->sym); }
 
 }  // namespace spmv
 
@@ -530,21 +413,19 @@ int spmv_plan_prepare_symmetric(spmv_plan *p, int mode)
         // runs may come on any stream: everything is complete when this returns
         if (rc == SPMV_SUCCESS && hipStreamSynchronize(st) != hipSuccess)
             rc = fail_msg(SPMV_PROGRAM_ERROR, "spmv_plan_prepare_symmetric: synchronise");
-        if (rc != SPMV_SUCCESS) {  // the plan stays as it was
-            char keep[512];
-            snprintf(keep, sizeof keep, "%s", spmv_last_error());
-            (void)hipStreamSynchronize(st);
-            state_free(&next);
-            return fail_msg(rc, keep);
-        }
+        if (rc != SPMV_SUCCESS)  // the plan stays as it was
+            return fail_after(rc, [&] {
+                (void)hipStreamSynchronize(st);
+                mode_state_free(&next);
+            });
         next.mode = mode;
     }
     // a run of the old mode may still be in flight on the build stream
     if (p->sym.mode != SPMV_S_NONE && hipStreamSynchronize(st) != hipSuccess) {
-        state_free(&next);
+        mode_state_free(&next);
         return fail_msg(SPMV_PROGRAM_ERROR, "spmv_plan_prepare_symmetric: synchronise");
     }
-    state_free(&p->sym);
+    mode_state_free(&p->sym);
     p->sym = next;
     return SPMV_SUCCESS;
 }

@@ -24,37 +24,33 @@
 // mode was prepared: copy is spmv_plan_run_multi on the inner plan; scatter is
 // csr_t_multi_kernel<KV>, the window kernel's geometry with KV vectors per
 // pass and an LDS accumulator of span * KV sums (below).
+//
+// Block prologue, entry stream, row search and flush: rowblock.h.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
 #include "common.h"
 #include "plan.h"
+#include "rowblock.h"
 
 namespace spmv {
 
-constexpr int kTRows = 128;       // rows per block (the forward x-window default)
 constexpr int32_t kTCap = 2048;   // LDS accumulator entries per workgroup (16 KiB)
-constexpr int kTPtr = kTRows + 2; // LDS slots of the block's kTRows + 1 row offsets (a 16-byte multiple)
-constexpr int kTU = 4;            // entries in flight per thread
 
-// column range {lo, hi} of every block of kTRows rows ({0, -1}: no entries)
+// column range {lo, hi} of every block of kRbRows rows ({0, -1}: no entries)
 __global__ __launch_bounds__(kBlock) void csr_t_range_kernel(int64_t n_rows, const int64_t *__restrict__ ptr,
                                                              const int32_t *__restrict__ col, int2 *__restrict__ win)
 {
-    const int64_t r0 = (int64_t)blockIdx.x * kTRows;
-    const int64_t r1 = r0 + kTRows < n_rows ? r0 + kTRows : n_rows;
+    const int64_t r0 = (int64_t)blockIdx.x * kRbRows;
+    const int64_t r1 = r0 + kRbRows < n_rows ? r0 + kRbRows : n_rows;
     const int2 r = block_col_range(col, ptr[r0], ptr[r1]);
     if (threadIdx.x == 0)
         win[blockIdx.x] = r;
 }
 
-// The block's entries [s_ptr[0], s_ptr[nr]) as ONE coalesced stream: thread t
-// takes entries t, t + 256, ... with kTU of them in flight, whatever the row
-// lengths (a lane group per row waits out one memory round trip per row: 39 us
-// instead of 28 on the cant-like matrix, profiles/transpose/README.md).  The
-// row of an entry is the last r with s_ptr[r] <= e, a fixed-depth binary
-// search of the offsets in LDS; x of the block's rows is staged in LDS too.
+// The per-entry body of the single-vector scatter over the block's stream
+// (rb_stream, per-thread loops); x of the block's rows is staged in LDS.
 // LDS = true: val * x[row] is added to acc[col - lo] (ds_add_f64); false:
 // straight into y[col] (global_atomic_add_f64, no return).  Every destination
 // is bounds-checked against the recorded range (LDS) or n_cols (global): a
@@ -64,13 +60,8 @@ __device__ __forceinline__ void t_scatter_block(const int64_t *s_ptr, const doub
                                                 const int32_t *__restrict__ col, const double *__restrict__ val,
                                                 double *__restrict__ y, double *acc, int32_t lo, uint32_t bound)
 {
-    auto add = [&](int64_t e, int32_t c, double v) {
-        int r = 0;  // s_ptr[r] <= e < s_ptr[r + span of the search]
-#pragma unroll
-        for (int step = kTRows / 2; step > 0; step >>= 1)
-            if (r + step < nr && s_ptr[r + step] <= e)
-                r += step;
-        const double p = v * s_x[r];
+    rb_stream<false>(s_ptr, nr, col, val, [&](bool, int64_t e, int32_t c, double v) {
+        const double p = v * s_x[rb_row_of(s_ptr, nr, e)];
         if constexpr (LDS) {
             const uint32_t j = (uint32_t)(c - lo);
             if (j < bound)
@@ -79,27 +70,11 @@ __device__ __forceinline__ void t_scatter_block(const int64_t *s_ptr, const doub
             if ((uint32_t)c < bound)
                 unsafeAtomicAdd(&y[c], p);
         }
-    };
-    const int64_t end = s_ptr[nr];
-    int64_t e = s_ptr[0] + (int64_t)threadIdx.x;
-    for (; e + (kTU - 1) * kBlock < end; e += kTU * kBlock) {
-        int32_t c[kTU];
-        double v[kTU];
-#pragma unroll
-        for (int u = 0; u < kTU; ++u) {
-            c[u] = stream_load<true>(col + e + u * kBlock);
-            v[u] = stream_load<true>(val + e + u * kBlock);
-        }
-#pragma unroll
-        for (int u = 0; u < kTU; ++u)
-            add(e + u * kBlock, c[u], v[u]);
-    }
-    for (; e < end; e += kBlock)
-        add(e, stream_load<true>(col + e), stream_load<true>(val + e));
+    });
 }
 
-// One workgroup per block of kTRows rows.  LDS: the block's kTRows + 1 row
-// offsets and its kTRows entries of x, then the accumulator of the block's
+// One workgroup per block of kRbRows rows.  LDS: the block's kRbRows + 1 row
+// offsets and its kRbRows entries of x, then the accumulator of the block's
 // column range when it spans at most `cap` columns.
 __global__ __launch_bounds__(kBlock) void csr_t_window_kernel(int64_t n_rows, int64_t n_cols,
                                                               const int64_t *__restrict__ ptr,
@@ -110,37 +85,26 @@ __global__ __launch_bounds__(kBlock) void csr_t_window_kernel(int64_t n_rows, in
 {
     extern __shared__ double s_mem[];
     int64_t *s_ptr = reinterpret_cast<int64_t *>(s_mem);
-    double *s_x = s_mem + kTPtr;
-    double *acc = s_x + kTRows;
+    double *s_x = s_mem + kRbPtr;
+    double *acc = s_x + kRbRows;
     const int tid = (int)threadIdx.x;
-    const int2 w = win[blockIdx.x];
-    const int span = w.y - w.x + 1;             // <= 0: a block without entries
-    if (span <= 0)                              // uniform per workgroup
+    RowBlock b;
+    if (!rb_open(n_rows, ptr, win, s_ptr, &b))
         return;
-    const bool lds = span <= cap;
-    const int64_t r0 = (int64_t)blockIdx.x * kTRows;
-    const int nr = (int)(n_rows - r0 < kTRows ? n_rows - r0 : kTRows);
-    for (int i = tid; i <= nr; i += kBlock)
-        s_ptr[i] = ptr[r0 + i];
-    if (tid < nr)
-        s_x[tid] = x[r0 + tid];
+    const bool lds = b.span <= cap;
+    if (tid < b.nr)
+        s_x[tid] = x[b.r0 + tid];
     if (lds)
-        for (int j = tid; j < span; j += kBlock)
+        for (int j = tid; j < b.span; j += kBlock)
             acc[j] = 0.0;
     __syncthreads();
     if (!lds) {
-        t_scatter_block<false>(s_ptr, s_x, nr, col, val, y, acc, 0, (uint32_t)n_cols);
+        t_scatter_block<false>(s_ptr, s_x, b.nr, col, val, y, acc, 0, (uint32_t)n_cols);
         return;
     }
-    t_scatter_block<true>(s_ptr, s_x, nr, col, val, y, acc, w.x, (uint32_t)span);
+    t_scatter_block<true>(s_ptr, s_x, b.nr, col, val, y, acc, b.w.x, (uint32_t)b.span);
     __syncthreads();
-    // the flush: consecutive lanes, consecutive columns; sums still exactly
-    // 0.0 add nothing to the zeroed y
-    for (int j = tid; j < span; j += kBlock) {
-        const double s = acc[j];
-        if (s != 0.0)
-            unsafeAtomicAdd(&y[w.x + j], s);
-    }
+    rb_flush(acc, b.span, y, b.w.x);
 }
 
 // ------------------------------------------------- multi-vector scatter
@@ -231,12 +195,11 @@ __device__ __forceinline__ void t_multi_rounds(const double *s_x, double *acc, d
     }
 }
 
-// t_scatter_block for KV vectors: the same coalesced non-temporal stream
-// (thread t loads entries t, t + 256, ... with kTU in flight; every lane its
-// own entry, so the matrix is loaded once) and the same 7-step row search,
-// done once per entry by the lane that loaded it.  The loops are uniform over
-// the workgroup (the DPP moves need whole waves): in the last partial step a
-// lane past the end carries column -1, which every bound check drops.
+// t_scatter_block for KV vectors: the same stream (every lane its own entry,
+// so the matrix is loaded once) and the same row search, done once per entry
+// by the lane that loaded it.  rb_stream's uniform loops (the DPP moves need
+// whole waves): in the last partial step a lane past the end carries column
+// -1, which every bound check drops.
 template <int KV, bool LDS>
 __device__ __forceinline__ void t_multi_block(const int64_t *s_ptr, const double *s_x, int nr,
                                               const int32_t *__restrict__ col, const double *__restrict__ val,
@@ -246,46 +209,15 @@ __device__ __forceinline__ void t_multi_block(const int64_t *s_ptr, const double
     constexpr int P = t_multi_p<KV>();
     constexpr int CPL = KV / P;
     const int j0 = ((int)threadIdx.x % P) * CPL;
-    auto row_of = [&](int64_t e) {
-        int r = 0;
-#pragma unroll
-        for (int step = kTRows / 2; step > 0; step >>= 1)
-            if (r + step < nr && s_ptr[r + step] <= e)
-                r += step;
-        return r;
-    };
-    const int64_t end = s_ptr[nr];
-    int64_t e0 = s_ptr[0];  // uniform
-    for (; e0 + kTU * kBlock <= end; e0 += kTU * kBlock) {
-        const int64_t e = e0 + (int64_t)threadIdx.x;
-        int32_t c[kTU];
-        double v[kTU];
-#pragma unroll
-        for (int u = 0; u < kTU; ++u) {
-            c[u] = stream_load<true>(col + e + u * kBlock);
-            v[u] = stream_load<true>(val + e + u * kBlock);
-        }
-#pragma unroll
-        for (int u = 0; u < kTU; ++u)
-            t_multi_rounds<KV, LDS>(s_x, acc, Y, ldy, lo, bound, live, j0, c[u], v[u], row_of(e + u * kBlock));
-    }
-    for (; e0 < end; e0 += kBlock) {
-        const int64_t e = e0 + (int64_t)threadIdx.x;
-        int32_t c = -1;
-        double v = 0.0;
-        int r = 0;
-        if (e < end) {
-            c = stream_load<true>(col + e);
-            v = stream_load<true>(val + e);
-            r = row_of(e);
-        }
+    rb_stream<true>(s_ptr, nr, col, val, [&](bool mine, int64_t e, int32_t c, double v) {
+        const int r = mine ? rb_row_of(s_ptr, nr, e) : 0;
         t_multi_rounds<KV, LDS>(s_x, acc, Y, ldy, lo, bound, live, j0, c, v, r);
-    }
+    });
 }
 
-// One workgroup per block of kTRows rows, one pass over the block's entries
+// One workgroup per block of kRbRows rows, one pass over the block's entries
 // for `live` <= KV vectors (X, Y: the pass's first column).  LDS: the block's
-// kTRows + 1 row offsets, its kTRows x KV values of X (8-byte loads: under 2 %
+// kRbRows + 1 row offsets, its kRbRows x KV values of X (8-byte loads: under 2 %
 // of the block's bytes), then the accumulator of span x KV sums when the
 // block's column range spans at most `cap` = kTMultiCap / KV columns.
 template <int KV>
@@ -299,18 +231,16 @@ __global__ __launch_bounds__(kBlock) void csr_t_multi_kernel(int64_t n_rows, int
 {
     extern __shared__ double s_mem[];
     int64_t *s_ptr = reinterpret_cast<int64_t *>(s_mem);
-    double *s_x = s_mem + kTPtr;
-    double *acc = s_x + kTRows * KV;
+    double *s_x = s_mem + kRbPtr;
+    double *acc = s_x + kRbRows * KV;
     const int tid = (int)threadIdx.x;
-    const int2 w = win[blockIdx.x];
-    const int span = w.y - w.x + 1;  // <= 0: a block without entries
-    if (span <= 0)                   // uniform per workgroup
+    RowBlock b;
+    if (!rb_open(n_rows, ptr, win, s_ptr, &b))
         return;
+    const int2 w = b.w;
+    const int span = b.span, nr = b.nr;
+    const int64_t r0 = b.r0;
     const bool lds = span <= cap;
-    const int64_t r0 = (int64_t)blockIdx.x * kTRows;
-    const int nr = (int)(n_rows - r0 < kTRows ? n_rows - r0 : kTRows);
-    for (int i = tid; i <= nr; i += kBlock)
-        s_ptr[i] = ptr[r0 + i];
     for (int i = tid; i < nr * KV; i += kBlock) {
         const int j = i % KV;
         if (j < live)
@@ -348,21 +278,16 @@ __global__ __launch_bounds__(kBlock) void t_zero_cols_kernel(int64_t n_cols, int
 
 namespace {
 
-int t_alloc(spmv_plan *p, void **dst, size_t bytes)
+int t_alloc(TransposeState *t, void **dst, size_t bytes)
 {
-    *dst = nullptr;
-    hipError_t e = hipMalloc(dst, bytes > 0 ? bytes : 16);
-    if (e != hipSuccess)
-        return fail(SPMV_PROGRAM_ERROR, "spmv_plan_prepare_transpose: hipMalloc", e);
-    p->t_owned += bytes;
-    return SPMV_SUCCESS;
+    return owned_alloc(dst, bytes, &t->owned, "spmv_plan_prepare_transpose");
 }
 
 // dynamic LDS bytes of a csr_t_multi_kernel<kv> launch whose widest LDS block
 // spans `span` columns, and the most a plan can ask for
 constexpr size_t t_multi_lds(int kv, int64_t span)
 {
-    return (size_t)(kTPtr + kTRows * kv + span * kv) * sizeof(double);
+    return (size_t)(kRbPtr + kRbRows * kv + span * kv) * sizeof(double);
 }
 
 constexpr size_t t_multi_lds_max(int kv) { return t_multi_lds(kv, kTMultiCap / kv); }
@@ -379,34 +304,31 @@ void with_each_width(F &&f)
 int prepare_scatter(spmv_plan *p)
 {
     const spmv_dims &d = p->d;
+    TransposeState &t = p->t;
     const hipStream_t st = (hipStream_t)d.stream;
-    const int64_t blocks = (d.n_rows + kTRows - 1) / kTRows;
+    const int64_t blocks = (d.n_rows + kRbRows - 1) / kRbRows;
     if (blocks > INT32_MAX)
         return fail_msg(SPMV_OTHER_ERROR, "spmv_plan_prepare_transpose: too many row blocks");
-    p->t_blocks = blocks;
+    t.blocks = blocks;
     if (blocks == 0 || d.nnz == 0)  // a run only zeroes y
         return SPMV_SUCCESS;
-    int rc = t_alloc(p, &p->t_win, (size_t)blocks * sizeof(int2));
+    int rc = t_alloc(&t, &t.win, (size_t)blocks * sizeof(int2));
     if (rc != SPMV_SUCCESS)
         return rc;
     hipLaunchKernelGGL(csr_t_range_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, st, d.n_rows, p->ptr, p->col,
-                       (int2 *)p->t_win);
+                       (int2 *)t.win);
     SPMV_CHECK_LAUNCH("csr_t_range_kernel");
     int2 *h = nullptr;
-    if ((rc = windows_download(p->t_win, blocks, st, &h, "spmv_plan_prepare_transpose")) != SPMV_SUCCESS)
+    if ((rc = windows_download(t.win, blocks, st, &h, "spmv_plan_prepare_transpose")) != SPMV_SUCCESS)
         return rc;
-    for (int64_t b = 0; b < blocks; ++b) {
-        const int64_t span = (int64_t)h[b].y - h[b].x + 1;
-        if (span > 0 && span <= kTCap) {
-            p->t_lds_blocks++;
-            p->t_flush += span;
-            p->t_xcap = span > p->t_xcap ? (int32_t)span : p->t_xcap;
-        }
-        for (int w = 0; w < 4; ++w)  // the multi-vector kernels: span * KV sums per block
-            if (span > 0 && span <= kTMultiCap / kTWidths[w]) {
-                p->t_mlds[w]++;
-                p->t_mxcap[w] = span > p->t_mxcap[w] ? (int32_t)span : p->t_mxcap[w];
-            }
+    const WindowTally one = windows_tally(h, blocks, kTCap);
+    t.lds_blocks = one.blocks;
+    t.flush = one.spans;
+    t.xcap = one.widest;
+    for (int w = 0; w < 4; ++w) {  // the multi-vector kernels: span * KV sums per block
+        const WindowTally multi = windows_tally(h, blocks, kTMultiCap / kTWidths[w]);
+        t.mlds[w] = multi.blocks;
+        t.mxcap[w] = multi.widest;
     }
     free(h);
     // a launch of the widest fitting span may need more than the default 64 KiB
@@ -428,19 +350,20 @@ int prepare_copy(spmv_plan *p)
     const spmv_dims &d = p->d;
     if (d.n_rows > INT32_MAX)
         return fail_msg(SPMV_OTHER_ERROR, "spmv_plan_prepare_transpose: the copy stores row ids as int32");
+    TransposeState &t = p->t;
     int rc;
-    if ((rc = t_alloc(p, (void **)&p->t_ptr, (size_t)(d.n_cols + 1) * sizeof(int64_t))) != SPMV_SUCCESS ||
-        (rc = t_alloc(p, (void **)&p->t_col, (size_t)d.nnz * sizeof(int32_t))) != SPMV_SUCCESS ||
-        (rc = t_alloc(p, (void **)&p->t_val, (size_t)d.nnz * sizeof(double))) != SPMV_SUCCESS ||
-        (rc = spmv_dev_csr_transpose(d, p->ptr, p->col, p->val, p->t_ptr, p->t_col, p->t_val)) != SPMV_SUCCESS)
+    if ((rc = t_alloc(&t, (void **)&t.ptr, (size_t)(d.n_cols + 1) * sizeof(int64_t))) != SPMV_SUCCESS ||
+        (rc = t_alloc(&t, (void **)&t.col, (size_t)d.nnz * sizeof(int32_t))) != SPMV_SUCCESS ||
+        (rc = t_alloc(&t, (void **)&t.val, (size_t)d.nnz * sizeof(double))) != SPMV_SUCCESS ||
+        (rc = spmv_dev_csr_transpose(d, p->ptr, p->col, p->val, t.ptr, t.col, t.val)) != SPMV_SUCCESS)
         return rc;
-    spmv_dims t = d;
-    t.n_rows = d.n_cols;
-    t.n_cols = d.n_rows;
-    if ((rc = spmv_plan_csr(t, p->t_ptr, p->t_col, p->t_val, nullptr, &p->t_inner)) != SPMV_SUCCESS)
+    spmv_dims dt = d;
+    dt.n_rows = d.n_cols;
+    dt.n_cols = d.n_rows;
+    if ((rc = spmv_plan_csr(dt, t.ptr, t.col, t.val, nullptr, &t.inner)) != SPMV_SUCCESS)
         return rc;
     // a balanced outer plan (spmv_plan_prepare_multi) extends to the inner one
-    return p->m_mode != SPMV_M_NONE ? spmv_plan_prepare_multi(p->t_inner, p->m_mode, &p->m_req) : SPMV_SUCCESS;
+    return p->m.mode != SPMV_M_NONE ? spmv_plan_prepare_multi(t.inner, p->m.mode, &p->m.req) : SPMV_SUCCESS;
 }
 
 int launch_scatter(const spmv_plan *p, const double *x, double *y, hipStream_t st)
@@ -451,11 +374,11 @@ int launch_scatter(const spmv_plan *p, const double *x, double *y, hipStream_t s
         if (e != hipSuccess)
             return fail(SPMV_PROGRAM_ERROR, "spmv_plan_run_t: memset", e);
     }
-    if (!p->t_win || d.n_cols == 0)
+    if (!p->t.win || d.n_cols == 0)
         return SPMV_SUCCESS;
-    const size_t lds = (size_t)(kTPtr + kTRows + p->t_xcap) * sizeof(double);
-    hipLaunchKernelGGL(csr_t_window_kernel, dim3((unsigned)p->t_blocks), dim3(kBlock), lds, st, d.n_rows, d.n_cols,
-                       p->ptr, p->col, p->val, x, y, (const int2 *)p->t_win, kTCap);
+    const size_t lds = (size_t)(kRbPtr + kRbRows + p->t.xcap) * sizeof(double);
+    hipLaunchKernelGGL(csr_t_window_kernel, dim3((unsigned)p->t.blocks), dim3(kBlock), lds, st, d.n_rows, d.n_cols,
+                       p->ptr, p->col, p->val, x, y, (const int2 *)p->t.win, kTCap);
     SPMV_CHECK_LAUNCH("csr_t_window_kernel");
     return SPMV_SUCCESS;
 }
@@ -478,16 +401,16 @@ int launch_scatter_multi(const spmv_plan *p, int32_t k, const double *X, int64_t
                            d.n_cols, k, Y, ldy);
         SPMV_CHECK_LAUNCH("t_zero_cols_kernel");
     }
-    if (!p->t_win || d.n_cols == 0)
+    if (!p->t.win || d.n_cols == 0)
         return SPMV_SUCCESS;
     for (int32_t j0 = 0; j0 < k; j0 += 8) {
         const int32_t live = k - j0 < 8 ? k - j0 : 8;
         const int w = live > 4 ? 3 : live > 2 ? 2 : live - 1;  // width kTWidths[w] >= live
         with_int<1, 2, 4, 8>(kTWidths[w], [&](auto KV) {
             constexpr int kv = decltype(KV)::value;
-            hipLaunchKernelGGL(csr_t_multi_kernel<kv>, dim3((unsigned)p->t_blocks), dim3(kBlock),
-                               t_multi_lds(kv, p->t_mxcap[w]), st, d.n_rows, d.n_cols, p->ptr, p->col, p->val, X + j0,
-                               ldx, Y + j0, ldy, (const int2 *)p->t_win, kTMultiCap / kv, live);
+            hipLaunchKernelGGL(csr_t_multi_kernel<kv>, dim3((unsigned)p->t.blocks), dim3(kBlock),
+                               t_multi_lds(kv, p->t.mxcap[w]), st, d.n_rows, d.n_cols, p->ptr, p->col, p->val, X + j0,
+                               ldx, Y + j0, ldy, (const int2 *)p->t.win, kTMultiCap / kv, live);
         });
         SPMV_CHECK_LAUNCH("csr_t_multi_kernel");
     }
@@ -496,27 +419,7 @@ int launch_scatter_multi(const spmv_plan *p, int32_t k, const double *X, int64_t
 
 }  // namespace
 
-void plan_transpose_free(spmv_plan *p)
-{
-    if (p->t_inner)
-        spmv_plan_destroy(p->t_inner);
-    for (void *q : {p->t_win, (void *)p->t_ptr, (void *)p->t_col, (void *)p->t_val})
-        if (q)
-            (void)hipFree(q);
-    p->t_inner = nullptr;
-    p->t_win = nullptr;
-    p->t_ptr = nullptr;
-    p->t_col = nullptr;
-    p->t_val = nullptr;
-    p->t_mode = SPMV_T_NONE;
-    p->t_xcap = 0;
-    p->t_blocks = p->t_lds_blocks = p->t_flush = 0;
-    for (int w = 0; w < 4; ++w) {
-        p->t_mxcap[w] = 0;
-        p->t_mlds[w] = 0;
-    }
-    p->t_owned = 0;
-}
+void plan_transpose_free(spmv_plan *p) { mode_state_free(&p->t); }
 
 }  // namespace spmv
 
@@ -534,12 +437,12 @@ int spmv_plan_prepare_transpose(spmv_plan *p, int mode)
         return fail_msg(SPMV_OTHER_ERROR, "spmv_plan_prepare_transpose: unknown mode");
     if (p->fmt != SPMV_FMT_CSR)
         return fail_msg(SPMV_OTHER_ERROR, "spmv_plan_prepare_transpose: only CSR plans have a transposed run");
-    if (mode == p->t_mode)
+    if (mode == p->t.mode)
         return SPMV_SUCCESS;
     SPMV_GUARD(p->d);
     const hipStream_t st = (hipStream_t)p->d.stream;
     // a run of the old mode may still be in flight on the build stream
-    if (p->t_mode != SPMV_T_NONE && hipStreamSynchronize(st) != hipSuccess)
+    if (p->t.mode != SPMV_T_NONE && hipStreamSynchronize(st) != hipSuccess)
         return fail_msg(SPMV_PROGRAM_ERROR, "spmv_plan_prepare_transpose: synchronise");
     plan_transpose_free(p);
     if (mode == SPMV_T_NONE)
@@ -548,13 +451,9 @@ int spmv_plan_prepare_transpose(spmv_plan *p, int mode)
     // runs may come on any stream: everything is complete when this returns
     if (rc == SPMV_SUCCESS && hipStreamSynchronize(st) != hipSuccess)
         rc = fail_msg(SPMV_PROGRAM_ERROR, "spmv_plan_prepare_transpose: synchronise");
-    if (rc != SPMV_SUCCESS) {
-        char keep[512];
-        snprintf(keep, sizeof keep, "%s", spmv_last_error());
-        plan_transpose_free(p);
-        return fail_msg(rc, keep);
-    }
-    p->t_mode = mode;
+    if (rc != SPMV_SUCCESS)  // SPMV_T_NONE is left
+        return fail_after(rc, [&] { plan_transpose_free(p); });
+    p->t.mode = mode;
     return SPMV_SUCCESS;
 }
 
@@ -563,16 +462,17 @@ int spmv_plan_get_transpose_info(const spmv_plan *p, spmv_transpose_info *info)
     if (!p || !info)
         return fail_msg(SPMV_OTHER_ERROR, "spmv_plan_get_transpose_info: NULL argument");
     memset(info, 0, sizeof *info);
-    info->mode = p->t_mode;
-    info->owned_bytes = (int64_t)(p->t_owned + (p->t_inner ? p->t_inner->owned : 0));
-    if (p->t_mode == SPMV_T_SCATTER) {
+    const TransposeState &t = p->t;
+    info->mode = t.mode;
+    info->owned_bytes = (int64_t)(t.owned + (t.inner ? t.inner->owned : 0));
+    if (t.mode == SPMV_T_SCATTER) {
         info->cap = kTCap;
-        info->blocks = p->t_blocks;
-        info->lds_blocks = p->t_lds_blocks;
-        info->flush_entries = p->t_flush;
+        info->blocks = t.blocks;
+        info->lds_blocks = t.lds_blocks;
+        info->flush_entries = t.flush;
         snprintf(info->kernel, sizeof info->kernel, "csr_t_window_kernel");
-    } else if (p->t_inner) {
-        snprintf(info->kernel, sizeof info->kernel, "%s", p->t_inner->kernel);
+    } else if (t.inner) {
+        snprintf(info->kernel, sizeof info->kernel, "%s", t.inner->kernel);
     }
     return SPMV_SUCCESS;
 }
@@ -581,12 +481,12 @@ int spmv_plan_run_t(const spmv_plan *p, const double *x, double *y, void *stream
 {
     if (!p)
         return fail_msg(SPMV_OTHER_ERROR, "spmv_plan_run_t: plan is NULL");
-    if (p->t_mode == SPMV_T_NONE)
+    if (p->t.mode == SPMV_T_NONE)
         return fail_msg(SPMV_OTHER_ERROR, "spmv_plan_run_t: the plan was not prepared (spmv_plan_prepare_transpose)");
     if ((p->d.n_rows > 0 && !x) || (p->d.n_cols > 0 && !y))
         return fail_msg(SPMV_OTHER_ERROR, "spmv_plan_run_t: x or y is NULL");
-    if (p->t_mode == SPMV_T_COPY)
-        return spmv_plan_run(p->t_inner, x, y, stream);
+    if (p->t.mode == SPMV_T_COPY)
+        return spmv_plan_run(p->t.inner, x, y, stream);
     SPMV_GUARD(p->d);
     return launch_scatter(p, x, y, (hipStream_t)stream);
 }
@@ -596,14 +496,14 @@ int spmv_plan_get_transpose_multi_info(const spmv_plan *p, spmv_transpose_multi_
     if (!p || !info)
         return fail_msg(SPMV_OTHER_ERROR, "spmv_plan_get_transpose_multi_info: NULL argument");
     memset(info, 0, sizeof *info);
-    info->mode = p->t_mode;
-    if (p->t_mode == SPMV_T_SCATTER) {
+    info->mode = p->t.mode;
+    if (p->t.mode == SPMV_T_SCATTER) {
         for (int w = 0; w < 4; ++w) {
             info->cap_cols[w] = kTMultiCap / kTWidths[w];
-            info->lds_blocks[w] = p->t_mlds[w];
+            info->lds_blocks[w] = p->t.mlds[w];
         }
         snprintf(info->kernel, sizeof info->kernel, "csr_t_multi_kernel");
-    } else if (p->t_inner) {
+    } else if (p->t.inner) {
         snprintf(info->kernel, sizeof info->kernel, "csr_multi_kernel");  // every CSR path's multi-vector kernel
     }
     return SPMV_SUCCESS;
@@ -614,7 +514,7 @@ int spmv_plan_run_t_multi(const spmv_plan *p, int32_t k, const double *X, int64_
 {
     if (!p)
         return fail_msg(SPMV_OTHER_ERROR, "spmv_plan_run_t_multi: plan is NULL");
-    if (p->t_mode == SPMV_T_NONE)
+    if (p->t.mode == SPMV_T_NONE)
         return fail_msg(SPMV_OTHER_ERROR,
                         "spmv_plan_run_t_multi: the plan was not prepared (spmv_plan_prepare_transpose)");
     if (k < 1)
@@ -623,8 +523,8 @@ int spmv_plan_run_t_multi(const spmv_plan *p, int32_t k, const double *X, int64_
         return fail_msg(SPMV_OTHER_ERROR, "spmv_plan_run_t_multi: ldx and ldy must be at least k");
     if ((p->d.n_rows > 0 && !X) || (p->d.n_cols > 0 && !Y))
         return fail_msg(SPMV_OTHER_ERROR, "spmv_plan_run_t_multi: X or Y is NULL");
-    if (p->t_mode == SPMV_T_COPY)
-        return spmv_plan_run_multi(p->t_inner, k, X, ldx, Y, ldy, stream);
+    if (p->t.mode == SPMV_T_COPY)
+        return spmv_plan_run_multi(p->t.inner, k, X, ldx, Y, ldy, stream);
     SPMV_GUARD(p->d);
     return launch_scatter_multi(p, k, X, ldx, Y, ldy, (hipStream_t)stream);
 }
