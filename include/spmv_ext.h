@@ -410,8 +410,8 @@ int spmv_gather(int64_t n, const int32_t *order, const double *x, double *out, i
 /* ---------------------------------------------------------- switches ---
  * Placement and load-policy switches for A/B runs; each changes speed,
  * never a result bit (tests/test_gpu_parity.py checks that).  The library
- * reads SPMV_XWIN_REMAP, SPMV_XCD_REMAP, SPMV_STREAM_NT, SPMV_CSR_PREFETCH
- * and SPMV_CSR_COL16 once, when it is loaded, as their initial values; spmv_set_option changes them for
+ * reads SPMV_XWIN_REMAP, SPMV_XCD_REMAP, SPMV_STREAM_NT and SPMV_CSR_COL16
+ * once, when it is loaded, as their initial values; spmv_set_option changes them for
  * the whole process (value -1 = each kernel's measured default, 0 off,
  * 1 on).  Nothing reads the environment on the launch path.
  * SPMV_OPT_CSR_COL16 is read when a CSR plan is created, not when it runs:
@@ -423,7 +423,7 @@ enum spmv_option {
     SPMV_OPT_XWIN_REMAP = 1,   /* XCD-contiguous x-window workgroups        */
     SPMV_OPT_XCD_REMAP = 2,    /* XCD-contiguous global-gather workgroups   */
     SPMV_OPT_STREAM_NT = 3,    /* non-temporal matrix loads                 */
-    SPMV_OPT_CSR_PREFETCH = 4, /* CSR x-window: first chunk in the prologue */
+    /* 4 is unused (a retired CSR x-window load schedule): an unknown option */
     SPMV_OPT_CSR_COL16 = 5     /* CSR x-window plans: 16-bit column offsets */
 };
 int spmv_set_option(int option, int value);

@@ -67,8 +67,6 @@ bool xcd_remap_enabled();
 // XCD-contiguous window placement of the x-window kernels; `dflt` = each
 // kernel's measured best.
 bool xwin_remap(bool dflt);
-// CSR x-window kernel: the first chunk prefetched in the prologue (MODE 4)
-bool csr_prefetch(bool dflt);
 // CSR x-window plans: the plan-owned 16-bit window-relative column copy
 // (read at plan creation)
 bool csr_col16(bool dflt);

@@ -9,7 +9,8 @@
 //   2 = staged: the row group's entry range is streamed through LDS by all
 //       256 lanes like a copy kernel, then each L-lane group sums its row;
 //   3 = staged, persistent workgroups with the next group's offsets
-//       prefetched (default; spmv_csr_run_xwin adds the LDS x windows);
+//       fetched ahead (default; spmv_csr_run_xwin adds the LDS x windows,
+//       load schedule MODE 0 or 3 of csr_xwin_kernel);
 //   4 = entry-balanced tiles for skewed rows (spmv_csr_run_tiled, staged.hip).
 // Bytes per row: 12·len + 8 (row_ptr) + 8 (y), plus x gathers.
 #include <stdio.h>
@@ -275,23 +276,6 @@ struct StreamRegs {
     typename Cols::Raw c[R];
     int64_t q[R];  // the pair each lane loaded (decode needs it for escaped blocks only)
 
-    // issue() for an array known to hold at least 2 entries: branch-free, so
-    // a caller may issue it inside straight-line code whose later waits must
-    // leave these loads in flight (a branch around loads makes the compiler's
-    // wait counts conservative at the join: vmcnt(0) for everything)
-    __device__ __forceinline__ void issue_nz2(int64_t cb, int64_t ce, int64_t nz, const Cols &cols,
-                                              const V *__restrict__ val)
-    {
-        const int64_t spare = cb + 1 < nz ? cb : (nz - 2) & ~(int64_t)1;  // this chunk's first pair
-#pragma unroll
-        for (int k = 0; k < R; ++k) {
-            const int64_t p = cb + 2 * (int64_t)(threadIdx.x + k * kBlock);
-            q[k] = (p < ce && p + 1 < nz) ? p : spare;
-            v[k] = vpair<NT>(val + q[k]);
-            c[k] = cols.raw(q[k]);
-        }
-    }
-
     __device__ __forceinline__ void issue(int64_t cb, int64_t ce, int64_t nz, const Cols &cols,
                                           const V *__restrict__ val)
     {
@@ -352,15 +336,11 @@ struct StreamRegs {
     do {             \
     } while (0)
 #endif
-// st: the chunk loads in flight; prefetched = the caller already issued
-// group 0's first chunk into st (csr_xwin_kernel MODE 4), so the first issue
-// here is skipped (the same chunk, the same bits).
 template <int L, int R, bool NT, typename XS, typename V, typename Cols = Col32<NT>>
 __device__ __forceinline__ void staged_window_pipelined(int64_t row0, int ngroups, const int64_t *s_off,
                                                         double2 *s_prod, const Cols cols,
                                                         const V *__restrict__ val, const XS xs,
-                                                        double *__restrict__ y, int64_t n_rows, int64_t nz,
-                                                        StreamRegs<R, NT, V, Cols> &st, bool prefetched)
+                                                        double *__restrict__ y, int64_t n_rows, int64_t nz)
 {
     constexpr int RPB = kBlock / L;
     constexpr int CH = 2 * kBlock * R;
@@ -375,8 +355,9 @@ __device__ __forceinline__ void staged_window_pipelined(int64_t row0, int ngroup
             ++j;
         return j;
     };
+    StreamRegs<R, NT, V, Cols> st;  // the chunk loads in flight
     int jn = next_group(0);
-    if (jn < ngroups && !prefetched) {
+    if (jn < ngroups) {
         const int64_t b = chunk_start(s_off[jn * RPB]), e = s_off[(jn + 1) * RPB];
         st.issue(b, b + CH < e ? b + CH : e, nz, cols, val);
     }
@@ -536,16 +517,13 @@ __global__ __launch_bounds__(kBlock) void csr_col16_kernel(int64_t n_rows, int64
 //       x range) and its x range loaded together, 8 loads in flight per
 //       thread, before ONE barrier; the chunks software-pipelined: the next
 //       chunk's loads are issued before the current chunk's barrier and
-//       reduction (staged_window_pipelined);
-//   4 = MODE 3 with the window's first chunk also issued in the prologue,
-//       right behind the x-range and offset loads, from two scalar loads of
-//       its bounds: its HBM round trip overlaps the window's instead of
-//       following the window barrier (a small grid, all windows resident:
-//       the per-window chain is the kernel's time).
-// (Modes 1/2/4/5-7, a prefetched first chunk, a persistent streaming kernel
-// with an x ring and a per-entry-range flat schedule were measured slower
-// or equal and removed: profiles/round2/ab_csr_xwin*.log, ab_csr_flat.log,
-// ab_xstream.log.)
+//       reduction (staged_window_pipelined).
+// (Modes 1/2/4/5-7, a persistent streaming kernel with an x ring and a
+// per-entry-range flat schedule were measured slower or equal and removed:
+// profiles/round2/ab_csr_xwin*.log, ab_csr_flat.log, ab_xstream.log; so was
+// the later MODE 4, MODE 3 with the window's first chunk issued in the
+// prologue behind the x-range and offset loads: 15.6 against 14.8 us cold on
+// one cant-like matrix, 90 against 72 VGPRs, profiles/round6/csr_prefetch_ab.md.)
 template <int L, int R, bool NT, typename V, int MODE, typename Cols>
 __global__ __launch_bounds__(kBlock) void csr_xwin_kernel(
     int64_t n_rows, int64_t n_groups, int64_t gpw, const int64_t *__restrict__ row_ptr,
@@ -553,11 +531,11 @@ __global__ __launch_bounds__(kBlock) void csr_xwin_kernel(
     const double *__restrict__ x, double *__restrict__ y, const int2 *__restrict__ win, int32_t xcap,
     int remap)
 {
-    static_assert(MODE == 0 || MODE == 3 || MODE == 4, "csr_xwin_kernel: MODE 0, 3 or 4");
+    static_assert(MODE == 0 || MODE == 3, "csr_xwin_kernel: MODE 0 or 3");
     CSR_STAMP(0);
     constexpr int RPB = kBlock / L;
     extern __shared__ double s_x[];
-    __shared__ int64_t s_ptr[MODE >= 3 ? 1 : RPB + 1];
+    __shared__ int64_t s_ptr[MODE == 3 ? 1 : RPB + 1];
     __shared__ double2 s_prod[kBlock * R];
     int64_t *s_off = reinterpret_cast<int64_t *>(s_x + xcap);  // MODE 3: the window's offsets
     const int64_t nz = row_ptr[n_rows];
@@ -566,30 +544,13 @@ __global__ __launch_bounds__(kBlock) void csr_xwin_kernel(
     const int64_t wi = xcd_block(remap);
     const int64_t g_beg = wi * gpw;
     const int64_t g_end = (wi + 1) * gpw < n_groups ? (wi + 1) * gpw : n_groups;
-    // MODE 4: group 0's bounds, uniform addresses (scalar loads, their own
-    // counter), requested together with the window bounds and pinned by the
-    // empty asm (a scheduling boundary) so that ONE scalar round trip
-    // precedes every vector load
-    int64_t pb = 0, pe = 0, b0 = 0;
-    if constexpr (MODE == 4) {
-        const int64_t r0p = g_beg * RPB;
-        const int64_t r1 = r0p + RPB < n_rows ? r0p + RPB : n_rows;
-        b0 = row_ptr[r0p];
-        pe = row_ptr[r1];
-    }
     const int2 wnd = win[wi];
-    if constexpr (MODE == 4) {
-        asm volatile("" ::"s"(b0), "s"(pe), "s"(wnd.x), "s"(wnd.y), "s"(nz));
-        pb = chunk_start(b0);
-    }
     const int32_t span = wnd.y - wnd.x + 1;
     const bool staged = span > 0 && span <= xcap;  // uniform per workgroup
-    if constexpr (MODE >= 3) {
+    if constexpr (MODE == 3) {
         // offsets r0 .. r0 + nr of the window's rows (clamped past n_rows),
         // then the x range: every load issued before the stores
         const int64_t r0 = g_beg * RPB;
-        StreamRegs<R, NT, V, Cols> st;
-        bool pre = MODE == 4 && pb < pe;  // group 0 has a chunk (next_group(0) == 0)
         const int32_t nr = (int32_t)((g_end - g_beg) * RPB) + 1;
         constexpr int U = 2;  // offsets per thread per pass (nr <= U·256 in one pass)
         constexpr int XU = 8;  // window entries per thread (copy_window's default)
@@ -610,18 +571,6 @@ __global__ __launch_bounds__(kBlock) void csr_xwin_kernel(
                 const int32_t i = (int32_t)threadIdx.x + k * kBlock;
                 xv[k] = x[wnd.x + (i < xl ? i : xl)];
             }
-            // MODE 4: the first chunk behind them (loads return in order:
-            // storing the offsets and the window waits for those only).
-            // Unconditional (an empty group 0 loads its spare pair, then the
-            // pipeline issues its real first chunk); the launcher picks MODE
-            // 4 only for nnz >= 2
-            if constexpr (MODE == 4) {
-                st.issue_nz2(pb, pre ? (pb + 2 * kBlock * R < pe ? pb + 2 * kBlock * R : pe) : pb, nz, cols, val);
-                // the offsets' loads stay here, ahead of the chunk's (the
-                // compiler otherwise sinks o[0] into its conditional store,
-                // behind every load of the prologue, and waits for all)
-                asm volatile("" ::"v"(o[0]), "v"(o[1]));
-            }
 #pragma unroll
             for (int k = 0; k < U; ++k) {
                 const int32_t i = (int32_t)threadIdx.x + k * kBlock;
@@ -636,8 +585,7 @@ __global__ __launch_bounds__(kBlock) void csr_xwin_kernel(
                         s_x[i] = xv[k];
                 }
             }
-        } else {
-        pre = false;  // a window too big for the one-pass prologue: issued after the barrier
+        } else {  // a window too big for one pass
         for (int32_t b = 0; b < nr; b += U * kBlock) {
             int64_t o[U];
 #pragma unroll
@@ -663,13 +611,13 @@ __global__ __launch_bounds__(kBlock) void csr_xwin_kernel(
         if constexpr (Cols::kWindowRelative)
             staged_window_pipelined<L, R, NT, XWindowRel, V, Cols>(r0, (int)(g_end - g_beg), s_off, s_prod, cols,
                                                                   val, XWindowRel{s_x, staged ? (uint32_t)span - 1 : 0u},
-                                                                  y, n_rows, nz, st, pre);
+                                                                  y, n_rows, nz);
         else if (staged)
             staged_window_pipelined<L, R, NT, XWindow, V, Cols>(r0, (int)(g_end - g_beg), s_off, s_prod, cols, val,
-                                                               XWindow{s_x, wnd.x}, y, n_rows, nz, st, pre);
+                                                               XWindow{s_x, wnd.x}, y, n_rows, nz);
         else
             staged_window_pipelined<L, R, NT, XGlobal, V, Cols>(r0, (int)(g_end - g_beg), s_off, s_prod, cols, val,
-                                                               XGlobal{x}, y, n_rows, nz, st, pre);
+                                                               XGlobal{x}, y, n_rows, nz);
         return;
     }
     if (staged)
@@ -896,19 +844,7 @@ static bool csr_xwin_remap_rule(int32_t xcap, int64_t rows_per_window, int64_t n
 // row offsets behind it
 static size_t csr_xwin_lds(int mode, int32_t xcap, int64_t gpw, int rpb)
 {
-    return ((size_t)xcap + (mode >= 3 ? (size_t)(gpw * rpb + 1) : 0)) * sizeof(double);
-}
-
-// MODE 4 (the first chunk prefetched in the prologue, behind the x window's
-// and offsets' loads) is opt-in: on one cant-like matrix (976 windows of 64
-// rows, all resident at once) it measured 15.6 us cold against MODE 3's
-// 14.8 us (profiles/round6/csr_prefetch_ab.md) — its 90 VGPRs cost a wave per
-// SIMD and the barrier already waits on the x window's HBM round trip.
-// SPMV_OPT_CSR_PREFETCH (spmv_set_option) = 1 selects it (same bits).
-static bool csr_xwin_prefetch_rule(int64_t n_windows)
-{
-    (void)n_windows;
-    return csr_prefetch(false);
+    return ((size_t)xcap + (mode == 3 ? (size_t)(gpw * rpb + 1) : 0)) * sizeof(double);
 }
 
 // rows per x window: a multiple of the row group (256/L rows), default
@@ -938,6 +874,17 @@ static int64_t csr_xwin_gpw(int L, int32_t rows_per_window, int64_t n_rows)
     return g;
 }
 
+// the window table's geometry for a valid L and n_rows > 0: rows per x window
+// (whole row groups) and the number of windows
+struct XwinGeom {
+    int64_t rpw, n_win;
+};
+static XwinGeom csr_xwin_geom(int L, int32_t rows_per_window, int64_t n_rows)
+{
+    const int64_t rpw = csr_xwin_gpw(L, rows_per_window, n_rows) * (kBlock / L);
+    return {rpw, (n_rows + rpw - 1) / rpw};
+}
+
 template <int L, int R, bool NT, typename Cols, typename V = double>
 static void launch_csr_xwin(const spmv_dims &d, const int64_t *row_ptr, const Cols cols,
                             const V *val, const double *x, double *y, const int2 *win, int32_t xcap,
@@ -954,9 +901,7 @@ static void launch_csr_xwin(const spmv_dims &d, const int64_t *row_ptr, const Co
     const size_t lds = csr_xwin_lds(mode, xcap, gpw, RPB);
     const int remap = csr_xwin_remap_rule(xcap, gpw * RPB, n_win) ? 1 : 0;
     const hipStream_t st = (hipStream_t)d.stream;
-    if (mode == 3 && d.nnz >= 2 && csr_xwin_prefetch_rule(n_win))
-        mode = 4;
-    with_int<4, 3, 0>(mode, [&](auto M) {
+    with_int<3, 0>(mode, [&](auto M) {
         hipLaunchKernelGGL((csr_xwin_kernel<L, R, NT, V, decltype(M)::value, Cols>), dim3((unsigned)n_win),
                            dim3(kBlock), lds, st, d.n_rows, groups, gpw, row_ptr, cols, val, x, y, win, xcap, remap);
     });
@@ -1007,10 +952,9 @@ static int launch_xwin_any(const spmv_dims &d, int L, const int64_t *row_ptr, Ma
 extern "C" size_t spmv_csr_xwin_bytes(int64_t n_rows, int64_t nnz, int lanes_per_row, int32_t rows_per_window)
 {
     const int L = lanes_per_row > 0 ? lanes_per_row : spmv_csr_auto_lanes(n_rows, nnz);
-    if (L < 2 || L > 64 || (L & (L - 1)) || n_rows <= 0 || rows_per_window < 0)
+    if (!lanes_ok(L) || n_rows <= 0 || rows_per_window < 0)
         return 0;
-    const int64_t rpw = csr_xwin_gpw(L, rows_per_window, n_rows) * (kBlock / L);
-    return (size_t)((n_rows + rpw - 1) / rpw) * sizeof(int2);
+    return (size_t)csr_xwin_geom(L, rows_per_window, n_rows).n_win * sizeof(int2);
 }
 
 extern "C" int spmv_csr_xwin_build(spmv_dims d, const int64_t *row_ptr, const int32_t *col,
@@ -1023,22 +967,20 @@ extern "C" int spmv_csr_xwin_build(spmv_dims d, const int64_t *row_ptr, const in
     if (d.n_rows == 0)
         return SPMV_SUCCESS;
     const int L = lanes_per_row > 0 ? lanes_per_row : spmv_csr_auto_lanes(d.n_rows, d.nnz);
-    const size_t need = spmv_csr_xwin_bytes(d.n_rows, d.nnz, L, rows_per_window);
-    if (need == 0)
+    if (!lanes_ok(L))
         return fail_msg(SPMV_OTHER_ERROR, "spmv_csr_xwin_build: lanes_per_row must be 0 or a power of two in [2,64]");
-    if (!win || win_bytes < need)
+    const XwinGeom g = csr_xwin_geom(L, rows_per_window, d.n_rows);
+    if (!win || win_bytes < (size_t)g.n_win * sizeof(int2))
         return fail_msg(SPMV_OTHER_ERROR, "spmv_csr_xwin_build: window buffer too small");
     SPMV_GUARD(d);
-    const int64_t rpw = csr_xwin_gpw(L, rows_per_window, d.n_rows) * (kBlock / L);
-    const int64_t n_win = (d.n_rows + rpw - 1) / rpw;
     const hipStream_t st = (hipStream_t)d.stream;
-    hipLaunchKernelGGL(csr_window_kernel, dim3((unsigned)n_win), dim3(kBlock), 0, st, d.n_rows, rpw, row_ptr,
+    hipLaunchKernelGGL(csr_window_kernel, dim3((unsigned)g.n_win), dim3(kBlock), 0, st, d.n_rows, g.rpw, row_ptr,
                        col, (int2 *)win);
     SPMV_CHECK_LAUNCH("csr_window_kernel");
-    return windows_xcap(win, n_win, kCsrXwinCap, st, xcap, "spmv_csr_xwin_build");
+    return windows_xcap(win, g.n_win, kCsrXwinCap, st, xcap, "spmv_csr_xwin_build");
 }
 
-// argument checks of the three x-window runs; *L = lanes per row, *gpw = row
+// argument checks of the x-window runs; *L = lanes per row, *gpw = row
 // groups per window (a grid of one workgroup per window)
 static int xwin_args(spmv_dims d, int32_t rows_per_window, const void *win, int32_t xcap, int lanes_per_row,
                      int *L, int64_t *gpw, const char *who)
@@ -1066,21 +1008,38 @@ static int xwin_args(spmv_dims d, int32_t rows_per_window, const void *win, int3
     return SPMV_SUCCESS;
 }
 
+// The tail of every x-window run: the shared argument checks, nothing to do
+// for a matrix without rows, then the entry point's own check, then the
+// launch on d's device.  mk = the column source, who = the entry point's name
+// for the shared error texts, own_err = the text of the entry point's own
+// argument error (tested by the caller; null = none), kernel = the launch's
+// name in a launch error.
+template <typename V, typename MakeCols>
+static int run_xwin(spmv_dims d, const int64_t *row_ptr, MakeCols mk, const V *val, const double *x, double *y,
+                    int lanes_per_row, int32_t rows_per_window, const void *win, int32_t xcap, const char *who,
+                    const char *own_err, const char *kernel)
+{
+    int L = 0;
+    int64_t gpw = 0;
+    int rc = xwin_args(d, rows_per_window, win, xcap, lanes_per_row, &L, &gpw, who);
+    if (rc != SPMV_SUCCESS || d.n_rows == 0)
+        return rc;
+    if (own_err)
+        return fail_msg(SPMV_OTHER_ERROR, own_err);
+    SPMV_GUARD(d);
+    rc = launch_xwin_any(d, L, row_ptr, mk, val, x, y, (const int2 *)win, xcap, gpw);
+    if (rc != SPMV_SUCCESS)
+        return rc;
+    SPMV_CHECK_LAUNCH(kernel);
+    return SPMV_SUCCESS;
+}
+
 extern "C" int spmv_csr_run_xwin(spmv_dims d, const int64_t *row_ptr, const int32_t *col, const double *val,
                                  const double *x, double *y, int lanes_per_row, int32_t rows_per_window,
                                  const void *win, int32_t xcap)
 {
-    int L = 0;
-    int64_t gpw = 0;
-    int rc = xwin_args(d, rows_per_window, win, xcap, lanes_per_row, &L, &gpw, "spmv_csr_run_xwin");
-    if (rc != SPMV_SUCCESS || d.n_rows == 0)
-        return rc;
-    SPMV_GUARD(d);
-    rc = launch_xwin_any(d, L, row_ptr, MakeCol32{col}, val, x, y, (const int2 *)win, xcap, gpw);
-    if (rc != SPMV_SUCCESS)
-        return rc;
-    SPMV_CHECK_LAUNCH("csr_xwin_kernel");
-    return SPMV_SUCCESS;
+    return run_xwin(d, row_ptr, MakeCol32{col}, val, x, y, lanes_per_row, rows_per_window, win, xcap,
+                    "spmv_csr_run_xwin", nullptr, "csr_xwin_kernel");
 }
 
 // ---- the plan's window-relative 16-bit column copy (ColWin16; plan.hip)
@@ -1119,10 +1078,9 @@ int spmv::csr_col16_fill(const spmv_dims &d, const int64_t *row_ptr, const int32
     const int L = lanes_per_row > 0 ? lanes_per_row : spmv_csr_auto_lanes(d.n_rows, d.nnz);
     if (!lanes_ok(L) || d.n_rows <= 0 || !win || !off)
         return fail_msg(SPMV_OTHER_ERROR, "spmv_plan_csr: 16-bit column copy: bad arguments");
-    const int64_t rpw = csr_xwin_gpw(L, rows_per_window, d.n_rows) * (kBlock / L);
-    const int64_t n_win = (d.n_rows + rpw - 1) / rpw;
-    hipLaunchKernelGGL(csr_col16_kernel, dim3((unsigned)n_win), dim3(kBlock), 0, (hipStream_t)d.stream, d.n_rows,
-                       d.nnz, rpw, row_ptr, col, (const int2 *)win, off);
+    const XwinGeom g = csr_xwin_geom(L, rows_per_window, d.n_rows);
+    hipLaunchKernelGGL(csr_col16_kernel, dim3((unsigned)g.n_win), dim3(kBlock), 0, (hipStream_t)d.stream, d.n_rows,
+                       d.nnz, g.rpw, row_ptr, col, (const int2 *)win, off);
     SPMV_CHECK_LAUNCH("csr_col16_kernel");
     return SPMV_SUCCESS;
 }
@@ -1133,19 +1091,10 @@ int spmv::csr_run_xwin_col16(spmv_dims d, const int64_t *row_ptr, const uint16_t
                              const double *x, double *y, int lanes_per_row, int32_t rows_per_window,
                              const void *win, int32_t xcap)
 {
-    int L = 0;
-    int64_t gpw = 0;
-    int rc = xwin_args(d, rows_per_window, win, xcap, lanes_per_row, &L, &gpw, "spmv_plan_run");
-    if (rc != SPMV_SUCCESS || d.n_rows == 0)
-        return rc;
-    if (!off || xcap < 1 || d.nnz < 2)
-        return fail_msg(SPMV_OTHER_ERROR, "spmv_plan_run: corrupt 16-bit column copy");
-    SPMV_GUARD(d);
-    rc = launch_xwin_any(d, L, row_ptr, MakeColWin16{off}, val, x, y, (const int2 *)win, xcap, gpw);
-    if (rc != SPMV_SUCCESS)
-        return rc;
-    SPMV_CHECK_LAUNCH("csr_xwin_kernel (16-bit window offsets)");
-    return SPMV_SUCCESS;
+    const bool corrupt = !off || xcap < 1 || d.nnz < 2;
+    return run_xwin(d, row_ptr, MakeColWin16{off}, val, x, y, lanes_per_row, rows_per_window, win, xcap,
+                    "spmv_plan_run", corrupt ? "spmv_plan_run: corrupt 16-bit column copy" : nullptr,
+                    "csr_xwin_kernel (16-bit window offsets)");
 }
 
 extern "C" int spmv_csr16_run(spmv_dims d, const int64_t *row_ptr, const int32_t *blk_base,
@@ -1184,20 +1133,11 @@ extern "C" int spmv_csr16_run_xwin(spmv_dims d, const int64_t *row_ptr, const in
                                    const double *x, double *y, int lanes_per_row, int32_t rows_per_window,
                                    const void *win, int32_t xcap)
 {
-    int L = 0;
-    int64_t gpw = 0;
-    int rc = xwin_args(d, rows_per_window, win, xcap, lanes_per_row, &L, &gpw, "spmv_csr16_run_xwin");
-    if (rc != SPMV_SUCCESS || d.n_rows == 0)
-        return rc;
-    if (d.nnz > 0 && (!blk_base || !col_off))
-        return fail_msg(SPMV_OTHER_ERROR, "spmv_csr16_run_xwin: missing index arrays");
-    SPMV_GUARD(d);
-    rc = launch_xwin_any(d, L, row_ptr, MakeCol16{blk_base, col_off, col_esc}, val, x, y, (const int2 *)win, xcap,
-                         gpw);
-    if (rc != SPMV_SUCCESS)
-        return rc;
-    SPMV_CHECK_LAUNCH("csr_xwin_kernel (16-bit columns)");
-    return SPMV_SUCCESS;
+    const bool missing = d.nnz > 0 && (!blk_base || !col_off);
+    return run_xwin(d, row_ptr, MakeCol16{blk_base, col_off, col_esc}, val, x, y, lanes_per_row, rows_per_window,
+                    win, xcap, "spmv_csr16_run_xwin",
+                    missing ? "spmv_csr16_run_xwin: missing index arrays" : nullptr,
+                    "csr_xwin_kernel (16-bit columns)");
 }
 
 // CSR with fp32 values (8 bytes per entry instead of
@@ -1209,17 +1149,8 @@ extern "C" int spmv_csr_f32v_run_xwin(spmv_dims d, const int64_t *row_ptr, const
                                       const double *x, double *y, int lanes_per_row, int32_t rows_per_window,
                                       const void *win, int32_t xcap)
 {
-    int L = 0;
-    int64_t gpw = 0;
-    int rc = xwin_args(d, rows_per_window, win, xcap, lanes_per_row, &L, &gpw, "spmv_csr_f32v_run_xwin");
-    if (rc != SPMV_SUCCESS || d.n_rows == 0)
-        return rc;
-    SPMV_GUARD(d);
-    rc = launch_xwin_any(d, L, row_ptr, MakeCol32{col}, val, x, y, (const int2 *)win, xcap, gpw);
-    if (rc != SPMV_SUCCESS)
-        return rc;
-    SPMV_CHECK_LAUNCH("csr_xwin_kernel (fp32 values)");
-    return SPMV_SUCCESS;
+    return run_xwin(d, row_ptr, MakeCol32{col}, val, x, y, lanes_per_row, rows_per_window, win, xcap,
+                    "spmv_csr_f32v_run_xwin", nullptr, "csr_xwin_kernel (fp32 values)");
 }
 
 extern "C" size_t spmv_csr_tiled_ws_bytes(int64_t n_rows, int64_t nnz)

@@ -62,7 +62,6 @@ static int env_switch(const char *name)
 static std::atomic<int> g_opt_xwin_remap{env_switch("SPMV_XWIN_REMAP")};
 static std::atomic<int> g_opt_xcd_remap{env_switch("SPMV_XCD_REMAP")};
 static std::atomic<int> g_opt_stream_nt{env_switch("SPMV_STREAM_NT")};
-static std::atomic<int> g_opt_csr_prefetch{env_switch("SPMV_CSR_PREFETCH")};
 static std::atomic<int> g_opt_csr_col16{env_switch("SPMV_CSR_COL16")};
 
 static std::atomic<int> *option_slot(int option)
@@ -74,8 +73,6 @@ static std::atomic<int> *option_slot(int option)
         return &g_opt_xcd_remap;
     case SPMV_OPT_STREAM_NT:
         return &g_opt_stream_nt;
-    case SPMV_OPT_CSR_PREFETCH:
-        return &g_opt_csr_prefetch;
     case SPMV_OPT_CSR_COL16:
         return &g_opt_csr_col16;
     default:
@@ -93,12 +90,6 @@ bool xwin_remap(bool dflt)
 // measured 1-2 % faster than the contiguous-per-XCD remap
 // (profiles/round1/sweeps.md).
 bool xcd_remap_enabled() { return g_opt_xcd_remap.load(std::memory_order_relaxed) == 1; }
-
-bool csr_prefetch(bool dflt)
-{
-    const int v = g_opt_csr_prefetch.load(std::memory_order_relaxed);
-    return v < 0 ? dflt : v == 1;
-}
 
 bool csr_col16(bool dflt)
 {

@@ -108,6 +108,9 @@ def test_plan_opts_defaults_and_options():
         sa.set_option(name, old)
     assert lib.spmv_set_option(99, 0) == sa.OTHER_ERROR and lib.spmv_get_option(99) == -2
     assert lib.spmv_set_option(1, 2) == sa.OTHER_ERROR
+    # 4 is a retired option's number, left unused: unknown like any other
+    assert lib.spmv_set_option(4, 0) == sa.OTHER_ERROR
+    assert lib.spmv_get_option(4) == -2
 
 
 def test_plan_without_gpu_is_a_device_error():
