@@ -35,7 +35,7 @@ LIB_HIP  := $(LIBDIR)/libspmv_hip.so
 LIB_HOST := $(LIBDIR)/libspmv_host.so
 ORACLE   := oracle/liboracle.so
 
-.PHONY: all default lib oracle probes lab test-san test-san-transpose test-san-transpose-multi test-san-multi-plan test-san-symmetric test-cpu test-gpu clean $(TARGETS)
+.PHONY: all default lib oracle probes lab test-san test-san-transpose test-san-transpose-multi test-san-multi-plan test-san-symmetric test-san-symmetric-multi test-cpu test-gpu clean $(TARGETS)
 
 default: all
 all: lib $(TARGETS) probes
@@ -172,6 +172,17 @@ build/san/symmetric_harness: tests/san/symmetric_harness.c $(HOST_SRC) include/s
 
 test-san-symmetric: build/san/symmetric_harness
 	$(SANENV) ASAN_OPTIONS=detect_leaks=1:exitcode=99 build/san/symmetric_harness tests/golden/*.mtx
+
+# the host side of the multi-vector symmetric product
+# (spmv_cpu_csr_sym_multi) under ASan + UBSan: a stand-alone program over the
+# square fixtures with exactly-sized allocations, ld == k and ld > k
+# (tests/san/symmetric_multi_harness.c)
+build/san/symmetric_multi_harness: tests/san/symmetric_multi_harness.c $(HOST_SRC) include/spmv_host.h include/spmv_rc.h
+	@mkdir -p build/san
+	$(CC) -std=c11 -Wall -Wextra -Werror -fopenmp -Iinclude $(SANFLAGS) $< $(HOST_SRC) -o $@ -lm
+
+test-san-symmetric-multi: build/san/symmetric_multi_harness
+	$(SANENV) ASAN_OPTIONS=detect_leaks=1:exitcode=99 build/san/symmetric_multi_harness tests/golden/*.mtx
 
 test-gpu: all oracle
 	python -m pytest tests/ -x -q -m gpu

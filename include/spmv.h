@@ -255,7 +255,10 @@ int spmv_plan_multi_supported(const spmv_plan *p);
  * With SPMV_T_COPY the mode and options extend to the inner plan over A^T
  * (rule values resolved against the inner plan's own lanes), whichever of
  * spmv_plan_prepare_multi / spmv_plan_prepare_transpose comes first, and
- * end with either; scatter mode is not affected.
+ * end with either; scatter mode is not affected.  With SPMV_S_EXPAND they
+ * extend in the same way to the inner plan over A = S + S^T - diag S
+ * (spmv_plan_prepare_symmetric, spmv_plan_run_sym_multi), whose balanced state
+ * is reported in spmv_symmetric_multi_info; fused mode is not affected.
  * spmv_plan_run_multi itself is unchanged: no allocation, no synchronisation,
  * capturable.  The partial workspace belongs to the plan, so two balanced
  * runs of ONE plan must not overlap in time, on different streams either
@@ -465,7 +468,8 @@ int spmv_plan_get_transpose_multi_info(const spmv_plan *p, spmv_transpose_multi_
  * square, (expand) a column outside [0, n).  It is independent of
  * spmv_plan_prepare_transpose and spmv_plan_prepare_multi: the three keep
  * separate buffers and separate byte reports, and spmv_plan_get_info is
- * unchanged.
+ * unchanged (a balanced plan's mode extends to expand mode's inner plan, for
+ * spmv_plan_run_sym_multi only: spmv_plan_run_sym never uses those tables).
  * spmv_plan_run_sym follows the run conventions: asynchronous on `stream`,
  * no allocation and no synchronisation (it can be captured into a graph on
  * one stream), codes of spmv_rc.h.
@@ -511,6 +515,94 @@ int spmv_plan_run_sym(const spmv_plan *p, const double *x, double *y, void *stre
  * SPMV_OTHER_ERROR for a NULL argument or a plan in another mode.          */
 int spmv_plan_get_symmetric_arrays(const spmv_plan *p, const int64_t **row_ptr, const int32_t **col,
                                    const double **val, int64_t *nnz);
+/* Y = (S + S^T - diag S)·X for k vectors stored row-major, the layout of
+ * spmv_plan_run_multi: X[c*ldx + j], Y[i*ldy + j], c, i < n;  j < k;
+ * ldx >= k, ldy >= k (elements), k >= 1.  Needs spmv_plan_prepare_symmetric
+ * first and runs in whichever mode was prepared; there is no further prepare
+ * call (spmv_plan_prepare_symmetric builds what this run needs too).
+ *
+ * The conventions above hold: device pointers, asynchronous on `stream`, no
+ * allocation and no synchronisation inside the call (it can be captured into
+ * a graph on one stream), codes of spmv_rc.h, a message in spmv_last_error().
+ *   - Y[i*ldy + j], j < k, is fully overwritten (rows and columns without
+ *     entries get 0.0); NO element with j >= k and nothing at or past row n
+ *     is written.
+ *   - NO byte outside X[c*ldx .. c*ldx + k) is read for any c.
+ *   - X and Y need 8-byte alignment only and any ldx, ldy >= k: every load
+ *     of X and every add to Y is 8 bytes wide.
+ *   - X and Y must not overlap; runs of one plan must be serialised.
+ *   - Reads the caller's row_ptr, col and val, never the plan's
+ *     hot-renumbered column copy.  A column outside [0, n) is dropped whole,
+ *     as in spmv_plan_run_sym.
+ *   - SPMV_OTHER_ERROR with a message, before any device work (Y is left
+ *     untouched): NULL plan, a plan that was not prepared (every plan that is
+ *     not CSR or not square: it cannot be), k < 1, ldx < k or ldy < k, NULL X
+ *     or Y with n > 0.
+ * SPMV_S_EXPAND: spmv_plan_run_multi on the inner forward plan over A and
+ *     nothing else, so its bit rule carries over: the bits of column j are
+ *     those of spmv_plan_run_multi on a default forward CSR plan over the
+ *     arrays of spmv_plan_get_symmetric_arrays, independent of k, of j's place
+ *     in its block of 8 and of ldx / ldy.  An outer plan prepared with
+ *     spmv_plan_prepare_multi(SPMV_M_BALANCED) runs the inner plan balanced
+ *     too, whichever of the two prepares comes first (rule values are resolved
+ *     against the inner plan's own lanes; SPMV_M_NONE ends it on the inner
+ *     plan too): the bits of that forward plan prepared with the same options.
+ *     spmv_multi_info is unchanged; the inner plan's balanced state is
+ *     reported in spmv_symmetric_multi_info.  spmv_plan_run_sym never uses
+ *     the balanced tables.
+ * SPMV_S_FUSED: csr_sym_multi_kernel<KV>, KV in {1, 2, 4, 8}, one workgroup
+ *     per 128 rows on the window table spmv_plan_run_sym uses (owned_bytes
+ *     stays 8 * blocks).  The matrix is streamed once per block of up to 8
+ *     vectors (ceil(k/8) passes, pass b on X + 8b, Y + 8b); a block of r
+ *     remaining vectors runs the smallest KV >= r and neither loads nor adds
+ *     its unused columns.  Y's live columns are zeroed once before the first
+ *     pass.  A union window of at most cap_cols[w] = 4,096 / KV columns: LDS
+ *     holds X[lo..hi] as span * KV doubles and an accumulator of the same
+ *     size (66,576 bytes of LDS at the most, two workgroups per CU); entry
+ *     (r, c, v) adds v X[c][j] to acc[r - lo][j] and, when c != r, v X[r][j]
+ *     to acc[c - lo][j] (the row products of a wave's consecutive entries are
+ *     summed per row across the wave first); the accumulator is added to Y
+ *     with one fp64 atomic per non-zero word, consecutive lanes on
+ *     consecutive words.  A wider union: LDS holds the block's 128 x KV values
+ *     of X and 128 x KV row sums, X[c][j] is gathered from global memory and
+ *     every mirrored product is added straight into Y[c][j] with a global
+ *     fp64 atomic; the row sums are flushed at the end.  From KV = 4 on KV / 2
+ *     lanes share an entry (handed round by DPP), two columns each.  Results
+ *     are NOT bitwise reproducible from run to run; Y must be ordinary device
+ *     memory.  The k = 1 result need not have spmv_plan_run_sym's bits.
+ *     flush_entries[w] counts the rows of Y the flushes of one pass address
+ *     (the window blocks' spans plus the rows of the wide blocks).
+ * Which to call (MI355X, cold, one run on one box, profiles/symmetric/README.md;
+ * the yardstick is k calls of spmv_plan_run_sym on the same plan): one call was
+ * 1.50 / 2.29 / 3.60 times faster at k = 2 / 4 / 8 in fused mode on the
+ * cant-like lower triangle and 1.16 / 1.33 / 1.95 times on the 32-copy batch;
+ * 1.28 / 1.94 / 2.61 and 1.08 / 1.73 / 2.08 times in expand mode.  Fused stays
+ * slower than expand in absolute time at every k (0.0551 against 0.0323 ms at
+ * k = 8 on one matrix, 1.198 against 0.831 ms on the batch): it is for plans
+ * that are fused for memory.  In EXPAND mode on the lower triangle of a
+ * power-law R-MAT one call on an unprepared plan was 5 to 20 times SLOWER than
+ * k calls (0.58-0.62 ms: the hub rows of A are walked by two lanes each):
+ * prepare the plan with spmv_plan_prepare_multi(SPMV_M_BALANCED) there, after
+ * which one call took 0.036 / 0.040 / 0.045 ms at k = 2 / 4 / 8, 0.83 / 1.52 /
+ * 2.66 times the speed of k calls (at k = 2 the two calls are still the faster
+ * way).  One vector belongs to spmv_plan_run_sym.  Not measured: fused mode on
+ * the wide path (power-law columns), k > 8, ld > k.                          */
+int spmv_plan_run_sym_multi(const spmv_plan *p, int32_t k, const double *X, int64_t ldx,
+                            double *Y, int64_t ldy, void *stream);
+typedef struct spmv_symmetric_multi_info {
+    int32_t mode;             /* enum spmv_symmetric_mode */
+    int32_t reserved;
+    int32_t cap_cols[4];      /* fused: widest union window (columns) on the window path of the
+                                 kernel of width 1, 2, 4, 8; expand: 0 */
+    int64_t window_blocks[4]; /* fused: row blocks within that span, per width */
+    int64_t flush_entries[4]; /* fused: rows of Y addressed by the flushes of one pass, per width */
+    int64_t long_rows;        /* expand: the inner plan's balanced state (spmv_plan_prepare_multi), */
+    int64_t segments;         /*   as spmv_multi_info's fields of these names; 0 when not balanced  */
+    int64_t multi_owned_bytes;
+    char kernel[64];          /* fused: csr_sym_multi_kernel; expand: the inner plan's multi-vector kernel */
+} spmv_symmetric_multi_info;
+/* An unprepared plan answers all zeros and an empty kernel name. */
+int spmv_plan_get_symmetric_multi_info(const spmv_plan *p, spmv_symmetric_multi_info *info);
 int spmv_plan_get_info(const spmv_plan *p, spmv_plan_info *info);
 /* Frees what the plan allocated (never the caller's arrays). */
 int spmv_plan_destroy(spmv_plan *p);

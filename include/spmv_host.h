@@ -341,6 +341,18 @@ int spmv_cpu_csr_t(int64_t n_rows, int64_t n_cols, const int64_t *row_ptr,
  * array that would be read or written.                                     */
 int spmv_cpu_csr_sym(int64_t n, const int64_t *row_ptr, const int32_t *col, const double *val,
                      const double *x, double *y);
+/* Y = (S + S^T - diag S) X for k >= 1 vectors stored row-major, the layout of
+ * spmv_plan_run_sym_multi (spmv.h): X[c*ldx + j], Y[i*ldy + j], c, i < n,
+ * j < k; ldx >= k, ldy >= k.  Serial, the k-vector form of spmv_cpu_csr_sym:
+ * column j has that loop's bits on column j.  Writes nothing for j >= k or at
+ * or past row n and reads nothing of X outside [c*ldx, c*ldx + k).  The CPU
+ * statement of spmv_plan_run_sym_multi and the checker of
+ * tools/spmvsym_bench.py --vectors, never a device fallback.
+ * SPMV_OTHER_ERROR, before Y is touched, for a negative size, k < 1, a leading
+ * dimension below k, a column outside [0, n) or a NULL array that would be
+ * read or written.                                                          */
+int spmv_cpu_csr_sym_multi(int64_t n, const int64_t *row_ptr, const int32_t *col, const double *val,
+                           int32_t k, const double *X, int64_t ldx, double *Y, int64_t ldy);
 /* Y = A^T X for k >= 1 vectors stored row-major, the layout of
  * spmv_plan_run_t_multi (spmv.h): X[r*ldx + j], r < n_rows; Y[c*ldy + j],
  * c < n_cols; j < k; ldx >= k, ldy >= k.  Serial: zeroes Y[c*ldy + j], j < k,

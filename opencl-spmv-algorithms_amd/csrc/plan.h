@@ -49,6 +49,11 @@ struct SymState {
     int32_t mode = 0;         // enum spmv_symmetric_mode
     int32_t xcap = 0;         // fused: widest union window that fits the cap
     int64_t blocks = 0, win_blocks = 0, flush = 0;
+    // fused, multi-vector run (csr_sym_multi_kernel of width 1, 2, 4, 8): the
+    // widest union that fits the width's cap, the blocks that fit and the Y
+    // rows the flushes address per pass
+    int32_t mxcap[4] = {0, 0, 0, 0};
+    int64_t mwin[4] = {0, 0, 0, 0}, mflush[4] = {0, 0, 0, 0};
     void *win = nullptr;      // fused: int2 {lo, hi} union window per row block
     int64_t nnz_a = 0;        // expand: entries of A = S + S^T - diag S
     int64_t *ptr = nullptr;   // expand: A as CSR (ptr[n+1], col/val[nnz_a])
@@ -145,4 +150,9 @@ struct WindowTally {
     int32_t widest = 0;
 };
 WindowTally windows_tally(const int2 *h, int64_t n, int32_t cap);
+
+// Y[i*ldy + j] = 0.0 for i < n, j < k on `st`, the first step of the scattering
+// multi-vector runs (transpose.hip): a memset when ldy == k, else a kernel that
+// leaves the gaps alone.  `who` = the entry point, for the message.
+int zero_cols(int64_t n, int32_t k, double *Y, int64_t ldy, hipStream_t st, const char *who);
 }  // namespace spmv

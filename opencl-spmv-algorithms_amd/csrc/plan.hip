@@ -984,7 +984,12 @@ int spmv_plan_prepare_multi(spmv_plan *p, int mode, const spmv_multi_opts *o)
         if (hipStreamSynchronize(st) != hipSuccess)
             return fail_msg(SPMV_PROGRAM_ERROR, "spmv_plan_prepare_multi: synchronise");
         plan_multi_free(p);
-        return p->t.inner ? spmv_plan_prepare_multi(p->t.inner, SPMV_M_NONE, nullptr) : SPMV_SUCCESS;
+        for (spmv_plan *inner : {p->t.inner, p->sym.inner}) {
+            const int rc = inner ? spmv_plan_prepare_multi(inner, SPMV_M_NONE, nullptr) : SPMV_SUCCESS;
+            if (rc != SPMV_SUCCESS)
+                return rc;
+        }
+        return SPMV_SUCCESS;
     }
     if (mode == p->m.mode && req.long_len == p->m.req.long_len && req.seg_len == p->m.req.seg_len)
         return SPMV_SUCCESS;
@@ -993,9 +998,12 @@ int spmv_plan_prepare_multi(spmv_plan *p, int mode, const spmv_multi_opts *o)
     const int32_t seg_len = req.seg_len >= 1 ? req.seg_len : kMultiSegLen;
     MultiState next;
     int rc = multi_build(p, long_len, seg_len, &next.bal, &next.long_entries, &next.owned);
-    // copy mode: the inner plan over A^T follows (it keeps its state when refused)
+    // copy mode: the inner plan over A^T follows (it keeps its state when
+    // refused); so does the symmetric expand mode's inner plan over A
     if (rc == SPMV_SUCCESS && p->t.inner)
         rc = spmv_plan_prepare_multi(p->t.inner, mode, &req);
+    if (rc == SPMV_SUCCESS && p->sym.inner)
+        rc = spmv_plan_prepare_multi(p->sym.inner, mode, &req);
     if (rc == SPMV_SUCCESS && hipStreamSynchronize(st) != hipSuccess)
         rc = fail_msg(SPMV_PROGRAM_ERROR, "spmv_plan_prepare_multi: synchronise");
     if (rc != SPMV_SUCCESS)  // the plan stays as it was

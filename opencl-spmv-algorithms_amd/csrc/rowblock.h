@@ -3,8 +3,11 @@
 // kernel (symmetric.hip).  One workgroup per block stages the block's row
 // offsets in LDS and streams its entries ONCE, coalesced, whatever the row
 // lengths; what is done with an entry (the per-entry body) and the LDS budget
-// of each kernel stay in its own file.
+// of each kernel stay in its own file.  The lane geometry the multi-vector
+// kernels of both files share (lanes per entry, DPP broadcast) is at the end.
 #pragma once
+
+#include <type_traits>
 
 #include "common.h"
 
@@ -123,6 +126,52 @@ __device__ __forceinline__ void rb_flush(const double *acc, int span, double *__
         if (s != 0.0)
             unsafeAtomicAdd(&y[lo + j], s);
     }
+}
+
+// ---- the lane geometry of the multi-vector kernels on this core
+// (csr_t_multi_kernel<KV>, csr_sym_multi_kernel<KV>; KV = vectors per pass)
+constexpr int kTWidths[4] = {1, 2, 4, 8};
+
+// lanes that share one entry: two columns per lane from KV = 4 on, as
+// csr_multi_kernel; the P lanes of an entry are neighbours inside one quad
+template <int KV>
+constexpr int t_multi_p()
+{
+    return KV >= 4 ? KV / 2 : 1;
+}
+
+// The value of lane Q of every P-lane group (P = 2 or 4, groups aligned inside
+// a quad) by a DPP quad_perm move: a VALU operand modifier, no LDS traffic.
+// Called in uniform control flow only (every lane of the wave active).
+template <int P, int Q>
+constexpr int group_bcast_ctrl()
+{
+    static_assert((P == 2 || P == 4) && Q < P, "groups inside one quad");
+    return P == 4 ? Q * 0x55 : (Q | Q << 2 | (2 + Q) << 4 | (2 + Q) << 6);
+}
+
+template <int P, int Q>
+__device__ __forceinline__ int group_bcast(int v)
+{
+    return __builtin_amdgcn_mov_dpp(v, group_bcast_ctrl<P, Q>(), 0xF, 0xF, false);
+}
+
+template <int P, int Q>
+__device__ __forceinline__ double group_bcast(double v)
+{
+    const long long b = __double_as_longlong(v);
+    const int lo = group_bcast<P, Q>((int)b);
+    const int hi = group_bcast<P, Q>((int)(b >> 32));
+    return __longlong_as_double((long long)(((unsigned long long)(unsigned)hi << 32) | (unsigned)lo));
+}
+
+template <typename F>
+inline void with_each_width(F &&f)
+{
+    f(std::integral_constant<int, 1>{});
+    f(std::integral_constant<int, 2>{});
+    f(std::integral_constant<int, 4>{});
+    f(std::integral_constant<int, 8>{});
 }
 
 }  // namespace spmv

@@ -27,7 +27,14 @@
 //       flags), spmv_dev_csr_from_coo over it, and a forward CSR plan with
 //       default options over the result.
 // Both read the caller's row_ptr / col / val, never the plan's hot-renumbered
-// column copy, and are independent of the transposed and multi-vector modes.
+// column copy, and are independent of the transposed mode.
+//
+// The multi-vector run Y = (S + S^T - diag S) X (spmv_plan_run_sym_multi)
+// works in whichever mode was prepared: expand is spmv_plan_run_multi on the
+// inner plan (the outer plan's balanced mode, spmv_plan_prepare_multi in
+// plan.hip, extends to it, whichever is prepared first); fused is
+// csr_sym_multi_kernel<KV>, the window kernel's geometry with KV vectors per
+// pass (below).  spmv_plan_prepare_symmetric builds what it needs too.
 #include <hipcub/hipcub.hpp>
 #include <stdio.h>
 #include <stdlib.h>
@@ -182,6 +189,191 @@ __global__ __launch_bounds__(kBlock) void csr_sym_window_kernel(int64_t n, const
     }
 }
 
+// ------------------------------------------------- multi-vector fused run
+// Y = (S + S^T - diag S) X (spmv_plan_run_sym_multi): the geometry of
+// csr_sym_window_kernel with KV vectors per pass.  The window and the
+// accumulator hold span * KV words each, word (c - lo) * KV + j, so a block
+// takes the window path when span * KV <= kSMultiCap.
+#ifndef SPMV_S_MULTI_CAP
+#define SPMV_S_MULTI_CAP 4096  // an A/B build may override it (profiles/symmetric/README.md)
+#endif
+constexpr int32_t kSMultiCap = SPMV_S_MULTI_CAP;  // doubles per LDS array (2 arrays: 64 KiB)
+static_assert(kSMultiCap >= kRbRows * 8, "the wide path's two arrays of kRbRows x KV fit the same LDS");
+
+// wave_run_add for lanes that hold CPL sums each (KV <= 2: every lane its own
+// entry, lanes in entry order): the runs of equal keys are summed across the
+// wave and the last lane of a run adds its CPL sums to acc[key + i], i < live.
+// key = -1: nothing to add (only the lanes past the stream's end, which are
+// the wave's last).  Called in uniform control flow.
+template <int CPL>
+__device__ __forceinline__ void wave_run_add_cols(double *acc, int key, double (&p)[CPL], int32_t live)
+{
+    const int lane = (int)threadIdx.x % kWave;
+#pragma unroll
+    for (int off = 1; off < kWave; off <<= 1) {
+        const int k = __shfl_up(key, off);
+        const bool same = lane >= off && k == key;
+#pragma unroll
+        for (int i = 0; i < CPL; ++i) {
+            const double t = __shfl_up(p[i], off);
+            if (same)
+                p[i] += t;
+        }
+    }
+    const int next = __shfl_down(key, 1);
+    if (key >= 0 && (lane == kWave - 1 || next != key)) {
+#pragma unroll
+        for (int i = 0; i < CPL; ++i)
+            if (i < live)
+                atomicAdd(&acc[key + i], p[i]);
+    }
+}
+
+// One lane's CPL columns [j0, j0 + CPL) of one entry (column c, value v, block
+// row r; r = -1: a lane past the stream's end).
+// WIN = true: xs = X[lo .. lo + bound) x KV and acc of the same shape, both
+// LDS; an entry whose row or column lies outside the window is dropped whole.
+// WIN = false: xs = X of the block's rows and acc their kRbRows x KV sums,
+// both LDS; X[c] comes from global memory, the mirrored products go straight
+// into Y[c]; bound = n, a column outside [0, n) is dropped whole.
+// Columns j >= live (a ragged last block of vectors) are neither read nor
+// added.  The row products: KV <= 2 (one lane per entry) sums them per row
+// across the wave first (wave_run_add_cols); from KV = 4 on (P lanes per
+// entry) they are plain LDS adds, measured faster there
+// (profiles/symmetric/README.md).
+template <int KV, bool WIN>
+__device__ __forceinline__ void sym_multi_add(const double *xs, double *acc, const double *__restrict__ X,
+                                              int64_t ldx, double *__restrict__ Y, int64_t ldy, int64_t r0,
+                                              int32_t lo, uint32_t bound, int32_t live, int j0, int32_t c, double v,
+                                              int r)
+{
+    constexpr int P = t_multi_p<KV>();
+    constexpr int CPL = KV / P;
+    double p[CPL];
+#pragma unroll
+    for (int i = 0; i < CPL; ++i)
+        p[i] = 0.0;
+    int key = -1;
+    if constexpr (WIN) {
+        const uint32_t jr = (uint32_t)(r0 + r) - (uint32_t)lo;
+        const uint32_t jc = (uint32_t)c - (uint32_t)lo;
+        if (r >= 0 && jr < bound) {
+            key = (int)jr * KV + j0;
+            if (jc < bound) {
+#pragma unroll
+                for (int i = 0; i < CPL; ++i) {
+                    const int j = j0 + i;
+                    if (j < live) {
+                        p[i] = v * xs[jc * KV + j];
+                        if (jc != jr)
+                            atomicAdd(&acc[jc * KV + j], v * xs[jr * KV + j]);
+                    }
+                }
+            }
+        }
+    } else {
+        if (r >= 0) {
+            key = r * KV + j0;
+            if ((uint32_t)c < bound) {
+#pragma unroll
+                for (int i = 0; i < CPL; ++i) {
+                    const int j = j0 + i;
+                    if (j < live) {
+                        p[i] = v * X[(int64_t)c * ldx + j];
+                        if ((int64_t)c != r0 + r)
+                            unsafeAtomicAdd(&Y[(int64_t)c * ldy + j], v * xs[r * KV + j]);
+                    }
+                }
+            }
+        }
+    }
+    if constexpr (P == 1) {
+        wave_run_add_cols<CPL>(acc, key, p, live);
+    } else if (key >= 0) {
+#pragma unroll
+        for (int i = 0; i < CPL; ++i)
+            if (j0 + i < live)
+                atomicAdd(&acc[key + i], p[i]);
+    }
+}
+
+// The P rounds of one step, as t_multi_rounds (transpose.hip): round Q hands
+// entry Q of every P-lane group to the group's P lanes.
+template <int KV, bool WIN, int Q = 0>
+__device__ __forceinline__ void sym_multi_rounds(const double *xs, double *acc, const double *__restrict__ X,
+                                                 int64_t ldx, double *__restrict__ Y, int64_t ldy, int64_t r0,
+                                                 int32_t lo, uint32_t bound, int32_t live, int j0, int32_t c,
+                                                 double v, int r)
+{
+    constexpr int P = t_multi_p<KV>();
+    if constexpr (P == 1) {
+        sym_multi_add<KV, WIN>(xs, acc, X, ldx, Y, ldy, r0, lo, bound, live, j0, c, v, r);
+    } else if constexpr (Q < P) {
+        sym_multi_add<KV, WIN>(xs, acc, X, ldx, Y, ldy, r0, lo, bound, live, j0, group_bcast<P, Q>(c),
+                               group_bcast<P, Q>(v), group_bcast<P, Q>(r));
+        sym_multi_rounds<KV, WIN, Q + 1>(xs, acc, X, ldx, Y, ldy, r0, lo, bound, live, j0, c, v, r);
+    }
+}
+
+// One workgroup per block of kRbRows rows, one pass over the block's entries
+// for `live` <= KV vectors (X, Y: the pass's first column).  LDS: the block's
+// kRbRows + 1 row offsets, then two arrays of span x KV doubles (X window,
+// accumulator) when the union spans at most `cap` = kSMultiCap / KV columns,
+// else two arrays of kRbRows x KV (the rows' X, their sums).  Every load of X
+// and every add to Y is 8 bytes wide.
+template <int KV>
+__global__ __launch_bounds__(kBlock) void csr_sym_multi_kernel(int64_t n, const int64_t *__restrict__ ptr,
+                                                               const int32_t *__restrict__ col,
+                                                               const double *__restrict__ val,
+                                                               const double *__restrict__ X, int64_t ldx,
+                                                               double *__restrict__ Y, int64_t ldy,
+                                                               const int2 *__restrict__ win, int32_t cap, int32_t live)
+{
+    extern __shared__ double s_mem[];
+    int64_t *s_ptr = reinterpret_cast<int64_t *>(s_mem);
+    double *xs = s_mem + kRbPtr;
+    constexpr int P = t_multi_p<KV>();
+    const int tid = (int)threadIdx.x;
+    const int j0 = (tid % P) * (KV / P);
+    RowBlock b;
+    if (!rb_open(n, ptr, win, s_ptr, &b))
+        return;
+    const int2 w = b.w;
+    const int span = b.span, nr = b.nr;
+    const int64_t r0 = b.r0;
+    // as csr_sym_window_kernel: a window this plan did not record is not used
+    if (w.x < 0 || w.y >= n || w.x > r0 || w.y < r0 + nr - 1)
+        return;
+    const bool window = span <= cap;
+    const int words = (window ? span : nr) * KV;
+    const int64_t first = window ? (int64_t)w.x : r0;  // the row of X and Y that word 0 stands for
+    double *acc = xs + (window ? span : kRbRows) * KV;
+    for (int i = tid; i < words; i += kBlock) {
+        const int j = i % KV;
+        if (j < live)
+            xs[i] = X[(first + i / KV) * ldx + j];
+        acc[i] = 0.0;
+    }
+    __syncthreads();
+    rb_stream<true>(s_ptr, nr, col, val, [&](bool mine, int64_t e, int32_t c, double v) {
+        const int r = mine ? rb_row_of(s_ptr, nr, e) : -1;
+        if (window)
+            sym_multi_rounds<KV, true>(xs, acc, X, ldx, Y, ldy, r0, w.x, (uint32_t)span, live, j0, c, v, r);
+        else
+            sym_multi_rounds<KV, false>(xs, acc, X, ldx, Y, ldy, r0, 0, (uint32_t)n, live, j0, c, v, r);
+    });
+    __syncthreads();
+    // the flush: thread t takes accumulator words t, t + 256, ...: with
+    // ldy == KV a wave instruction covers 512 contiguous bytes of Y.  Sums
+    // still exactly 0.0 add nothing to the zeroed Y.
+    for (int i = tid; i < words; i += kBlock) {
+        const int j = i % KV;
+        const double s = acc[i];
+        if (j < live && s != 0.0)
+            unsafeAtomicAdd(&Y[(first + i / KV) * ldy + j], s);
+    }
+}
+
 // ------------------------------------------------------------ expand mode
 // Entry e of the CSR: its row (the last r with ptr[r] <= e) and whether it is
 // off the diagonal; flag[nnz] = 0 closes the prefix sum.  A column outside
@@ -268,6 +460,13 @@ size_t fused_lds(int32_t xcap)
     return (size_t)(kRbPtr + 2 * (xcap > kRbRows ? xcap : kRbRows)) * sizeof(double);
 }
 
+// dynamic LDS bytes of a csr_sym_multi_kernel<kv> launch whose widest window
+// block spans `span` columns (the wide path needs kRbRows x kv per array)
+constexpr size_t sym_multi_lds(int kv, int64_t span)
+{
+    return (size_t)(kRbPtr + 2 * (span > kRbRows ? span : kRbRows) * kv) * sizeof(double);
+}
+
 int prepare_fused(const spmv_plan *p, SymState *s)
 {
     const spmv_dims &d = p->d;
@@ -294,7 +493,30 @@ int prepare_fused(const spmv_plan *p, SymState *s)
             const int64_t r0 = b * kRbRows;
             s->flush += d.n_rows - r0 < kRbRows ? d.n_rows - r0 : kRbRows;
         }
+    for (int w = 0; w < 4; ++w) {  // the multi-vector kernels: span * KV words per array
+        const int32_t cap = kSMultiCap / kTWidths[w];
+        const WindowTally multi = windows_tally(h, blocks, cap);
+        s->mwin[w] = multi.blocks;
+        s->mxcap[w] = multi.widest;
+        s->mflush[w] = multi.spans;
+        for (int64_t b = 0; b < blocks; ++b)
+            if ((int64_t)h[b].y - h[b].x + 1 > cap) {
+                const int64_t r0 = b * kRbRows;
+                s->mflush[w] += d.n_rows - r0 < kRbRows ? d.n_rows - r0 : kRbRows;
+            }
+    }
     free(h);
+    // a launch of the widest fitting window may need more than the default
+    // 64 KiB of dynamic LDS: allowed here, once, so that a run only launches
+    hipError_t e = hipSuccess;
+    with_each_width([&](auto KV) {
+        constexpr int kv = decltype(KV)::value;
+        if (e == hipSuccess)
+            e = hipFuncSetAttribute(reinterpret_cast<const void *>(csr_sym_multi_kernel<kv>),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)sym_multi_lds(kv, kSMultiCap / kv));
+    });
+    if (e != hipSuccess)
+        return fail(SPMV_PROGRAM_ERROR, "spmv_plan_prepare_symmetric: dynamic LDS of csr_sym_multi_kernel", e);
     return SPMV_SUCCESS;
 }
 
@@ -355,7 +577,10 @@ int prepare_expand(const spmv_plan *p, SymState *s)
     if ((rc = spmv_dev_csr_from_coo(da, (const int32_t *)c_row.p, (const int32_t *)c_col.p, (const double *)c_val.p,
                                     s->ptr, s->col, s->val)) != SPMV_SUCCESS)
         return rc;
-    return spmv_plan_csr(da, s->ptr, s->col, s->val, nullptr, &s->inner);
+    if ((rc = spmv_plan_csr(da, s->ptr, s->col, s->val, nullptr, &s->inner)) != SPMV_SUCCESS)
+        return rc;
+    // a balanced outer plan (spmv_plan_prepare_multi) extends to the inner one
+    return p->m.mode != SPMV_M_NONE ? spmv_plan_prepare_multi(s->inner, p->m.mode, &p->m.req) : SPMV_SUCCESS;
 }
 
 int launch_fused(const spmv_plan *p, const double *x, double *y, hipStream_t st)
@@ -372,6 +597,32 @@ int launch_fused(const spmv_plan *p, const double *x, double *y, hipStream_t st)
     hipLaunchKernelGGL(csr_sym_window_kernel, dim3((unsigned)s.blocks), dim3(kBlock), fused_lds(s.xcap), st, d.n_rows,
                        p->ptr, p->col, p->val, x, y, (const int2 *)s.win, kSCap);
     SPMV_CHECK_LAUNCH("csr_sym_window_kernel");
+    return SPMV_SUCCESS;
+}
+
+// Y zeroed once (columns j < k only), then ceil(k/8) passes of the narrowest
+// kernel that holds the pass's vectors
+int launch_fused_multi(const spmv_plan *p, int32_t k, const double *X, int64_t ldx, double *Y, int64_t ldy,
+                       hipStream_t st)
+{
+    const spmv_dims &d = p->d;
+    const SymState &s = p->sym;
+    const int rc = zero_cols(d.n_rows, k, Y, ldy, st, "spmv_plan_run_sym_multi");
+    if (rc != SPMV_SUCCESS)
+        return rc;
+    if (!s.win || d.nnz == 0 || d.n_rows == 0)
+        return SPMV_SUCCESS;
+    for (int32_t j0 = 0; j0 < k; j0 += 8) {
+        const int32_t live = k - j0 < 8 ? k - j0 : 8;
+        const int w = live > 4 ? 3 : live > 2 ? 2 : live - 1;  // width kTWidths[w] >= live
+        with_int<1, 2, 4, 8>(kTWidths[w], [&](auto KV) {
+            constexpr int kv = decltype(KV)::value;
+            hipLaunchKernelGGL(csr_sym_multi_kernel<kv>, dim3((unsigned)s.blocks), dim3(kBlock),
+                               sym_multi_lds(kv, s.mxcap[w]), st, d.n_rows, p->ptr, p->col, p->val, X + j0, ldx,
+                               Y + j0, ldy, (const int2 *)s.win, kSMultiCap / kv, live);
+        });
+        SPMV_CHECK_LAUNCH("csr_sym_multi_kernel");
+    }
     return SPMV_SUCCESS;
 }
 
@@ -477,6 +728,50 @@ int spmv_plan_run_sym(const spmv_plan *p, const double *x, double *y, void *stre
         return spmv_plan_run(p->sym.inner, x, y, stream);
     SPMV_GUARD(p->d);
     return launch_fused(p, x, y, (hipStream_t)stream);
+}
+
+int spmv_plan_get_symmetric_multi_info(const spmv_plan *p, spmv_symmetric_multi_info *info)
+{
+    if (!p || !info)
+        return fail_msg(SPMV_OTHER_ERROR, "spmv_plan_get_symmetric_multi_info: NULL argument");
+    memset(info, 0, sizeof *info);
+    const SymState &s = p->sym;
+    info->mode = s.mode;
+    if (s.mode == SPMV_S_FUSED) {
+        for (int w = 0; w < 4; ++w) {
+            info->cap_cols[w] = kSMultiCap / kTWidths[w];
+            info->window_blocks[w] = s.mwin[w];
+            info->flush_entries[w] = s.mflush[w];
+        }
+        snprintf(info->kernel, sizeof info->kernel, "csr_sym_multi_kernel");
+    } else if (s.inner) {
+        const MultiBalance &bal = s.inner->m.bal;
+        info->long_rows = bal.n_long;
+        info->segments = bal.n_seg;
+        info->multi_owned_bytes = (int64_t)s.inner->m.owned;
+        snprintf(info->kernel, sizeof info->kernel, "%s", bal.n_seg > 0 ? "csr_multi_long_kernel" : "csr_multi_kernel");
+    }
+    return SPMV_SUCCESS;
+}
+
+int spmv_plan_run_sym_multi(const spmv_plan *p, int32_t k, const double *X, int64_t ldx, double *Y, int64_t ldy,
+                            void *stream)
+{
+    if (!p)
+        return fail_msg(SPMV_OTHER_ERROR, "spmv_plan_run_sym_multi: plan is NULL");
+    if (p->sym.mode == SPMV_S_NONE)
+        return fail_msg(SPMV_OTHER_ERROR,
+                        "spmv_plan_run_sym_multi: the plan was not prepared (spmv_plan_prepare_symmetric)");
+    if (k < 1)
+        return fail_msg(SPMV_OTHER_ERROR, "spmv_plan_run_sym_multi: k must be at least 1");
+    if (ldx < k || ldy < k)
+        return fail_msg(SPMV_OTHER_ERROR, "spmv_plan_run_sym_multi: ldx and ldy must be at least k");
+    if (p->d.n_rows > 0 && (!X || !Y))
+        return fail_msg(SPMV_OTHER_ERROR, "spmv_plan_run_sym_multi: X or Y is NULL");
+    if (p->sym.mode == SPMV_S_EXPAND)
+        return spmv_plan_run_multi(p->sym.inner, k, X, ldx, Y, ldy, stream);
+    SPMV_GUARD(p->d);
+    return launch_fused_multi(p, k, X, ldx, Y, ldy, (hipStream_t)stream);
 }
 
 }  // extern "C"

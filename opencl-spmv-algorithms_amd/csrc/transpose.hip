@@ -25,7 +25,8 @@
 // csr_t_multi_kernel<KV>, the window kernel's geometry with KV vectors per
 // pass and an LDS accumulator of span * KV sums (below).
 //
-// Block prologue, entry stream, row search and flush: rowblock.h.
+// Block prologue, entry stream, row search, flush and the lane geometry of the
+// multi-vector kernel (t_multi_p, group_bcast): rowblock.h.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -115,40 +116,6 @@ __global__ __launch_bounds__(kBlock) void csr_t_window_kernel(int64_t n_rows, in
 #define SPMV_T_MULTI_CAP 8192  // an A/B build may override it (profiles/transpose/README.md)
 #endif
 constexpr int32_t kTMultiCap = SPMV_T_MULTI_CAP;  // LDS accumulator doubles per workgroup (64 KiB)
-constexpr int kTWidths[4] = {1, 2, 4, 8};
-
-// lanes that share one entry: two columns per lane from KV = 4 on, as
-// csr_multi_kernel; the P lanes of an entry are neighbours inside one quad
-template <int KV>
-constexpr int t_multi_p()
-{
-    return KV >= 4 ? KV / 2 : 1;
-}
-
-// The value of lane Q of every P-lane group (P = 2 or 4, groups aligned inside
-// a quad) by a DPP quad_perm move: a VALU operand modifier, no LDS traffic.
-// Called in uniform control flow only (every lane of the wave active).
-template <int P, int Q>
-constexpr int group_bcast_ctrl()
-{
-    static_assert((P == 2 || P == 4) && Q < P, "groups inside one quad");
-    return P == 4 ? Q * 0x55 : (Q | Q << 2 | (2 + Q) << 4 | (2 + Q) << 6);
-}
-
-template <int P, int Q>
-__device__ __forceinline__ int group_bcast(int v)
-{
-    return __builtin_amdgcn_mov_dpp(v, group_bcast_ctrl<P, Q>(), 0xF, 0xF, false);
-}
-
-template <int P, int Q>
-__device__ __forceinline__ double group_bcast(double v)
-{
-    const long long b = __double_as_longlong(v);
-    const int lo = group_bcast<P, Q>((int)b);
-    const int hi = group_bcast<P, Q>((int)(b >> 32));
-    return __longlong_as_double((long long)(((unsigned long long)(unsigned)hi << 32) | (unsigned)lo));
-}
 
 // One lane's CPL columns [j0, j0 + CPL) of one entry (column c, value v, block
 // row r): v * X[r][j] added to acc[(c - lo) * KV + j] (LDS = true, bound = the
@@ -292,15 +259,6 @@ constexpr size_t t_multi_lds(int kv, int64_t span)
 
 constexpr size_t t_multi_lds_max(int kv) { return t_multi_lds(kv, kTMultiCap / kv); }
 
-template <typename F>
-void with_each_width(F &&f)
-{
-    f(std::integral_constant<int, 1>{});
-    f(std::integral_constant<int, 2>{});
-    f(std::integral_constant<int, 4>{});
-    f(std::integral_constant<int, 8>{});
-}
-
 int prepare_scatter(spmv_plan *p)
 {
     const spmv_dims &d = p->d;
@@ -391,16 +349,9 @@ int launch_scatter_multi(const spmv_plan *p, int32_t k, const double *X, int64_t
     const spmv_dims &d = p->d;
     if (k == 1 && ldx == 1 && ldy == 1)
         return launch_scatter(p, X, Y, st);
-    if (d.n_cols > 0 && ldy == k) {
-        hipError_t e = hipMemsetAsync(Y, 0, (size_t)d.n_cols * k * sizeof(double), st);
-        if (e != hipSuccess)
-            return fail(SPMV_PROGRAM_ERROR, "spmv_plan_run_t_multi: memset", e);
-    } else if (d.n_cols > 0) {
-        const int64_t want = (d.n_cols * k + kBlock - 1) / kBlock;
-        hipLaunchKernelGGL(t_zero_cols_kernel, dim3((unsigned)(want < 65536 ? want : 65536)), dim3(kBlock), 0, st,
-                           d.n_cols, k, Y, ldy);
-        SPMV_CHECK_LAUNCH("t_zero_cols_kernel");
-    }
+    const int rc = zero_cols(d.n_cols, k, Y, ldy, st, "spmv_plan_run_t_multi");
+    if (rc != SPMV_SUCCESS)
+        return rc;
     if (!p->t.win || d.n_cols == 0)
         return SPMV_SUCCESS;
     for (int32_t j0 = 0; j0 < k; j0 += 8) {
@@ -420,6 +371,23 @@ int launch_scatter_multi(const spmv_plan *p, int32_t k, const double *X, int64_t
 }  // namespace
 
 void plan_transpose_free(spmv_plan *p) { mode_state_free(&p->t); }
+
+int zero_cols(int64_t n, int32_t k, double *Y, int64_t ldy, hipStream_t st, const char *who)
+{
+    if (n <= 0)
+        return SPMV_SUCCESS;
+    if (ldy == k) {
+        const hipError_t e = hipMemsetAsync(Y, 0, (size_t)n * k * sizeof(double), st);
+        if (e != hipSuccess)
+            return fail(SPMV_PROGRAM_ERROR, who, e);
+        return SPMV_SUCCESS;
+    }
+    const int64_t want = (n * k + kBlock - 1) / kBlock;
+    hipLaunchKernelGGL(t_zero_cols_kernel, dim3((unsigned)(want < 65536 ? want : 65536)), dim3(kBlock), 0, st, n, k, Y,
+                       ldy);
+    SPMV_CHECK_LAUNCH(who);
+    return SPMV_SUCCESS;
+}
 
 }  // namespace spmv
 

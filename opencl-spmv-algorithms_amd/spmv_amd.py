@@ -133,6 +133,14 @@ class SymmetricInfo(ctypes.Structure):
 SYMMETRIC_MODES = {None: 0, "fused": 1, "expand": 2}  # enum spmv_symmetric_mode
 
 
+class SymmetricMultiInfo(ctypes.Structure):
+    """``spmv_symmetric_multi_info`` (include/spmv.h)."""
+
+    _fields_ = [("mode", _c_i32), ("reserved", _c_i32), ("cap_cols", _c_i32 * 4), ("window_blocks", _c_i64 * 4),
+                ("flush_entries", _c_i64 * 4), ("long_rows", _c_i64), ("segments", _c_i64),
+                ("multi_owned_bytes", _c_i64), ("kernel", ctypes.c_char * 64)]
+
+
 class MultiOpts(ctypes.Structure):
     """``spmv_multi_opts`` (include/spmv.h); -1 = the library's rule."""
 
@@ -178,6 +186,8 @@ HIP_SYMBOLS = {
     "spmv_plan_get_symmetric_info": (ctypes.c_int, [_vp, ctypes.POINTER(SymmetricInfo)]),
     "spmv_plan_run_sym": (ctypes.c_int, [_vp, _vp, _vp, _vp]),
     "spmv_plan_get_symmetric_arrays": (ctypes.c_int, [_vp, _PP, _PP, _PP, ctypes.POINTER(_c_i64)]),
+    "spmv_plan_run_sym_multi": (ctypes.c_int, [_vp, _c_i32, _vp, _c_i64, _vp, _c_i64, _vp]),
+    "spmv_plan_get_symmetric_multi_info": (ctypes.c_int, [_vp, ctypes.POINTER(SymmetricMultiInfo)]),
     "spmv_plan_get_info": (ctypes.c_int, [_vp, ctypes.POINTER(PlanInfo)]),
     "spmv_plan_destroy": (ctypes.c_int, [_vp]),
     "spmv_set_option": (ctypes.c_int, [ctypes.c_int, ctypes.c_int]),
@@ -327,6 +337,7 @@ HOST_SYMBOLS = {
     "spmv_csr_transpose": (ctypes.c_int, [_c_i64, _c_i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "spmv_coo_symmetrize": (ctypes.c_int, [_c_i64, _c_i64, _vp, _vp, _vp, ctypes.POINTER(_c_i64), _vp, _vp, _vp]),
     "spmv_cpu_csr_sym": (ctypes.c_int, [_c_i64, _vp, _vp, _vp, _vp, _vp]),
+    "spmv_cpu_csr_sym_multi": (ctypes.c_int, [_c_i64, _vp, _vp, _vp, _c_i32, _vp, _c_i64, _vp, _c_i64]),
     "spmv_csr_sort_rows": (ctypes.c_int, [_c_i64, _vp, _vp, _vp]),
     "spmv_csr_row_stats": (ctypes.c_int, [_c_i64, _vp, ctypes.POINTER(_c_i64), ctypes.POINTER(_c_i64), ctypes.POINTER(ctypes.c_double)]),
     "spmv_csr_pick_variant": (ctypes.c_int, [_c_i64, _vp]),
@@ -587,6 +598,26 @@ def cpu_csr_sym(n: int, ptr, col, val, x: np.ndarray, y: np.ndarray) -> None:
         if a.size < n:
             raise SpmvError(OTHER_ERROR, "cpu_csr_sym", "x or y too short")
     _check_host(host_lib().spmv_cpu_csr_sym(n, _ptr(ptr), _ptr(col), _ptr(val), _ptr(x), _ptr(y)), "spmv_cpu_csr_sym")
+
+
+def cpu_csr_sym_multi(n: int, ptr, col, val, X: np.ndarray, Y: np.ndarray, k: int | None = None) -> None:
+    """Host Y = (S + S^T - diag S) X on the half storage
+    (spmv_cpu_csr_sym_multi): X and Y (>= n rows) are 2-D float64 arrays with
+    unit inner stride whose row strides are ldx and ldy; k defaults to X's
+    width.  Only Y[:n, :k] is written."""
+    for a in (X, Y):
+        if not isinstance(a, np.ndarray) or a.dtype != np.float64 or a.ndim != 2:
+            raise SpmvError(OTHER_ERROR, "cpu_csr_sym_multi", "X and Y must be 2-D float64 arrays")
+        if a.shape[1] > 1 and a.strides[1] != 8 or a.strides[0] % 8:
+            raise SpmvError(OTHER_ERROR, "cpu_csr_sym_multi", "X and Y need unit inner stride")
+        if a.shape[0] < n:
+            raise SpmvError(OTHER_ERROR, "cpu_csr_sym_multi", "X or Y has too few rows")
+    k = X.shape[1] if k is None else int(k)
+    if k > X.shape[1] or k > Y.shape[1]:
+        raise SpmvError(OTHER_ERROR, "cpu_csr_sym_multi", "X or Y has fewer than k columns")
+    ldx, ldy = (a.strides[0] // 8 if a.shape[0] > 1 else k for a in (X, Y))  # one row: its stride is never used
+    rc = host_lib().spmv_cpu_csr_sym_multi(n, _ptr(ptr), _ptr(col), _ptr(val), k, _ptr(X), ldx, _ptr(Y), ldy)
+    _check_host(rc, "spmv_cpu_csr_sym_multi")
 
 
 def csr_sort_rows(n_rows: int, ptr, col, val) -> None:
@@ -1224,6 +1255,57 @@ class DeviceMatrix:
         st = stream if stream is not None else torch.cuda.current_stream(here)
         _check(hip_lib().spmv_plan_run_sym(self.plan, _ptr(x), _ptr(y), st.cuda_stream),
                f"spmv_plan_run_sym ({self.fmt})")
+
+    @property
+    def symmetric_multi_info(self) -> dict:
+        """spmv_symmetric_multi_info as a dict (cap_cols, window_blocks and
+        flush_entries are lists over the kernel widths 1, 2, 4, 8); mode as in
+        symmetric_info."""
+        if self.plan is None:
+            raise SpmvError(OTHER_ERROR, "symmetric_multi_info", f"format {self.fmt} has no plan")
+        info = SymmetricMultiInfo()
+        _check(hip_lib().spmv_plan_get_symmetric_multi_info(self.plan, ctypes.byref(info)),
+               "spmv_plan_get_symmetric_multi_info")
+        out = {k: [int(v) for v in getattr(info, k)] for k in ("cap_cols", "window_blocks", "flush_entries")}
+        out.update({k: int(getattr(info, k)) for k in ("long_rows", "segments", "multi_owned_bytes")})
+        out["mode"] = {v: k for k, v in SYMMETRIC_MODES.items()}[info.mode]
+        out["kernel"] = info.kernel.decode()
+        return out
+
+    def run_sym_multi(self, X, Y, stream=None) -> None:
+        """Y = (S + S^T - diag S) X on `stream` for k vectors stored row-major
+        (spmv_plan_run_sym_multi), S the stored half this matrix holds: X and
+        Y are (>= n, k), float64 on the matrix's device with inner stride 1;
+        their row strides (>= k) are ldx and ldy.  Only Y[:n, :k] is written.
+        Needs prepare_symmetric first."""
+        torch = _torch()
+        for t in (X, Y):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float64:
+                raise SpmvError(OTHER_ERROR, "run_sym_multi", "X and Y must be float64 tensors")
+            if t.dim() != 2:
+                raise SpmvError(OTHER_ERROR, "run_sym_multi", "X and Y must be 2-D (rows, k)")
+        if self.n_rows != self.n_cols:
+            raise SpmvError(OTHER_ERROR, "run_sym_multi", "the matrix is not square")
+        k = X.shape[1]
+        if k < 1 or Y.shape[1] != k:
+            raise SpmvError(OTHER_ERROR, "run_sym_multi", "X and Y must have the same number k >= 1 of columns")
+        if X.shape[0] < self.n_cols or Y.shape[0] < self.n_rows:
+            raise SpmvError(OTHER_ERROR, "run_sym_multi", "X or Y has too few rows")
+        for t in (X, Y):  # as run_multi: raw data_ptr()s and strides go to the C-ABI
+            if (k > 1 and t.stride(1) != 1) or (t.shape[0] > 1 and t.stride(0) < k):
+                raise SpmvError(OTHER_ERROR, "run_sym_multi", "X and Y need inner stride 1 and a row stride >= k")
+        here = torch.device(self.device)
+        idx = here.index or 0
+        for t in (X, Y):
+            if t.device.type != here.type or (t.device.index or 0) != idx:
+                raise SpmvError(OTHER_ERROR, "run_sym_multi", f"X and Y must be on {here.type}:{idx}")
+        if self.plan is None:
+            raise SpmvError(OTHER_ERROR, "run_sym_multi", f"format {self.fmt} has no plan: no symmetric run")
+        ldx = X.stride(0) if X.shape[0] > 1 else k
+        ldy = Y.stride(0) if Y.shape[0] > 1 else k
+        st = stream if stream is not None else torch.cuda.current_stream(here)
+        _check(hip_lib().spmv_plan_run_sym_multi(self.plan, k, _ptr(X), ldx, _ptr(Y), ldy, st.cuda_stream),
+               f"spmv_plan_run_sym_multi ({self.fmt})")
 
     @property
     def transpose_multi_info(self) -> dict:
