@@ -402,6 +402,34 @@ int spmv_xpay_ratio(int64_t n, const double *num, const double *den, const doubl
 /* y = x / sqrt(*s)                (power iteration: normalise)          */
 int spmv_scale_rsqrt(int64_t n, const double *s, const double *x, double *y, int device,
                      void *stream);
+/* The same three on BLOCKS of k >= 1 vectors (multi-right-hand-side CG,
+ * iterate.cg_multi), laid out as spmv_plan_run_multi lays them out:
+ * row-major, V[i*ld + j], j < k <= ld, 8-byte alignment only.  Nothing
+ * outside V[i*ld .. i*ld + k), i < n, is read or written.  Asynchronous on
+ * `stream`, no allocation, no synchronisation (capturable).  k < 1, an
+ * ld < k and a workspace that is too small return SPMV_OTHER_ERROR.
+ *
+ * out[j] = sum_i A[i*lda + j] * B[i*ldb + j], j < k; n == 0 writes k zeros.
+ * ws holds spmv_dot_multi_ws_bytes(n, k) bytes.  No atomics: a fixed
+ * two-stage tree per column.  out[j]'s bits depend only on n and on the
+ * values of column j of A and B: not on k, on j, on lda / ldb, on the base
+ * alignment or on the load width the call chose (they need not equal
+ * spmv_dot's).  At most two stage-1 launches and one final launch.        */
+size_t spmv_dot_multi_ws_bytes(int64_t n, int32_t k);
+int spmv_dot_multi(int64_t n, int32_t k, const double *A, int64_t lda, const double *B, int64_t ldb,
+                   double *out, void *ws, size_t ws_bytes, int device, void *stream);
+/* Y[i,j] = fma(c_j, X[i,j], Y[i,j]),  c_j = sign * (num[j] / den[j])
+ * Y[i,j] = fma(c_j, Y[i,j], X[i,j]),  c_j = num[j] / den[j]
+ * num and den are device arrays of k doubles; X and Y must not overlap.
+ * den[j] == 0.0 GIVES c_j = 0.0 (not Inf or NaN): in CG a column whose
+ * residual has reached exactly zero (a zero right-hand side at once, any
+ * column once its residual underflows) has rr = pAp = 0, and 0/0 would turn
+ * the column into NaN; with c_j = 0 it stays where it is.  An element's
+ * result depends only on its own inputs and c_j, not on k or the ld path. */
+int spmv_axpy_ratio_multi(int64_t n, int32_t k, const double *num, const double *den, double sign,
+                          const double *X, int64_t ldx, double *Y, int64_t ldy, int device, void *stream);
+int spmv_xpay_ratio_multi(int64_t n, int32_t k, const double *num, const double *den, const double *X,
+                          int64_t ldx, double *Y, int64_t ldy, int device, void *stream);
 /* out[k] = x[order[k]]: x in the layout of a matrix whose columns were
  * relabelled by spmv_column_relabel (spmv_host.h), the input its SpMV
  * takes.  out must not alias x.                                          */

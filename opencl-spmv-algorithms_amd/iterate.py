@@ -1,4 +1,5 @@
-"""iterate.py — iterated SpMV over row shards: power iteration and CG.
+"""iterate.py — iterated SpMV over row shards: power iteration, CG and
+multi-right-hand-side CG.
 
 SURVEY.md §8f row 3: "Iterated SpMV (power iteration / CG) reusing the y
 all-gather as the next x".  The reference stops after one SpMV (reference
@@ -31,6 +32,14 @@ scalars are all-reduced in place over RCCL (`torch.distributed`, backend
 nccl) and never visit the host except for CG's convergence test every
 `check_every` iterations.  With one rank the loop can be captured into a
 HIP graph (`graph=True`).
+
+Several right-hand sides (cg_multi): k independent CG recurrences, one per
+column of a row-major (rows, k) block, share ONE multi-vector product
+(DeviceMatrix.run_multi / run_sym_multi) per iteration and the block vector
+kernels of csrc/vec_multi.hip; the k alphas and betas are k-vectors in device
+memory.  build_operator(symmetric="fused" | "expand") builds the operator on
+the stored half of a symmetric matrix (prepare_symmetric), for cg, cg_multi
+and power_iteration alike.
 
 The device work goes through a `kernels` object (HipKernels by default).
 Tests substitute a numpy double to exercise the multi-rank orchestration on
@@ -184,9 +193,12 @@ class Comm:
 class HipKernels:
     """The device kernels of one iteration, all on one stream."""
 
-    def __init__(self, dm: sa.DeviceMatrix, stream=None):
+    def __init__(self, dm: sa.DeviceMatrix, stream=None, symmetric: bool = False):
+        """symmetric: dm holds the stored half of a symmetric matrix and was
+        prepared (prepare_symmetric): spmv is run_sym, spmm run_sym_multi."""
         torch = sa._torch()
         self.dm = dm
+        self.symmetric = symmetric
         self.dev = torch.device(dm.device)
         self.lib = sa.hip_lib()
         self.stream = stream
@@ -197,7 +209,22 @@ class HipKernels:
         return st.cuda_stream
 
     def spmv(self, x_full, y) -> None:
-        self.dm.run(x_full, y, self.stream)
+        if self.symmetric:
+            self.dm.run_sym(x_full, y, self.stream)
+        else:
+            self.dm.run(x_full, y, self.stream)
+
+    @property
+    def multi_supported(self) -> bool:
+        """spmm can run this matrix (a CSR, ELL or SELL plan)."""
+        return self.dm.multi_supported
+
+    def spmm(self, X_full, Y) -> None:
+        """Y = A X_full for row-major (rows, k) blocks."""
+        if self.symmetric:
+            self.dm.run_sym_multi(X_full, Y, self.stream)
+        else:
+            self.dm.run_multi(X_full, Y, self.stream)
 
     def dot(self, n, a, b, out, ws) -> None:
         sa._check(self.lib.spmv_dot(n, sa._ptr(a), sa._ptr(b), sa._ptr(out), sa._ptr(ws), ws.numel(),
@@ -218,6 +245,32 @@ class HipKernels:
     def dot_ws(self, n):
         torch = sa._torch()
         nbytes = self.lib.spmv_dot_ws_bytes(n)
+        return torch.empty(nbytes, dtype=torch.uint8, device=self.dev)
+
+    # the block kernels (csrc/vec_multi.hip): A, B, X, Y are row-major
+    # (>= n, k) blocks with inner stride 1, out / num / den hold k scalars
+    @staticmethod
+    def _ld(t) -> int:
+        return t.stride(0) if t.shape[0] > 1 else t.shape[1]
+
+    def dot_multi(self, n, A, B, out, ws) -> None:
+        sa._check(self.lib.spmv_dot_multi(n, A.shape[1], sa._ptr(A), self._ld(A), sa._ptr(B), self._ld(B),
+                                          sa._ptr(out), sa._ptr(ws), ws.numel(), self.dev.index or 0, self._s()),
+                  "spmv_dot_multi")
+
+    def axpy_ratio_multi(self, n, num, den, sign, X, Y) -> None:
+        sa._check(self.lib.spmv_axpy_ratio_multi(n, X.shape[1], sa._ptr(num), sa._ptr(den), float(sign), sa._ptr(X),
+                                                 self._ld(X), sa._ptr(Y), self._ld(Y), self.dev.index or 0,
+                                                 self._s()), "spmv_axpy_ratio_multi")
+
+    def xpay_ratio_multi(self, n, num, den, X, Y) -> None:
+        sa._check(self.lib.spmv_xpay_ratio_multi(n, X.shape[1], sa._ptr(num), sa._ptr(den), sa._ptr(X), self._ld(X),
+                                                 sa._ptr(Y), self._ld(Y), self.dev.index or 0, self._s()),
+                  "spmv_xpay_ratio_multi")
+
+    def dot_multi_ws(self, n, k):
+        torch = sa._torch()
+        nbytes = self.lib.spmv_dot_multi_ws_bytes(n, k)
         return torch.empty(nbytes, dtype=torch.uint8, device=self.dev)
 
 
@@ -253,14 +306,41 @@ class DistOperator:
 
 def build_operator(m: sa.Coo, rank: int = 0, world: int = 1, fmt: str = "csr", device="cuda:0", align: int = 1024,
                    split: bool = False, overlap: bool = False, expand_symmetric: bool = False,
-                   **fmt_kw) -> DistOperator:
+                   symmetric: str | None = None, **fmt_kw) -> DistOperator:
     """Partition, renumber and upload this rank's shard (HIP kernels).
     split (implied by overlap): local / remote column parts
     (split_local_remote), each its own device matrix.
     expand_symmetric: m holds one half of a symmetric matrix (a Matrix Market
     `symmetric` file); sa.expand_symmetric turns it into the matrix it
     describes before sharding, which is what CG needs.  Default: the entries
-    as listed."""
+    as listed.
+    symmetric ("fused" or "expand"): m holds one half of a symmetric matrix
+    and STAYS that half: the CSR device matrix is built over it and prepared
+    with prepare_symmetric(symmetric), so the operator's products are
+    run_sym / run_sym_multi ("expand" is bitwise reproducible, "fused" is
+    not).  One rank, CSR, unsplit only; anything else is refused before
+    anything is uploaded."""
+    if symmetric is not None:
+        def refuse(why):
+            return sa.SpmvError(sa.OTHER_ERROR, "build_operator", f"symmetric={symmetric!r}: {why}")
+
+        if symmetric not in ("fused", "expand"):
+            raise refuse('must be None, "fused" or "expand"')
+        if world != 1:
+            raise refuse("one rank only (the stored half is not row-sharded)")
+        if fmt != "csr":
+            raise refuse(f'format "csr" only, not {fmt!r}')
+        if split or overlap:
+            raise refuse("no split / overlap operators")
+        if expand_symmetric:
+            raise refuse("expand_symmetric=True expands on the host: choose one of the two")
+        if m.n_rows != m.n_cols:
+            raise refuse("the matrix is not square")
+        counts = np.bincount(m.row, minlength=m.n_rows).astype(np.int64)
+        layout = layout_for(m.n_rows, counts, 1, align)  # one block: positions are the identity
+        dm = sa.to_device(m, "csr", device, **fmt_kw)  # the half itself, n x n
+        dm.prepare_symmetric(symmetric)
+        return DistOperator(layout, rank, m.n_rows, HipKernels(dm, symmetric=True), device)
     if expand_symmetric:
         m = sa.expand_symmetric(m)
     counts = np.bincount(m.row, minlength=m.n_rows).astype(np.int64)
@@ -285,8 +365,10 @@ class _Apply:
     wait: overlap), wait, remote SpMV on `full` into a scratch vector, exact
     add."""
 
-    def __init__(self, op, comm, full, send):
-        self.op, self.comm, self.full, self.send = op, comm, full, send
+    def __init__(self, op, comm, full, send, multi=False):
+        """multi: full and send are (.., k) blocks and the product is spmm
+        (unsplit operators only)."""
+        self.op, self.comm, self.full, self.send, self.multi = op, comm, full, send, multi
         if op.remote is not None:
             self.y2 = _zeros(op, max(op.rows, 1))
             self.one = _zeros(op, 1) + 1.0
@@ -302,7 +384,7 @@ class _Apply:
         if op.remote is None:
             comm.allgather(self.full, self.send)
             _order(cur, st)
-            op.kernels.spmv(self.full, y)
+            (op.kernels.spmm if self.multi else op.kernels.spmv)(self.full, y)
             return
         work = comm.allgather_start(self.full, self.send)
         if work is None:
@@ -449,3 +531,114 @@ def _cg(op: DistOperator, b_loc, comm: Comm | None = None, tol: float = 1e-10, m
             if float(rr.item()) <= tol * tol * bb:
                 break
     return x, it, float(np.sqrt(max(float(rr.item()), 0.0) / bb))
+
+
+# ------------------------------------------------ CG, several right-hand sides
+def cg_multi(op: DistOperator, B_loc, comm: Comm | None = None, tol: float = 1e-10, maxit: int = 1000,
+             check_every: int = 10):
+    """Conjugate gradients for k right-hand sides at once, on the operator's
+    kernel stream (_cg_multi)."""
+    with _kernel_stream(op):
+        return _cg_multi(op, B_loc, comm, tol, maxit, check_every)
+
+
+def _check_block(op, B_loc) -> int:
+    """B_loc must be a contiguous float64 (rows, k >= 1) tensor on the
+    operator's device; returns k."""
+    torch = sa._torch()
+
+    def refuse(why):
+        return sa.SpmvError(sa.OTHER_ERROR, "cg_multi", why)
+
+    if not isinstance(B_loc, torch.Tensor) or B_loc.dtype != torch.float64:
+        raise refuse("B_loc must be a float64 tensor")
+    if B_loc.dim() != 2:
+        raise refuse("B_loc must be 2-D (rows, k): one column per right-hand side")
+    if B_loc.shape[0] != op.rows or B_loc.shape[1] < 1:
+        raise refuse(f"B_loc must be ({op.rows}, k >= 1), not {tuple(B_loc.shape)}")
+    if not B_loc.is_contiguous():
+        raise refuse("B_loc must be contiguous (row-major, ld = k)")
+    here = torch.device(op.device if op.device is not None else "cpu")
+    if B_loc.device.type != here.type or (B_loc.device.index or 0) != (here.index or 0):
+        raise refuse(f"B_loc must be on {here}")
+    return int(B_loc.shape[1])
+
+
+def _cg_multi(op: DistOperator, B_loc, comm: Comm | None = None, tol: float = 1e-10, maxit: int = 1000,
+              check_every: int = 10):
+    """k independent CG recurrences (x0 = 0, A symmetric positive definite),
+    one per column of B_loc (rows, k), sharing one multi-vector product per
+    iteration; NOT block CG (no k x k Gram systems).  Returns (X_local
+    (rows, k), iterations, rel: numpy (k,) of ||r_j|| / ||b_j||).
+
+    Per iteration: one spmm, dot_multi(P, AP), two axpy_ratio_multi,
+    dot_multi(R, R), one xpay_ratio_multi.  The k alphas and betas stay in
+    device memory; the host reads rr every `check_every` iterations and
+    stops when EVERY column has rr_j <= tol^2 bb_j, or at maxit.
+
+    No freeze mask: a column that has converged keeps iterating with the
+    others (its updates shrink with its residual).  What keeps such a column
+    finite is the block kernels' rule that a zero denominator gives the
+    ratio 0: once rr_j (or p_j·Ap_j) is exactly 0, alpha_j and beta_j are 0
+    and the column stands still instead of turning into 0/0.  A column with
+    b_j = 0 hits the rule at once: x_j = 0 exactly, rel_j = 0.0.
+
+    Column j's bits do not depend on k or on the other columns when the
+    operator's spmm is reproducible (forward plans, symmetric="expand").
+
+    With more than one rank the gathered layout carries over: `full` is
+    (world * pad, k), `send` (pad, k), one all_gather_into_tensor per
+    iteration and one all-reduce per k-vector of scalars.  Unsplit operators
+    only."""
+    comm = comm or Comm()
+    k = op.kernels
+    if op.remote is not None:
+        raise sa.SpmvError(sa.OTHER_ERROR, "cg_multi", "split / overlap operators are not supported")
+    if not getattr(k, "multi_supported", False):
+        raise sa.SpmvError(sa.OTHER_ERROR, "cg_multi",
+                           "the operator's matrix has no multi-vector run (CSR, ELL and SELL plans have one)")
+    nv = _check_block(op, B_loc)
+    torch = sa._torch()
+    rows = op.rows
+
+    def zeros(*shape):
+        return torch.zeros(shape, dtype=torch.float64, device=op.device)
+
+    send = zeros(op.pad, nv)
+    full = zeros(op.world * op.pad, nv) if comm.world > 1 else send
+    P = send[:rows]
+    X = zeros(rows, nv)
+    R = B_loc.clone()
+    P.copy_(B_loc)
+    apply = _Apply(op, comm, full, send, multi=True)
+    AP = zeros(max(rows, 1), nv)
+    ws = k.dot_multi_ws(rows, nv)
+    rr, rr_new, pAp = zeros(nv), zeros(nv), zeros(nv)
+    k.dot_multi(rows, R, R, rr, ws)
+    comm.allreduce(rr)
+    bb = rr.cpu().numpy().copy()
+
+    def rel(rr_host):
+        out = np.zeros(nv)
+        live = bb > 0.0
+        out[live] = np.sqrt(np.maximum(rr_host[live], 0.0) / bb[live])
+        return out
+
+    if not (bb > 0.0).any():
+        return X, 0, np.zeros(nv)
+    it = 0
+    while it < maxit:
+        apply(AP)  # gathers P
+        k.dot_multi(rows, P, AP, pAp, ws)
+        comm.allreduce(pAp)
+        k.axpy_ratio_multi(rows, rr, pAp, 1.0, P, X)  # x_j += alpha_j p_j
+        k.axpy_ratio_multi(rows, rr, pAp, -1.0, AP, R)  # r_j -= alpha_j Ap_j
+        k.dot_multi(rows, R, R, rr_new, ws)
+        comm.allreduce(rr_new)
+        k.xpay_ratio_multi(rows, rr_new, rr, R, P)  # p_j = r_j + beta_j p_j
+        rr, rr_new = rr_new, rr
+        it += 1
+        if it % check_every == 0 or it == maxit:
+            if (rr.cpu().numpy() <= tol * tol * bb).all():
+                break
+    return X, it, rel(rr.cpu().numpy())

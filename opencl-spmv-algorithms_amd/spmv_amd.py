@@ -292,6 +292,13 @@ HIP_SYMBOLS = {
     "spmv_axpy_ratio": (ctypes.c_int, [_c_i64, _vp, _vp, ctypes.c_double, _vp, _vp, ctypes.c_int, _vp]),
     "spmv_xpay_ratio": (ctypes.c_int, [_c_i64, _vp, _vp, _vp, _vp, ctypes.c_int, _vp]),
     "spmv_scale_rsqrt": (ctypes.c_int, [_c_i64, _vp, _vp, _vp, ctypes.c_int, _vp]),
+    "spmv_dot_multi_ws_bytes": (ctypes.c_size_t, [_c_i64, ctypes.c_int32]),
+    "spmv_dot_multi": (ctypes.c_int, [_c_i64, ctypes.c_int32, _vp, _c_i64, _vp, _c_i64, _vp, _vp, ctypes.c_size_t,
+                                      ctypes.c_int, _vp]),
+    "spmv_axpy_ratio_multi": (ctypes.c_int, [_c_i64, ctypes.c_int32, _vp, _vp, ctypes.c_double, _vp, _c_i64, _vp,
+                                             _c_i64, ctypes.c_int, _vp]),
+    "spmv_xpay_ratio_multi": (ctypes.c_int, [_c_i64, ctypes.c_int32, _vp, _vp, _vp, _c_i64, _vp, _c_i64,
+                                             ctypes.c_int, _vp]),
     "spmv_gather": (ctypes.c_int, [_c_i64, _vp, _vp, _vp, ctypes.c_int, _vp]),
     "spmv_device_count": (ctypes.c_int, [ctypes.POINTER(ctypes.c_int)]),
     "spmv_set_device": (ctypes.c_int, [ctypes.c_int]),
