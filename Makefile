@@ -35,7 +35,7 @@ LIB_HIP  := $(LIBDIR)/libspmv_hip.so
 LIB_HOST := $(LIBDIR)/libspmv_host.so
 ORACLE   := oracle/liboracle.so
 
-.PHONY: all default lib oracle probes lab test-san test-san-transpose test-san-transpose-multi test-san-multi-plan test-san-symmetric test-san-symmetric-multi test-cpu test-gpu clean $(TARGETS)
+.PHONY: all default lib oracle probes lab test-san test-san-transpose test-san-transpose-multi test-san-multi-plan test-san-symmetric test-san-symmetric-multi test-san-precond test-cpu test-gpu clean $(TARGETS)
 
 default: all
 all: lib $(TARGETS) probes
@@ -183,6 +183,17 @@ build/san/symmetric_multi_harness: tests/san/symmetric_multi_harness.c $(HOST_SR
 
 test-san-symmetric-multi: build/san/symmetric_multi_harness
 	$(SANENV) ASAN_OPTIONS=detect_leaks=1:exitcode=99 build/san/symmetric_multi_harness tests/golden/*.mtx
+
+# the host statement of the block-Jacobi preconditioner (spmv_bjacobi_build,
+# spmv_cpu_bjacobi_apply_multi) under ASan + UBSan: a stand-alone program over
+# the square fixtures, every block size, exactly-sized buffers and the refused
+# inputs (tests/san/precond_harness.c)
+build/san/precond_harness: tests/san/precond_harness.c $(HOST_SRC) include/spmv_host.h include/spmv_rc.h
+	@mkdir -p build/san
+	$(CC) -std=c11 -Wall -Wextra -Werror -fopenmp -Iinclude $(SANFLAGS) $< $(HOST_SRC) -o $@ -lm
+
+test-san-precond: build/san/precond_harness
+	$(SANENV) ASAN_OPTIONS=detect_leaks=1:exitcode=99 build/san/precond_harness tests/golden/*.mtx
 
 test-gpu: all oracle
 	python -m pytest tests/ -x -q -m gpu

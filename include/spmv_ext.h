@@ -430,6 +430,53 @@ int spmv_axpy_ratio_multi(int64_t n, int32_t k, const double *num, const double 
                           const double *X, int64_t ldx, double *Y, int64_t ldy, int device, void *stream);
 int spmv_xpay_ratio_multi(int64_t n, int32_t k, const double *num, const double *den, const double *X,
                           int64_t ldx, double *Y, int64_t ldy, int device, void *stream);
+/* Block-Jacobi preconditioner M = blockdiag(D_0, D_1, ...), bs x bs blocks of
+ * the diagonal, 1 <= bs <= 16, for the CG solvers of iterate.py (cg, cg_multi).
+ * spmv_bjacobi_build (spmv_host.h) defines the blocks (col_base,
+ * symmetric_half, the short last block) and the inversion; this is its device
+ * form.
+ * spmv_bjacobi_create is a build-time call: it reads the caller's CSR device
+ * arrays (d.n_rows rows, d.nnz entries) on d.stream, extracts and inverts
+ * every block on the device and synchronises.  The object owns only the
+ * inverse (n_blocks*bs*bs doubles, the layout of spmv_bjacobi_build's inv;
+ * spmv_bjacobi_inverse returns the device pointer), so the arrays may be
+ * freed afterwards.  No atomics: two builds of the same input give the same
+ * bits.  info.singular_blocks counts the blocks replaced by the identity.
+ *
+ * The two apply calls follow the conventions of the block vector kernels
+ * above: row-major blocks R[i*ldr + j], Z[i*ldz + j], j < k <= ld, 8-byte
+ * alignment only; asynchronous on `stream`, no allocation, no synchronisation
+ * (capturable).  Nothing outside Z[i*ldz + j], i < n, j < k is written and
+ * nothing outside R[i*ldr .. i*ldr + k) is read; R, Z, out and ws must not
+ * overlap.  Every element of Z has exactly the bits of
+ * spmv_cpu_bjacobi_apply_multi's fma chain on the same inv, whatever k, ld,
+ * the alignment or the load width the call chose.
+ * spmv_bjacobi_apply_dot_multi also returns out[j] = sum_i R[i][j] Z[i][j]
+ * and out[k + j] = sum_i R[i][j]^2 (what a preconditioned CG iteration needs)
+ * through spmv_dot_multi's fixed tree: the 2k results are bit for bit what
+ * spmv_dot_multi(R, Z) and spmv_dot_multi(R, R) give afterwards.  ws holds
+ * spmv_bjacobi_ws_bytes(n, k) bytes; n == 0 writes 2k zeros.  At most two
+ * stage-1 launches and one final launch.
+ * SPMV_OTHER_ERROR, before anything is written, for negative sizes, bs outside
+ * 1..16, k < 1, a leading dimension below k, a NULL argument that would be
+ * read or written or a workspace that is too small.                       */
+typedef struct spmv_bjacobi spmv_bjacobi;
+typedef struct spmv_bjacobi_info {
+    int32_t bs, symmetric_half;
+    int64_t n, n_blocks, singular_blocks, col_base, owned_bytes;
+    char kernel[64];
+} spmv_bjacobi_info;
+int spmv_bjacobi_create(spmv_dims d, const int64_t *row_ptr, const int32_t *col, const double *val,
+                        int32_t bs, int64_t col_base, int32_t symmetric_half, spmv_bjacobi **out);
+int spmv_bjacobi_get_info(const spmv_bjacobi *m, spmv_bjacobi_info *info);
+int spmv_bjacobi_inverse(const spmv_bjacobi *m, const double **inv);
+int spmv_bjacobi_apply_multi(const spmv_bjacobi *m, int32_t k, const double *R, int64_t ldr,
+                             double *Z, int64_t ldz, void *stream);
+size_t spmv_bjacobi_ws_bytes(int64_t n, int32_t k);
+int spmv_bjacobi_apply_dot_multi(const spmv_bjacobi *m, int32_t k, const double *R, int64_t ldr,
+                                 double *Z, int64_t ldz, double *out, void *ws, size_t ws_bytes,
+                                 void *stream);
+int spmv_bjacobi_destroy(spmv_bjacobi *m);
 /* out[k] = x[order[k]]: x in the layout of a matrix whose columns were
  * relabelled by spmv_column_relabel (spmv_host.h), the input its SpMV
  * takes.  out must not alias x.                                          */

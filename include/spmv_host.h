@@ -353,6 +353,39 @@ int spmv_cpu_csr_sym(int64_t n, const int64_t *row_ptr, const int32_t *col, cons
  * read or written.                                                          */
 int spmv_cpu_csr_sym_multi(int64_t n, const int64_t *row_ptr, const int32_t *col, const double *val,
                            int32_t k, const double *X, int64_t ldx, double *Y, int64_t ldy);
+/* Block-Jacobi preconditioner M = blockdiag(D_0, D_1, ...) of a square CSR
+ * matrix (rows 0 .. n-1; the host statement of spmv_bjacobi_create,
+ * spmv_ext.h).  1 <= bs <= 16, n_blocks = ceil(n / bs), block q covers rows
+ * [q*bs, min(n, (q+1)*bs)).  D_q[r][c] is the sum, in storage order, of the
+ * entries of row q*bs + r whose column equals col_base + q*bs + c (duplicates
+ * add); col_base is where the rows' own columns start (a row shard in the
+ * gathered layout of iterate.py: rank * pad; otherwise 0).  symmetric_half
+ * != 0: the arrays hold the stored half S of a symmetric matrix and every
+ * off-diagonal entry inside a block also counts at its mirrored place,
+ * diagonal entries once (spmv_coo_symmetrize's meaning).  Entries outside a
+ * row's own block are ignored, out-of-range columns included; a short last
+ * block is completed with the identity.
+ * inv[(q*bs + r)*bs + c] = D_q^-1 by Gauss-Jordan elimination with partial
+ * pivoting (the first largest entry of the column), multiply-adds as fma().  A
+ * block that meets a zero or non-finite pivot, or whose inverse has a
+ * non-finite element, becomes the identity and is counted in
+ * *singular_blocks (the identity keeps M positive definite).
+ * SPMV_OTHER_ERROR, before anything is written, for a negative n or col_base,
+ * bs outside 1..16 or a NULL array that would be read or written.          */
+int spmv_bjacobi_build(int64_t n, const int64_t *row_ptr, const int32_t *col, const double *val,
+                       int32_t bs, int64_t col_base, int32_t symmetric_half, double *inv,
+                       int64_t *singular_blocks);
+/* Z = M^-1 R for k >= 1 vectors stored row-major (R[i*ldr + j], Z[i*ldz + j],
+ * i < n, j < k; ldr, ldz >= k) with inv from spmv_bjacobi_build: for row i of
+ * block q, s = inv[i*bs] * R[(q*bs)*ldr + j], then for c = 1 .. bs-1 in order
+ * s = fma(inv[i*bs + c], R[(q*bs + c)*ldr + j], s); in a short last block only
+ * the columns that exist are read.  This fixes the bits of every element: the
+ * CPU statement of spmv_bjacobi_apply_multi (spmv_ext.h).  R and Z must not
+ * overlap.  SPMV_OTHER_ERROR, before Z is touched, for a negative n, bs outside
+ * 1..16, k < 1, a leading dimension below k or a NULL array that would be read
+ * or written.                                                                */
+int spmv_cpu_bjacobi_apply_multi(int64_t n, int32_t bs, const double *inv, int32_t k,
+                                 const double *R, int64_t ldr, double *Z, int64_t ldz);
 /* Y = A^T X for k >= 1 vectors stored row-major, the layout of
  * spmv_plan_run_t_multi (spmv.h): X[r*ldx + j], r < n_rows; Y[c*ldy + j],
  * c < n_cols; j < k; ldx >= k, ldy >= k.  Serial: zeroes Y[c*ldy + j], j < k,

@@ -17,44 +17,9 @@
 // depends on n and on column j of A and B, not on k, ld, alignment or VEC.
 // The updates are one fma per element with c_j computed the same way by
 // every thread.
-#include "common.h"
+#include "vec_multi.h"
 
 namespace spmv {
-
-constexpr int kVecW = 8;               // columns per thread and pass
-constexpr int kDotMultiBlocks = 1024;  // stage-1 partials per column (fixed by n -> deterministic)
-
-// W adjacent doubles of one row; VEC: p is 16-byte aligned and W is even
-template <int W, bool VEC>
-__device__ __forceinline__ void load_cols(const double *__restrict__ p, double (&v)[W])
-{
-    if constexpr (VEC) {
-#pragma unroll
-        for (int c = 0; c < W / 2; ++c) {
-            const double2 t = reinterpret_cast<const double2 *>(p)[c];
-            v[2 * c] = t.x;
-            v[2 * c + 1] = t.y;
-        }
-    } else {
-#pragma unroll
-        for (int c = 0; c < W; ++c)
-            v[c] = p[c];
-    }
-}
-
-template <int W, bool VEC>
-__device__ __forceinline__ void store_cols(double *__restrict__ p, const double (&v)[W])
-{
-    if constexpr (VEC) {
-#pragma unroll
-        for (int c = 0; c < W / 2; ++c)
-            reinterpret_cast<double2 *>(p)[c] = double2{v[2 * c], v[2 * c + 1]};
-    } else {
-#pragma unroll
-        for (int c = 0; c < W; ++c)
-            p[c] = v[c];
-    }
-}
 
 // stage 1: columns j0 + W*blockIdx.y + [0, W); workgroup b sums rows
 // b*256 + t + s*G*256 (even steps s into s0, odd into s1) and writes
@@ -95,17 +60,7 @@ __global__ __launch_bounds__(kBlock) void dot_multi_partial_kernel(int64_t n, in
         for (int c = 0; c < W; ++c)
             s0[c] = fma(a0[c], b0[c], s0[c]);
     }
-#pragma unroll
-    for (int c = 0; c < W; ++c) {
-        const double t = group_sum<kWave>(s0[c] + s1[c]);
-        if (threadIdx.x % kWave == 0)
-            s_warp[c][threadIdx.x / kWave] = t;
-    }
-    __syncthreads();
-    if ((int)threadIdx.x < W) {
-        const double *s = s_warp[threadIdx.x];
-        partial[(int64_t)(j + (int32_t)threadIdx.x) * gridDim.x + blockIdx.x] = (s[0] + s[1]) + (s[2] + s[3]);
-    }
+    dot_partial_store<W>(s0, s1, s_warp, j, partial);
 }
 
 // stage 2: workgroup j folds column j's G partials in a fixed order
@@ -125,15 +80,6 @@ __global__ __launch_bounds__(1024) void dot_multi_final_kernel(int g, const doub
         if (threadIdx.x == 0)
             out[blockIdx.x] = t;
     }
-}
-
-// G: a function of n alone (the bit rule); every thread has two rows, one
-// per accumulator, before another workgroup is added
-static int dot_multi_blocks(int64_t n)
-{
-    const int64_t per = (int64_t)kBlock * 2;
-    const int64_t g = (n + per - 1) / per;
-    return (int)(g < 1 ? 1 : (g > kDotMultiBlocks ? kDotMultiBlocks : g));
 }
 
 // XPAY = false: Y = fma(c_j, X, Y), c_j = sign * (num[j] / den[j])
@@ -189,30 +135,6 @@ static unsigned update_multi_grid(int64_t n)
 {
     const int64_t g = (n + kBlock * 4 - 1) / (kBlock * 4);
     return (unsigned)(g < 1 ? 1 : (g > 256 * 16 ? 256 * 16 : g));
-}
-
-// the 16-byte path of a launch whose first column is j0: W even, the first
-// element 16-byte aligned and an even ld, so that every row start is aligned
-static bool vec_ok(const double *p, int64_t ld, int32_t j0, int w)
-{
-    return w % 2 == 0 && ld % 2 == 0 && (reinterpret_cast<uintptr_t>(p + j0) & 15) == 0;
-}
-
-// f(W, VEC, j0, chunks) for the whole blocks of kVecW columns, then for the
-// k % kVecW columns left: at most two launches
-template <typename F>
-static void for_column_blocks(int32_t k, const double *a, int64_t lda, const double *b, int64_t ldb, F &&f)
-{
-    const int32_t whole = k / kVecW, rest = k % kVecW;
-    if (whole > 0)
-        with_bool(vec_ok(a, lda, 0, kVecW) && vec_ok(b, ldb, 0, kVecW),
-                  [&](auto V) { f(std::integral_constant<int, kVecW>{}, V, 0, whole); });
-    if (rest > 0) {
-        const int32_t j0 = whole * kVecW;
-        with_bool(vec_ok(a, lda, j0, rest) && vec_ok(b, ldb, j0, rest), [&](auto V) {
-            with_int<1, 2, 3, 4, 5, 6, 7>(rest, [&](auto Wc) { f(Wc, V, j0, 1); });
-        });
-    }
 }
 
 template <bool XPAY>

@@ -41,6 +41,13 @@ memory.  build_operator(symmetric="fused" | "expand") builds the operator on
 the stored half of a symmetric matrix (prepare_symmetric), for cg, cg_multi
 and power_iteration alike.
 
+Preconditioning (build_operator(bjacobi=bs), cg / cg_multi(precond=...)): a
+block-Jacobi preconditioner (sa.BlockJacobi, csrc/precond.hip) built from the
+very shard the operator uploads.  It is fully parallel (no level schedules,
+nothing that waits on another workgroup), keeps every scalar in device memory,
+and its fused kernel also returns the two dot products a preconditioned
+iteration needs, so PCG launches as many kernels per iteration as CG.
+
 The device work goes through a `kernels` object (HipKernels by default).
 Tests substitute a numpy double to exercise the multi-rank orchestration on
 CPU ranks (gloo); the product path only ever builds HipKernels.
@@ -273,6 +280,16 @@ class HipKernels:
         nbytes = self.lib.spmv_dot_multi_ws_bytes(n, k)
         return torch.empty(nbytes, dtype=torch.uint8, device=self.dev)
 
+    # the preconditioner M (sa.BlockJacobi over this rank's n rows):
+    # Z = M^-1 R, out[:k] = column sums of R Z, out[k:2k] of R R
+    def precond_apply_dot(self, M, n, R, Z, out, ws) -> None:
+        sa._check(self.lib.spmv_bjacobi_apply_dot_multi(M.handle, R.shape[1], sa._ptr(R), self._ld(R), sa._ptr(Z),
+                                                        self._ld(Z), sa._ptr(out), sa._ptr(ws), ws.numel(), self._s()),
+                  "spmv_bjacobi_apply_dot_multi")
+
+    def precond_ws(self, M, n, k):
+        return M.ws(n, k)
+
 
 # --------------------------------------------------------------- operator
 @dataclass
@@ -286,6 +303,7 @@ class DistOperator:
     device: object = None
     remote: object = None  # kernels of the remote-column part (split shards only)
     overlap: bool = False  # split shards: run the local part while the all-gather is in flight
+    precond: object = None  # sa.BlockJacobi over this rank's rows (build_operator(bjacobi=bs)), or None
 
     @property
     def world(self) -> int:
@@ -306,7 +324,7 @@ class DistOperator:
 
 def build_operator(m: sa.Coo, rank: int = 0, world: int = 1, fmt: str = "csr", device="cuda:0", align: int = 1024,
                    split: bool = False, overlap: bool = False, expand_symmetric: bool = False,
-                   symmetric: str | None = None, **fmt_kw) -> DistOperator:
+                   symmetric: str | None = None, bjacobi: int | None = None, **fmt_kw) -> DistOperator:
     """Partition, renumber and upload this rank's shard (HIP kernels).
     split (implied by overlap): local / remote column parts
     (split_local_remote), each its own device matrix.
@@ -319,7 +337,19 @@ def build_operator(m: sa.Coo, rank: int = 0, world: int = 1, fmt: str = "csr", d
     with prepare_symmetric(symmetric), so the operator's products are
     run_sym / run_sym_multi ("expand" is bitwise reproducible, "fused" is
     not).  One rank, CSR, unsplit only; anything else is refused before
-    anything is uploaded."""
+    anything is uploaded.
+    bjacobi (a block size, 1..16): also builds a block-Jacobi preconditioner
+    (sa.BlockJacobi) from the very shard that is uploaded, whatever fmt, and
+    stores it in the operator's `precond`, which cg and cg_multi then use.
+    Its blocks are cut from this rank's rows, so they never span two ranks; a
+    split shard builds it from its local part."""
+    if bjacobi is not None and (not isinstance(bjacobi, (int, np.integer)) or isinstance(bjacobi, bool)
+                                or not 1 <= bjacobi <= 16):
+        raise sa.SpmvError(sa.OTHER_ERROR, "build_operator", f"bjacobi must be a block size in 1..16, not {bjacobi!r}")
+
+    def precond(shard, col_base=0, half=False):
+        return None if bjacobi is None else sa.BlockJacobi.from_coo(shard, int(bjacobi), device, col_base, half)
+
     if symmetric is not None:
         def refuse(why):
             return sa.SpmvError(sa.OTHER_ERROR, "build_operator", f"symmetric={symmetric!r}: {why}")
@@ -340,17 +370,19 @@ def build_operator(m: sa.Coo, rank: int = 0, world: int = 1, fmt: str = "csr", d
         layout = layout_for(m.n_rows, counts, 1, align)  # one block: positions are the identity
         dm = sa.to_device(m, "csr", device, **fmt_kw)  # the half itself, n x n
         dm.prepare_symmetric(symmetric)
-        return DistOperator(layout, rank, m.n_rows, HipKernels(dm, symmetric=True), device)
+        return DistOperator(layout, rank, m.n_rows, HipKernels(dm, symmetric=True), device,
+                            precond=precond(m, 0, True))
     if expand_symmetric:
         m = sa.expand_symmetric(m)
     counts = np.bincount(m.row, minlength=m.n_rows).astype(np.int64)
     layout = layout_for(m.n_rows, counts, world, align)
     loc = local_shard(m, layout, rank)
     if not (split or overlap):
-        return DistOperator(layout, rank, m.n_rows, HipKernels(sa.to_device(loc, fmt, device, **fmt_kw)), device)
+        return DistOperator(layout, rank, m.n_rows, HipKernels(sa.to_device(loc, fmt, device, **fmt_kw)), device,
+                            precond=precond(loc, rank * layout.pad))
     local, remote = split_local_remote(loc, layout, rank)
     return DistOperator(layout, rank, m.n_rows, HipKernels(sa.to_device(local, fmt, device, **fmt_kw)), device,
-                        HipKernels(sa.to_device(remote, fmt, device, **fmt_kw)), overlap)
+                        HipKernels(sa.to_device(remote, fmt, device, **fmt_kw)), overlap, precond(local))
 
 
 def _zeros(op, n):
@@ -487,11 +519,27 @@ def _power_iteration(op: DistOperator, iters: int, comm: Comm | None = None, x0=
 
 
 # ---------------------------------------------------------------------- CG
+def _precond_of(op, precond):
+    """precond=None: the operator's own preconditioner, if it has one;
+    False: none; anything else: that preconditioner."""
+    if precond is False:
+        return None
+    return getattr(op, "precond", None) if precond is None else precond
+
+
 def cg(op: DistOperator, b_loc, comm: Comm | None = None, tol: float = 1e-10, maxit: int = 1000,
-       check_every: int = 10):
-    """Conjugate gradients on the operator's kernel stream (_cg)."""
+       check_every: int = 10, precond=None):
+    """Conjugate gradients on the operator's kernel stream (_cg); with a
+    preconditioner (precond, or the operator's: _precond_of) preconditioned
+    CG through the block kernels with k = 1, ld = 1 (_pcg)."""
     with _kernel_stream(op):
-        return _cg(op, b_loc, comm, tol, maxit, check_every)
+        M = _precond_of(op, precond)
+        if M is None:
+            return _cg(op, b_loc, comm, tol, maxit, check_every)
+        comm = comm or Comm()
+        full, send = _gathered_pair(op, comm)
+        X, its, rel = _pcg(op, comm, M, b_loc.unsqueeze(1), full, send, False, tol, maxit, check_every)
+        return X[:, 0], its, float(rel[0])
 
 
 def _cg(op: DistOperator, b_loc, comm: Comm | None = None, tol: float = 1e-10, maxit: int = 1000,
@@ -535,11 +583,12 @@ def _cg(op: DistOperator, b_loc, comm: Comm | None = None, tol: float = 1e-10, m
 
 # ------------------------------------------------ CG, several right-hand sides
 def cg_multi(op: DistOperator, B_loc, comm: Comm | None = None, tol: float = 1e-10, maxit: int = 1000,
-             check_every: int = 10):
+             check_every: int = 10, precond=None):
     """Conjugate gradients for k right-hand sides at once, on the operator's
-    kernel stream (_cg_multi)."""
+    kernel stream (_cg_multi); preconditioned when the operator has a
+    preconditioner or `precond` names one (_precond_of; False: none)."""
     with _kernel_stream(op):
-        return _cg_multi(op, B_loc, comm, tol, maxit, check_every)
+        return _cg_multi(op, B_loc, comm, tol, maxit, check_every, _precond_of(op, precond))
 
 
 def _check_block(op, B_loc) -> int:
@@ -565,7 +614,7 @@ def _check_block(op, B_loc) -> int:
 
 
 def _cg_multi(op: DistOperator, B_loc, comm: Comm | None = None, tol: float = 1e-10, maxit: int = 1000,
-              check_every: int = 10):
+              check_every: int = 10, M=None):
     """k independent CG recurrences (x0 = 0, A symmetric positive definite),
     one per column of B_loc (rows, k), sharing one multi-vector product per
     iteration; NOT block CG (no k x k Gram systems).  Returns (X_local
@@ -589,7 +638,9 @@ def _cg_multi(op: DistOperator, B_loc, comm: Comm | None = None, tol: float = 1e
     With more than one rank the gathered layout carries over: `full` is
     (world * pad, k), `send` (pad, k), one all_gather_into_tensor per
     iteration and one all-reduce per k-vector of scalars.  Unsplit operators
-    only."""
+    only.
+
+    M (a preconditioner): the same checks and layout, then _pcg."""
     comm = comm or Comm()
     k = op.kernels
     if op.remote is not None:
@@ -606,6 +657,8 @@ def _cg_multi(op: DistOperator, B_loc, comm: Comm | None = None, tol: float = 1e
 
     send = zeros(op.pad, nv)
     full = zeros(op.world * op.pad, nv) if comm.world > 1 else send
+    if M is not None:
+        return _pcg(op, comm, M, B_loc, full, send, True, tol, maxit, check_every)
     P = send[:rows]
     X = zeros(rows, nv)
     R = B_loc.clone()
@@ -637,6 +690,81 @@ def _cg_multi(op: DistOperator, B_loc, comm: Comm | None = None, tol: float = 1e
         comm.allreduce(rr_new)
         k.xpay_ratio_multi(rows, rr_new, rr, R, P)  # p_j = r_j + beta_j p_j
         rr, rr_new = rr_new, rr
+        it += 1
+        if it % check_every == 0 or it == maxit:
+            if (rr.cpu().numpy() <= tol * tol * bb).all():
+                break
+    return X, it, rel(rr.cpu().numpy())
+
+
+# ------------------------------------------------------- preconditioned CG
+def _pcg(op: DistOperator, comm: Comm, M, B, full, send, multi: bool, tol: float, maxit: int, check_every: int):
+    """Preconditioned CG (x0 = 0) for the nv columns of B (rows, nv) with the
+    preconditioner M, one recurrence per column as in _cg_multi.  `full` and
+    `send` are the gathered buffers of the product: (.., nv) blocks and spmm
+    when `multi`, vectors and spmv otherwise (nv = 1: cg, any operator _cg
+    runs).  Returns (X (rows, nv), iterations, rel: numpy (nv,)).
+
+    Per iteration:
+        the product AP = A P                             1 launch
+        pAp = dot_multi(P, AP)                           2
+        x_j += alpha_j p_j, r_j -= alpha_j Ap_j          2   alpha_j = rz_j / pAp_j
+        z = M^-1 r, rz' = r.z, rr = r.r  (one kernel)    2   precond_apply_dot
+        p_j = z_j + beta_j p_j                           1   beta_j = rz'_j / rz_j
+    which is _cg_multi's count (8 for nv <= 8): the fused kernel stands where
+    dot_multi(R, R) stood.  rz' and rr are 2 nv scalars in one tensor and
+    travel in ONE all-reduce.  The stop test and the returned rel use rr
+    against bb, as without a preconditioner.  The zero-denominator rule of
+    the ratio kernels carries over: a column with b_j = 0 has z_j = 0 and
+    rz_j = 0, so alpha_j = beta_j = 0 and x_j stays exactly 0."""
+    torch = sa._torch()
+    k = op.kernels
+    rows = op.rows
+    nv = int(B.shape[1])
+
+    def zeros(*shape):
+        return torch.zeros(shape, dtype=torch.float64, device=op.device)
+
+    def block(t):  # a product vector as a (.., 1) block with ld = 1
+        return t if multi else t.unsqueeze(1)
+
+    P = block(send[:rows])
+    X = zeros(rows, nv)
+    R = B.clone()
+    Z = zeros(max(rows, 1), nv)
+    ap = zeros(max(rows, 1), nv) if multi else zeros(max(rows, 1))
+    AP = block(ap)
+    apply = _Apply(op, comm, full, send, multi=multi)
+    ws = k.dot_multi_ws(rows, nv)
+    pws = k.precond_ws(M, rows, nv)
+    pAp = zeros(nv)
+    # (rz, rr) of the last and of the coming residual: two tensors of 2 nv
+    # scalars, each with views of its halves (no slicing inside the loop)
+    (s, rz, rr), (s_new, rz_new, rr_new) = ((t, t[:nv], t[nv:]) for t in (zeros(2 * nv), zeros(2 * nv)))
+    k.precond_apply_dot(M, rows, R, Z, s, pws)
+    comm.allreduce(s)
+    bb = rr.cpu().numpy().copy()
+
+    def rel(rr_host):
+        out = np.zeros(nv)
+        live = bb > 0.0
+        out[live] = np.sqrt(np.maximum(rr_host[live], 0.0) / bb[live])
+        return out
+
+    if not (bb > 0.0).any():
+        return X, 0, np.zeros(nv)
+    P.copy_(Z[:rows])
+    it = 0
+    while it < maxit:
+        apply(ap)  # gathers P
+        k.dot_multi(rows, P, AP, pAp, ws)
+        comm.allreduce(pAp)
+        k.axpy_ratio_multi(rows, rz, pAp, 1.0, P, X)  # x_j += alpha_j p_j
+        k.axpy_ratio_multi(rows, rz, pAp, -1.0, AP, R)  # r_j -= alpha_j Ap_j
+        k.precond_apply_dot(M, rows, R, Z, s_new, pws)  # z = M^-1 r, (rz', rr)
+        comm.allreduce(s_new)
+        k.xpay_ratio_multi(rows, rz_new, rz, Z, P)  # p_j = z_j + beta_j p_j
+        (s, rz, rr), (s_new, rz_new, rr_new) = (s_new, rz_new, rr_new), (s, rz, rr)
         it += 1
         if it % check_every == 0 or it == maxit:
             if (rr.cpu().numpy() <= tol * tol * bb).all():

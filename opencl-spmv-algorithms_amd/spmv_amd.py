@@ -158,6 +158,15 @@ class MultiInfo(ctypes.Structure):
 
 MULTI_MODES = {None: 0, "balanced": 1}  # enum spmv_multi_mode
 
+
+class BjacobiInfo(ctypes.Structure):
+    """``spmv_bjacobi_info`` (include/spmv_ext.h)."""
+
+    _fields_ = [("bs", _c_i32), ("symmetric_half", _c_i32)] + \
+               [(k, _c_i64) for k in ("n", "n_blocks", "singular_blocks", "col_base", "owned_bytes")] + \
+               [("kernel", ctypes.c_char * 64)]
+
+
 _PP = ctypes.POINTER(_vp)
 _PO = ctypes.POINTER(PlanOpts)
 
@@ -299,6 +308,14 @@ HIP_SYMBOLS = {
                                              _c_i64, ctypes.c_int, _vp]),
     "spmv_xpay_ratio_multi": (ctypes.c_int, [_c_i64, ctypes.c_int32, _vp, _vp, _vp, _c_i64, _vp, _c_i64,
                                              ctypes.c_int, _vp]),
+    "spmv_bjacobi_create": (ctypes.c_int, [Dims, _vp, _vp, _vp, _c_i32, _c_i64, _c_i32, _PP]),
+    "spmv_bjacobi_get_info": (ctypes.c_int, [_vp, ctypes.POINTER(BjacobiInfo)]),
+    "spmv_bjacobi_inverse": (ctypes.c_int, [_vp, _PP]),
+    "spmv_bjacobi_apply_multi": (ctypes.c_int, [_vp, _c_i32, _vp, _c_i64, _vp, _c_i64, _vp]),
+    "spmv_bjacobi_ws_bytes": (ctypes.c_size_t, [_c_i64, _c_i32]),
+    "spmv_bjacobi_apply_dot_multi": (ctypes.c_int, [_vp, _c_i32, _vp, _c_i64, _vp, _c_i64, _vp, _vp, ctypes.c_size_t,
+                                                    _vp]),
+    "spmv_bjacobi_destroy": (ctypes.c_int, [_vp]),
     "spmv_gather": (ctypes.c_int, [_c_i64, _vp, _vp, _vp, ctypes.c_int, _vp]),
     "spmv_device_count": (ctypes.c_int, [ctypes.POINTER(ctypes.c_int)]),
     "spmv_set_device": (ctypes.c_int, [ctypes.c_int]),
@@ -345,6 +362,8 @@ HOST_SYMBOLS = {
     "spmv_coo_symmetrize": (ctypes.c_int, [_c_i64, _c_i64, _vp, _vp, _vp, ctypes.POINTER(_c_i64), _vp, _vp, _vp]),
     "spmv_cpu_csr_sym": (ctypes.c_int, [_c_i64, _vp, _vp, _vp, _vp, _vp]),
     "spmv_cpu_csr_sym_multi": (ctypes.c_int, [_c_i64, _vp, _vp, _vp, _c_i32, _vp, _c_i64, _vp, _c_i64]),
+    "spmv_bjacobi_build": (ctypes.c_int, [_c_i64, _vp, _vp, _vp, _c_i32, _c_i64, _c_i32, _vp, ctypes.POINTER(_c_i64)]),
+    "spmv_cpu_bjacobi_apply_multi": (ctypes.c_int, [_c_i64, _c_i32, _vp, _c_i32, _vp, _c_i64, _vp, _c_i64]),
     "spmv_csr_sort_rows": (ctypes.c_int, [_c_i64, _vp, _vp, _vp]),
     "spmv_csr_row_stats": (ctypes.c_int, [_c_i64, _vp, ctypes.POINTER(_c_i64), ctypes.POINTER(_c_i64), ctypes.POINTER(ctypes.c_double)]),
     "spmv_csr_pick_variant": (ctypes.c_int, [_c_i64, _vp]),
@@ -625,6 +644,44 @@ def cpu_csr_sym_multi(n: int, ptr, col, val, X: np.ndarray, Y: np.ndarray, k: in
     ldx, ldy = (a.strides[0] // 8 if a.shape[0] > 1 else k for a in (X, Y))  # one row: its stride is never used
     rc = host_lib().spmv_cpu_csr_sym_multi(n, _ptr(ptr), _ptr(col), _ptr(val), k, _ptr(X), ldx, _ptr(Y), ldy)
     _check_host(rc, "spmv_cpu_csr_sym_multi")
+
+
+def bjacobi_build_host(n: int, ptr, col, val, bs: int, col_base: int = 0, symmetric_half: bool = False):
+    """The host statement of the block-Jacobi preconditioner
+    (spmv_bjacobi_build) on a CSR with n rows -> (inv, singular): inv is
+    (ceil(n / bs) * bs, bs), row q*bs + r holding row r of D_q^-1; singular
+    counts the blocks replaced by the identity."""
+    if not 1 <= bs <= 16:  # before inv is sized
+        raise SpmvError(OTHER_ERROR, "bjacobi_build_host", f"bs must be 1..16, not {bs}")
+    n_blocks = (max(n, 0) + bs - 1) // bs
+    inv = np.empty((n_blocks * bs, bs), np.float64)
+    singular = _c_i64()
+    ptr, col, val = (np.ascontiguousarray(a, t) for a, t in ((ptr, np.int64), (col, np.int32), (val, np.float64)))
+    _check_host(host_lib().spmv_bjacobi_build(n, _ptr(ptr), _ptr(col), _ptr(val), bs, col_base, int(symmetric_half),
+                                              _ptr(inv), ctypes.byref(singular)), "spmv_bjacobi_build")
+    return inv, int(singular.value)
+
+
+def cpu_bjacobi_apply_multi(n: int, bs: int, inv: np.ndarray, R: np.ndarray, Z: np.ndarray, k: int | None = None) -> None:
+    """Host Z = M^-1 R (spmv_cpu_bjacobi_apply_multi) with inv from
+    bjacobi_build_host: R and Z (>= n rows) are 2-D float64 arrays with unit
+    inner stride; k defaults to R's width.  Only Z[:n, :k] is written."""
+    for a in (R, Z):
+        if not isinstance(a, np.ndarray) or a.dtype != np.float64 or a.ndim != 2:
+            raise SpmvError(OTHER_ERROR, "cpu_bjacobi_apply_multi", "R and Z must be 2-D float64 arrays")
+        if a.shape[1] > 1 and a.strides[1] != 8 or a.strides[0] % 8:
+            raise SpmvError(OTHER_ERROR, "cpu_bjacobi_apply_multi", "R and Z need unit inner stride")
+        if a.shape[0] < n:
+            raise SpmvError(OTHER_ERROR, "cpu_bjacobi_apply_multi", "R or Z has too few rows")
+    k = R.shape[1] if k is None else int(k)
+    if k > R.shape[1] or k > Z.shape[1]:
+        raise SpmvError(OTHER_ERROR, "cpu_bjacobi_apply_multi", "R or Z has fewer than k columns")
+    inv = np.ascontiguousarray(inv, np.float64)
+    if 1 <= bs <= 16 and inv.size < (max(n, 0) + bs - 1) // bs * bs * bs:
+        raise SpmvError(OTHER_ERROR, "cpu_bjacobi_apply_multi", "inv is too short")
+    ldr, ldz = (a.strides[0] // 8 if a.shape[0] > 1 else k for a in (R, Z))  # one row: its stride is never used
+    _check_host(host_lib().spmv_cpu_bjacobi_apply_multi(n, bs, _ptr(inv), k, _ptr(R), ldr, _ptr(Z), ldz),
+                "spmv_cpu_bjacobi_apply_multi")
 
 
 def csr_sort_rows(n_rows: int, ptr, col, val) -> None:
@@ -1363,6 +1420,108 @@ class DeviceMatrix:
 
 # the library's A/B switches (include/spmv_ext.h; placement and load policy only)
 OPTIONS = {"xwin_remap": 1, "xcd_remap": 2, "stream_nt": 3, "csr_col16": 5}
+
+
+class BlockJacobi:
+    """A block-Jacobi preconditioner resident in HBM (spmv_bjacobi_*,
+    include/spmv_ext.h): the inverses of the bs x bs diagonal blocks, built on
+    the device.  apply / apply_dot take row-major (>= n, k) float64 blocks
+    with unit inner stride (a 1-D tensor is one column)."""
+
+    def __init__(self, handle, device):
+        self.handle = handle
+        self.device = device
+        self.n = self.info()["n"]
+
+    @classmethod
+    def from_coo(cls, m: Coo, bs: int, device="cuda:0", col_base: int = 0, symmetric_half: bool = False):
+        """CSR on the host (file order inside a row), upload, create; the
+        uploads are dropped: the object keeps only the inverse."""
+        if not isinstance(bs, (int, np.integer)) or isinstance(bs, bool) or not 1 <= bs <= 16:
+            raise SpmvError(OTHER_ERROR, "BlockJacobi.from_coo", f"bs must be an integer in 1..16, not {bs!r}")
+        if col_base < 0:
+            raise SpmvError(OTHER_ERROR, "BlockJacobi.from_coo", "col_base must be >= 0")
+        lib = hip_lib()
+        torch = _torch()
+        dev = torch.device(device)
+        ptr, col, val = csr_from_coo(m)
+        d_ptr, d_col, d_val = (_dev_tensor(a, dev) for a in (ptr, col, val))
+        d = Dims(m.n_rows, m.n_cols, m.nnz, dev.index or 0, torch.cuda.current_stream(dev).cuda_stream)
+        handle = _vp()
+        _check(lib.spmv_bjacobi_create(d, _ptr(d_ptr), _ptr(d_col), _ptr(d_val), int(bs), int(col_base),
+                                       int(bool(symmetric_half)), ctypes.byref(handle)), "spmv_bjacobi_create")
+        return cls(handle, dev)
+
+    def __del__(self):
+        handle, self.handle = getattr(self, "handle", None), None
+        if handle is not None and _hip is not None and not sys.is_finalizing():
+            _hip.spmv_bjacobi_destroy(handle)
+
+    def info(self) -> dict:
+        info = BjacobiInfo()
+        _check(hip_lib().spmv_bjacobi_get_info(self.handle, ctypes.byref(info)), "spmv_bjacobi_get_info")
+        out = {k: int(getattr(info, k)) for k in ("bs", "n", "n_blocks", "singular_blocks", "col_base", "owned_bytes")}
+        out["symmetric_half"] = bool(info.symmetric_half)
+        out["kernel"] = info.kernel.decode()
+        return out
+
+    def inverse(self):
+        """A tensor copy of the inverse, (n_blocks * bs, bs)."""
+        torch = _torch()
+        i = self.info()
+        host = np.empty((i["n_blocks"] * i["bs"], i["bs"]), np.float64)
+        p = _vp()
+        _check(hip_lib().spmv_bjacobi_inverse(self.handle, ctypes.byref(p)), "spmv_bjacobi_inverse")
+        if host.size:  # the build synchronised: the inverse is complete
+            with torch.cuda.device(self.device):
+                _check(hip_lib().spmv_download(_ptr(host), p, host.nbytes, None), "download of the inverse")
+        return torch.from_numpy(host).to(self.device)
+
+    def _blocks(self, what, R, Z):
+        torch = _torch()
+        n = self.n
+        for t in (R, Z):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or t.dim() not in (1, 2):
+                raise SpmvError(OTHER_ERROR, what, "R and Z must be 1-D or 2-D float64 tensors")
+            if t.dim() == 2 and t.shape[1] > 1 and t.stride(1) != 1:
+                raise SpmvError(OTHER_ERROR, what, "R and Z need unit inner stride")
+            if t.dim() == 1 and t.numel() > 1 and t.stride(0) != 1:
+                raise SpmvError(OTHER_ERROR, what, "a 1-D R or Z must be contiguous")
+            if t.shape[0] < n:
+                raise SpmvError(OTHER_ERROR, what, "R or Z has too few rows")
+            if t.device.type != self.device.type or (t.device.index or 0) != (self.device.index or 0):
+                raise SpmvError(OTHER_ERROR, what, f"R and Z must be on {self.device}")
+        k = R.shape[1] if R.dim() == 2 else 1
+        if (Z.shape[1] if Z.dim() == 2 else 1) != k or k < 1:
+            raise SpmvError(OTHER_ERROR, what, "R and Z must have the same number k >= 1 of columns")
+        ld = [t.stride(0) if t.dim() == 2 and t.shape[0] > 1 else k for t in (R, Z)]
+        return k, ld[0], ld[1]
+
+    def _stream(self, stream):
+        st = stream if stream is not None else _torch().cuda.current_stream(self.device)
+        return st.cuda_stream
+
+    def apply(self, R, Z, stream=None) -> None:
+        """Z = M^-1 R on `stream` (default: torch's current stream)."""
+        k, ldr, ldz = self._blocks("BlockJacobi.apply", R, Z)
+        _check(hip_lib().spmv_bjacobi_apply_multi(self.handle, k, _ptr(R), ldr, _ptr(Z), ldz, self._stream(stream)),
+               "spmv_bjacobi_apply_multi")
+
+    def apply_dot(self, R, Z, out, ws, stream=None) -> None:
+        """Z = M^-1 R, out[:k] = column sums of R Z, out[k:2k] of R R; ws
+        from ws(n, k)."""
+        torch = _torch()
+        k, ldr, ldz = self._blocks("BlockJacobi.apply_dot", R, Z)
+        if not isinstance(out, torch.Tensor) or out.dtype != torch.float64 or not out.is_contiguous() or \
+                out.numel() < 2 * k or out.device != R.device or ws.device != R.device:
+            raise SpmvError(OTHER_ERROR, "BlockJacobi.apply_dot", "out must hold 2k float64 scalars on the device")
+        _check(hip_lib().spmv_bjacobi_apply_dot_multi(self.handle, k, _ptr(R), ldr, _ptr(Z), ldz, _ptr(out), _ptr(ws),
+                                                      ws.numel() * ws.element_size(), self._stream(stream)),
+               "spmv_bjacobi_apply_dot_multi")
+
+    def ws(self, n: int, k: int):
+        torch = _torch()
+        return torch.empty(hip_lib().spmv_bjacobi_ws_bytes(n, k), dtype=torch.uint8, device=self.device)
 
 
 def set_option(name: str, value: int | None) -> None:

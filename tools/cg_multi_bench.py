@@ -27,6 +27,20 @@ Matrices:
 One JSON line: per matrix, mode and k the ms per iteration of (a) and (b) with
 their spreads, the ratio (b)/(a), and `faster`: every window of (a) beat every
 window of (b), i.e. the margin exceeds the spread.
+
+--bjacobi BS measures block-Jacobi preconditioned CG instead (one JSON line):
+on the Laplacian, on cantlike_sym (forward) and on the block-congruence matrix
+(--congruence-grid g: the g x g Laplacian with BS unknowns per node under a
+random congruence per node, condition 1e4 each; tests/precond_cases.py has the
+reasoning) it builds ONE operator with build_operator(bjacobi=BS) and reports
+    per iteration: cg_multi(precond=False), which is cg_multi as it was before
+        the preconditioner existed (same launches, same bits), against
+        cg_multi with the preconditioner, same windows as above, tol = 0;
+    to --tol: the iterations both need for 2 right-hand sides (at most
+        --maxit), and the wall time of each solve.
+--trace N (with --bjacobi) runs nothing but 200 calls each of
+dot_multi(R, R) and of the fused apply_dot on N rows for k in {1, 2, 4, 8}: the
+workload of a kernel-trace run that compares the two kernels.
 """
 from __future__ import annotations
 
@@ -84,6 +98,37 @@ def lower(m: sa.Coo) -> sa.Coo:
     return sa.Coo(m.n_rows, m.n_cols, m.row[keep], m.col[keep], m.val[keep], True, m.label + " (lower)")
 
 
+def block_congruence(g: int, b: int, seed: int = 0) -> sa.Coo:
+    """W (L_g (x) I_b) W^T, symmetrised; W = blockdiag(U_q diag(10^u) V_q^T),
+    u uniform in [0, 2], U_q and V_q orthogonal (QR of normal samples)."""
+    import scipy.sparse as sp
+
+    lap = laplacian_2d(g)
+    n = lap.n_rows
+    L = sp.csr_matrix((lap.val, (lap.row, lap.col)), shape=(n, n))
+    rng = np.random.default_rng(seed)
+    U = np.linalg.qr(rng.standard_normal((n, b, b)))[0]
+    V = np.linalg.qr(rng.standard_normal((n, b, b)))[0]
+    Wq = np.einsum("qij,qj,qkj->qik", U, 10.0 ** rng.uniform(0.0, 2.0, (n, b)), V)
+    W = sp.bsr_matrix((Wq, np.arange(n), np.arange(n + 1)), shape=(n * b, n * b)).tocsr()
+    A = W @ sp.kron(L, sp.identity(b), format="csr") @ W.T
+    A = ((A + A.T) * 0.5).tocoo()
+    o = np.lexsort((A.col, A.row))
+    return sa.Coo(n * b, n * b, A.row[o].astype(np.int32), A.col[o].astype(np.int32), A.data[o].astype(np.float64),
+                  False, f"block congruence {g}x{g} nodes, {b} unknowns each")
+
+
+def block_diagonal(n: int, b: int, seed: int = 0) -> sa.Coo:
+    """n rows of diagonally dominant b x b blocks (the --trace workload)."""
+    i = np.arange(n, dtype=np.int64)
+    col = (i // b * b)[:, None] + np.arange(b)[None, :]
+    val = np.random.default_rng(seed).uniform(-1, 1, (n, b))
+    val[col == i[:, None]] += b + 1.0
+    keep = (col < n).ravel()
+    return sa.Coo(n, n, np.repeat(i, b)[keep].astype(np.int32), col.ravel()[keep].astype(np.int32), val.ravel()[keep],
+                  False, f"block diagonal {n} rows")
+
+
 def window_ms(torch, fn, n):
     """n calls of fn between two events on the current stream -> ms in all."""
     a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -112,12 +157,19 @@ def main():
     ap.add_argument("--check-every", type=int, default=10)
     ap.add_argument("--window", type=float, default=0.5, help="seconds of solves per timing window")
     ap.add_argument("--matrices", default="laplacian,cantlike_sym")
+    ap.add_argument("--bjacobi", type=int, default=0, help="block size: measure preconditioned CG instead")
+    ap.add_argument("--congruence-grid", type=int, default=128, help="--bjacobi: nodes per side of the congruence matrix")
+    ap.add_argument("--tol", type=float, default=1e-10, help="--bjacobi: tolerance of the solves that count iterations")
+    ap.add_argument("--maxit", type=int, default=20000)
+    ap.add_argument("--trace", type=int, default=0, help="--bjacobi: rows of the kernel-trace workload (nothing else runs)")
     a = ap.parse_args()
     import torch
 
     if not torch.cuda.is_available():
         sys.exit("cg_multi_bench: no GPU")
     dev = torch.device("cuda:0")
+    if a.bjacobi:
+        return precond_main(a, torch, dev)
     out = {"tool": "cg_multi_bench", "device": sa.device_name(0), "window_s": a.window, "windows": WINDOWS,
            "iters": a.iters, "check_every": a.check_every, "unit": "ms per iteration, all k columns", "results": {}}
     rng = np.random.default_rng(7)
@@ -155,6 +207,78 @@ def main():
                            "loop_ms": round(mb, 5), "loop_spread_ms": round(max(wb) - min(wb), 5),
                            "solves": [na, nb], "ratio": round(mb / ma, 3), "faster": max(wa) < min(wb)}
         del op, Bs, bs, fns
+    print(json.dumps(out))
+
+
+def precond_main(a, torch, dev):
+    bs = a.bjacobi
+    rng = np.random.default_rng(7)
+    if a.trace:
+        n = a.trace
+        M = sa.BlockJacobi.from_coo(block_diagonal(n, bs), bs, dev)
+        lib = sa.hip_lib()
+        for k in (1, 2, 4, 8):
+            R = torch.from_numpy(rng.uniform(-1, 1, (n, k))).to(dev)
+            Z = torch.zeros_like(R)
+            out = torch.zeros(2 * k, dtype=torch.float64, device=dev)
+            ws = M.ws(n, k)
+            s = torch.cuda.current_stream(dev).cuda_stream
+            for _ in range(200):
+                sa._check(lib.spmv_dot_multi(n, k, sa._ptr(R), k, sa._ptr(R), k, sa._ptr(out), sa._ptr(ws), ws.numel(), 0,
+                                             s), "spmv_dot_multi")
+            for _ in range(200):
+                M.apply_dot(R, Z, out, ws)
+        torch.cuda.synchronize()
+        print(json.dumps({"tool": "cg_multi_bench", "trace_rows": n, "bjacobi": bs, "calls": 200}))
+        return
+    out = {"tool": "cg_multi_bench", "device": sa.device_name(0), "bjacobi": bs, "window_s": a.window,
+           "windows": WINDOWS, "iters": a.iters, "check_every": a.check_every, "tol": a.tol, "maxit": a.maxit,
+           "unit": "ms per iteration, all k columns", "results": {}}
+    cases = []
+    for name in a.matrices.split(",") + ["congruence"]:
+        if name == "laplacian":
+            cases.append((name, laplacian_2d(a.grid)))
+        elif name == "cantlike_sym":
+            cases.append((name, cantlike_sym()))
+        elif name == "congruence":
+            cases.append((name, block_congruence(a.congruence_grid, bs)))
+        else:
+            sys.exit(f"cg_multi_bench: unknown matrix {name}")
+    for name, m in cases:
+        op = it.build_operator(m, 0, 1, "csr", dev, bjacobi=bs)
+        n = m.n_rows
+        res = out["results"].setdefault(name, {"rows": n, "stored_entries": m.nnz,
+                                               "singular_blocks": op.precond.info()["singular_blocks"]})
+        kw = dict(tol=0.0, maxit=a.iters, check_every=a.check_every)
+        for k in KS:
+            B = torch.from_numpy(rng.uniform(-1, 1, (n, k))).to(dev)
+            fa = lambda: it.cg_multi(op, B, precond=False, **kw)  # noqa: E731  the yardstick
+            fb = lambda: it.cg_multi(op, B, **kw)  # noqa: E731
+            assert fa()[1] == a.iters and fb()[1] == a.iters
+            torch.cuda.synchronize()
+            na, nb = calls_for(torch, fa, a.window), calls_for(torch, fb, a.window)
+            wa, wb = [], []
+            for _ in range(WINDOWS):
+                wa.append(window_ms(torch, fa, na) / (na * a.iters))
+                wb.append(window_ms(torch, fb, nb) / (nb * a.iters))
+            ma, mb = statistics.median(wa), statistics.median(wb)
+            res[str(k)] = {"cg_ms": round(ma, 5), "cg_spread_ms": round(max(wa) - min(wa), 5), "pcg_ms": round(mb, 5),
+                           "pcg_spread_ms": round(max(wb) - min(wb), 5), "solves": [na, nb],
+                           "pcg_over_cg": round(mb / ma, 3)}
+        B = torch.from_numpy(rng.uniform(-1, 1, (n, 2))).to(dev)
+        to_tol = {}
+        for label, pre in (("cg", False), ("pcg", None)):
+            it.cg_multi(op, B, tol=0.0, maxit=2, precond=pre)  # warm-up
+            torch.cuda.synchronize()
+            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0.record()
+            _, its, rel = it.cg_multi(op, B, tol=a.tol, maxit=a.maxit, check_every=a.check_every, precond=pre)
+            t1.record()
+            t1.synchronize()
+            to_tol[label] = {"iterations": its, "reached": bool((rel <= a.tol).all()), "rel_max": float(rel.max()),
+                             "solve_ms": round(t0.elapsed_time(t1), 3)}
+        res["to_tol"] = to_tol
+        del op
     print(json.dumps(out))
 
 
