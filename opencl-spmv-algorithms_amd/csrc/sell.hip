@@ -887,11 +887,14 @@ __global__ __launch_bounds__(kSellFixThreads) void sell_split_fix_kernel(int32_t
     // s form a prefix of [c, n_chunks); counted 1024 probes at a time
     __shared__ int64_t s_end;
     int64_t lo = c + 1, step = 64;
-    for (;;) {  // coarse: probes lo + t * step
+    for (bool first = true;; first = false) {  // coarse: probes lo + t * step
         const int64_t q = lo + (int64_t)threadIdx.x * step;
         const int n = __syncthreads_count(q < n_chunks && chunk_slice[q] == s);
         if (n < kSellFixThreads) {  // the end lies in (lo + (n-1)*step, lo + n*step]
-            lo = n > 0 ? lo + (int64_t)(n - 1) * step + 1 : lo;
+            // n == 0 after a full pass: that pass's last probe, lo - step,
+            // matched, so the fine pass starts right behind it (c matches by
+            // definition: the first pass keeps lo = c + 1)
+            lo = n > 0 ? lo + (int64_t)(n - 1) * step + 1 : (first ? lo : lo - step + 1);
             break;
         }
         lo += (int64_t)kSellFixThreads * step;

@@ -53,8 +53,10 @@ def test_dot_matches_fp64_and_is_deterministic(torch_dev, n):
     for k in range(2):
         assert lib.spmv_dot(n, sa._ptr(a), sa._ptr(b), sa._ptr(out[k:]), sa._ptr(ws), ws.numel(), 0, s) == 0
     torch.cuda.synchronize()
-    ref = float(np.dot(a[:n].cpu().numpy(), b[:n].cpu().numpy())) if n else 0.0
-    assert abs(float(out[0]) - ref) <= 1e-12 * max(1.0, float((a[:n].abs() * b[:n].abs()).sum()))
+    # n rounded products summed in any order: (n + 2) 2^-53 sum |a b| against
+    # an extended-precision sum (tests/exact.py's rule; n = 0: exactly 0)
+    prod = a[:n].cpu().numpy().astype(np.longdouble) * b[:n].cpu().numpy().astype(np.longdouble)
+    assert abs(np.longdouble(float(out[0])) - prod.sum()) <= (n + 2) * 2.0 ** -53 * float(np.abs(prod).sum())
     assert torch.equal(out[0:1].view(torch.int64), out[1:2].view(torch.int64))
 
 
