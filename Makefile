@@ -35,7 +35,7 @@ LIB_HIP  := $(LIBDIR)/libspmv_hip.so
 LIB_HOST := $(LIBDIR)/libspmv_host.so
 ORACLE   := oracle/liboracle.so
 
-.PHONY: all default lib oracle probes lab test-san test-san-transpose test-san-transpose-multi test-san-multi-plan test-san-symmetric test-san-symmetric-multi test-san-precond test-cpu test-gpu clean $(TARGETS)
+.PHONY: all default lib oracle probes lab test-san test-san-transpose test-san-transpose-multi test-san-multi-plan test-san-symmetric test-san-symmetric-multi test-san-precond test-san-cheb test-cpu test-gpu clean $(TARGETS)
 
 default: all
 all: lib $(TARGETS) probes
@@ -194,6 +194,17 @@ build/san/precond_harness: tests/san/precond_harness.c $(HOST_SRC) include/spmv_
 
 test-san-precond: build/san/precond_harness
 	$(SANENV) ASAN_OPTIONS=detect_leaks=1:exitcode=99 build/san/precond_harness tests/golden/*.mtx
+
+# the host statement of one Chebyshev step over block Jacobi
+# (spmv_cpu_bjacobi_cheb_step_multi) under ASan + UBSan: a stand-alone program
+# over every block size, short last blocks, exactly-sized buffers, Zout == Zin
+# and the refused inputs (tests/san/cheb_harness.c)
+build/san/cheb_harness: tests/san/cheb_harness.c $(HOST_SRC) include/spmv_host.h include/spmv_rc.h
+	@mkdir -p build/san
+	$(CC) -std=c11 -Wall -Wextra -Werror -fopenmp -Iinclude $(SANFLAGS) $< $(HOST_SRC) -o $@ -lm
+
+test-san-cheb: build/san/cheb_harness
+	$(SANENV) ASAN_OPTIONS=detect_leaks=1:exitcode=99 build/san/cheb_harness
 
 test-gpu: all oracle
 	python -m pytest tests/ -x -q -m gpu

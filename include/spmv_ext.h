@@ -476,6 +476,30 @@ size_t spmv_bjacobi_ws_bytes(int64_t n, int32_t k);
 int spmv_bjacobi_apply_dot_multi(const spmv_bjacobi *m, int32_t k, const double *R, int64_t ldr,
                                  double *Z, int64_t ldz, double *out, void *ws, size_t ws_bytes,
                                  void *stream);
+/* One step of the Chebyshev recurrence over M^-1 (iterate.Chebyshev), the
+ * device form of spmv_cpu_bjacobi_cheb_step_multi (spmv_host.h), which fixes
+ * the bits of every element of D and Zout whatever k, the leading dimensions,
+ * the alignment or the load width.  a and b are passed by value: no scalar
+ * lives on the device.  AZ == NULL is step 0 (Zin may then be NULL too).
+ * Zout may be Zin itself (same leading dimension); R, AZ, D, Zout, out and ws
+ * must not overlap otherwise.  The conventions of the two apply calls hold:
+ * asynchronous on `stream`, no allocation, no synchronisation (capturable),
+ * 8-byte alignment only, at most two launches (plus the final one of the dot
+ * form).  spmv_bjacobi_cheb_step_dot_multi also returns out[j] = sum_i
+ * R[i][j] Zout[i][j] and out[k + j] = sum_i R[i][j]^2 through spmv_dot_multi's
+ * tree, bit for bit what spmv_dot_multi(R, Zout) and spmv_dot_multi(R, R) give
+ * afterwards; ws holds spmv_bjacobi_ws_bytes(n, k) bytes; n == 0 writes 2k
+ * zeros.  SPMV_OTHER_ERROR, before anything is written, as the apply calls,
+ * and for Zout == Zin with two leading dimensions.                         */
+int spmv_bjacobi_cheb_step_multi(const spmv_bjacobi *m, int32_t k, double a, double b, const double *R,
+                                 int64_t ldr, const double *AZ, int64_t ldaz, double *D, int64_t ldd,
+                                 const double *Zin, int64_t ldzin, double *Zout, int64_t ldzout,
+                                 void *stream);
+int spmv_bjacobi_cheb_step_dot_multi(const spmv_bjacobi *m, int32_t k, double a, double b,
+                                     const double *R, int64_t ldr, const double *AZ, int64_t ldaz,
+                                     double *D, int64_t ldd, const double *Zin, int64_t ldzin,
+                                     double *Zout, int64_t ldzout, double *out, void *ws,
+                                     size_t ws_bytes, void *stream);
 int spmv_bjacobi_destroy(spmv_bjacobi *m);
 /* out[k] = x[order[k]]: x in the layout of a matrix whose columns were
  * relabelled by spmv_column_relabel (spmv_host.h), the input its SpMV

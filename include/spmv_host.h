@@ -386,6 +386,29 @@ int spmv_bjacobi_build(int64_t n, const int64_t *row_ptr, const int32_t *col, co
  * or written.                                                                */
 int spmv_cpu_bjacobi_apply_multi(int64_t n, int32_t bs, const double *inv, int32_t k,
                                  const double *R, int64_t ldr, double *Z, int64_t ldz);
+/* One step of the Chebyshev recurrence for A z = r over B = M^-1 A, M the block
+ * Jacobi preconditioner above (iterate.Chebyshev computes the scalars a, b from
+ * the bounds of B's spectrum; AZ holds A Z of the current iterate).  For row i
+ * of block q and column j < k:
+ *   t_c = R[c][j] - AZ[c][j] over the rows c of the block (AZ == NULL, "step 0":
+ *   t_c = R[c][j]); s = inv[i*bs] * t_0, then s = fma(inv[i*bs + c], t_c, s) in
+ *   column order (spmv_cpu_bjacobi_apply_multi's chain, short last block
+ *   included);
+ *   step 0:    d = b * s;                     D[i][j] = d, Zout[i][j] = d
+ *              (a, the old D and Zin are not read; Zin may be NULL);
+ *   otherwise: d = fma(a, D[i][j], b * s);    D[i][j] = d,
+ *              Zout[i][j] = Zin[i][j] + d.
+ * This fixes the bits of every element: the CPU statement of
+ * spmv_bjacobi_cheb_step_multi (spmv_ext.h).  Zout may be Zin itself (with the
+ * same leading dimension); no other overlap is allowed.  Nothing is read
+ * outside columns [0, k) of a row or at or past row n, nothing is written for
+ * j >= k.  SPMV_OTHER_ERROR, before anything is written, for a negative n, bs
+ * outside 1..16, k < 1, a leading dimension below k, a NULL array that would be
+ * read or written, or Zout == Zin with two leading dimensions.              */
+int spmv_cpu_bjacobi_cheb_step_multi(int64_t n, int32_t bs, const double *inv, int32_t k, double a,
+                                     double b, const double *R, int64_t ldr, const double *AZ,
+                                     int64_t ldaz, double *D, int64_t ldd, const double *Zin,
+                                     int64_t ldzin, double *Zout, int64_t ldzout);
 /* Y = A^T X for k >= 1 vectors stored row-major, the layout of
  * spmv_plan_run_t_multi (spmv.h): X[r*ldx + j], r < n_rows; Y[c*ldy + j],
  * c < n_cols; j < k; ldx >= k, ldy >= k.  Serial: zeroes Y[c*ldy + j], j < k,

@@ -24,6 +24,12 @@
 // tree: same G(n), same row -> workgroup, thread and step rule, same two
 // accumulators, same fold (dot_partial_store) and the same final kernel over
 // the 2k columns, so its sums have spmv_dot_multi's bits.
+//
+// Chebyshev step (spmv_bjacobi_cheb_step_multi, spmv_bjacobi_cheb_step_dot_multi;
+// iterate.Chebyshev).  The apply's lanes and chain over t_c = R_c - AZ_c, then
+// d = a D + b s and Zout = Zin + d on the thread's own elements, as
+// spmv_cpu_bjacobi_cheb_step_multi states it; a and b are kernel arguments.  The
+// dot form sums r z (z = Zout) and r r exactly as the fused apply does.
 #include <cstdio>
 #include <cstdlib>
 
@@ -270,6 +276,194 @@ static void launch_apply(const spmv_bjacobi *m, int32_t k, const double *R, int6
     });
 }
 
+// s = row i of M^-1 (R - AZ) (STEP0: of M^-1 R) for the W columns at R and AZ,
+// `own` = row i of R itself: bjacobi_row with a second operand stream.  The
+// difference is formed as the rows arrive, so a block row in flight costs 2 W
+// doubles while it loads and W afterwards; with W > 4 two block rows are in
+// flight instead of four, which keeps the W = 8 kernels clear of scratch.
+template <int W, bool VEC, bool STEP0>
+__device__ __forceinline__ void cheb_row(int64_t n, int32_t bs, int64_t i, const double *__restrict__ inv,
+                                         const double *__restrict__ R, int64_t ldr, const double *__restrict__ AZ,
+                                         int64_t ldaz, double (&s)[W], double (&own)[W])
+{
+    constexpr int U = W > 4 ? 2 : 4;
+    const int64_t q = i <= (int64_t)UINT32_MAX ? (int64_t)((uint32_t)i / (uint32_t)bs) : i / bs;
+    const int64_t r0 = q * bs;
+    const int32_t nb = n - r0 < bs ? (int32_t)(n - r0) : bs;
+    const int32_t me = (int32_t)(i - r0);
+    const double *a = inv + i * bs;
+    const double *Rb = R + r0 * ldr;
+    const double *Ab = STEP0 ? nullptr : AZ + r0 * ldaz;
+#pragma unroll
+    for (int w = 0; w < W; ++w)
+        s[w] = own[w] = 0.0;
+    for (int32_t c0 = 0; c0 < nb; c0 += U) {
+        double av[U], rv[U][W], tv[U][W];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int32_t c = c0 + u < nb ? c0 + u : nb - 1;
+            av[u] = a[c];
+            load_cols<W, VEC>(Rb + (int64_t)c * ldr, rv[u]);
+            if constexpr (!STEP0)
+                load_cols<W, VEC>(Ab + (int64_t)c * ldaz, tv[u]);
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int32_t c = c0 + u;
+            if (c < nb) {
+#pragma unroll
+                for (int w = 0; w < W; ++w) {
+                    const double t = STEP0 ? rv[u][w] : rv[u][w] - tv[u][w];
+                    s[w] = c == 0 ? av[u] * t : fma(av[u], t, s[w]);
+                    own[w] = c == me ? rv[u][w] : own[w];
+                }
+            }
+        }
+    }
+}
+
+// the thread's own elements: d = b s (STEP0) or fma(a, D, b s); D = d,
+// Zout = d (STEP0) or Zin + d, which is also left in z
+template <int W, bool VEC, bool STEP0>
+__device__ __forceinline__ void cheb_update(double a, double b, const double (&s)[W], double *D, const double *Zin,
+                                            double *Zout, double (&z)[W])
+{
+    double d[W];
+    if constexpr (STEP0) {
+#pragma unroll
+        for (int w = 0; w < W; ++w)
+            z[w] = d[w] = b * s[w];
+    } else {
+        double dv[W], zi[W];
+        load_cols<W, VEC>(D, dv);
+        load_cols<W, VEC>(Zin, zi);
+#pragma unroll
+        for (int w = 0; w < W; ++w) {
+            d[w] = fma(a, dv[w], b * s[w]);
+            z[w] = zi[w] + d[w];
+        }
+    }
+    store_cols<W, VEC>(D, d);
+    store_cols<W, VEC>(Zout, z);
+}
+
+// One Chebyshev step (spmv_cpu_bjacobi_cheb_step_multi) for columns
+// j0 + W*blockIdx.y + [0, W): bjacobi_apply_kernel's rows, lanes and, with DOT,
+// its sums of r z and r r with z = Zout.  Zin and Zout may be one array: an
+// element is read and written by its own thread only.
+template <int W, bool VEC, bool DOT, bool STEP0>
+__global__ __launch_bounds__(kBlock) void bjacobi_cheb_kernel(int64_t n, int32_t bs, int32_t j0, int32_t k, double a,
+                                                              double b, const double *__restrict__ inv,
+                                                              const double *__restrict__ R, int64_t ldr,
+                                                              const double *__restrict__ AZ, int64_t ldaz,
+                                                              double *__restrict__ D, int64_t ldd, const double *Zin,
+                                                              int64_t ldzin, double *Zout, int64_t ldzout,
+                                                              double *__restrict__ partial)
+{
+    const int32_t j = j0 + W * (int32_t)blockIdx.y;
+    R += j;
+    D += j;
+    Zout += j;
+    if constexpr (!STEP0) {
+        AZ += j;
+        Zin += j;
+    }
+    const int64_t stride = (int64_t)gridDim.x * kBlock;
+    double rz0[W], rz1[W], rr0[W], rr1[W];
+#pragma unroll
+    for (int c = 0; c < W; ++c)
+        rz0[c] = rz1[c] = rr0[c] = rr1[c] = 0.0;
+    int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    for (; i + stride < n; i += 2 * stride) {
+        double s0[W], o0[W], z0[W], s1[W], o1[W], z1[W];
+        cheb_row<W, VEC, STEP0>(n, bs, i, inv, R, ldr, AZ, ldaz, s0, o0);
+        cheb_update<W, VEC, STEP0>(a, b, s0, D + i * ldd, Zin + i * ldzin, Zout + i * ldzout, z0);
+        cheb_row<W, VEC, STEP0>(n, bs, i + stride, inv, R, ldr, AZ, ldaz, s1, o1);
+        cheb_update<W, VEC, STEP0>(a, b, s1, D + (i + stride) * ldd, Zin + (i + stride) * ldzin,
+                                   Zout + (i + stride) * ldzout, z1);
+        if constexpr (DOT) {
+#pragma unroll
+            for (int c = 0; c < W; ++c) {
+                rz0[c] = fma(o0[c], z0[c], rz0[c]);
+                rz1[c] = fma(o1[c], z1[c], rz1[c]);
+                rr0[c] = fma(o0[c], o0[c], rr0[c]);
+                rr1[c] = fma(o1[c], o1[c], rr1[c]);
+            }
+        }
+    }
+    if (i < n) {
+        double s0[W], o0[W], z0[W];
+        cheb_row<W, VEC, STEP0>(n, bs, i, inv, R, ldr, AZ, ldaz, s0, o0);
+        cheb_update<W, VEC, STEP0>(a, b, s0, D + i * ldd, Zin + i * ldzin, Zout + i * ldzout, z0);
+        if constexpr (DOT) {
+#pragma unroll
+            for (int c = 0; c < W; ++c) {
+                rz0[c] = fma(o0[c], z0[c], rz0[c]);
+                rr0[c] = fma(o0[c], o0[c], rr0[c]);
+            }
+        }
+    }
+    if constexpr (DOT) {
+        __shared__ double s_rz[W][kBlock / kWave], s_rr[W][kBlock / kWave];
+        dot_partial_store<W>(rz0, rz1, s_rz, j, partial);
+        dot_partial_store<W>(rr0, rr1, s_rr, (int64_t)k + j, partial);
+    }
+}
+
+struct ChebOperands {
+    double a, b;
+    const double *R;
+    int64_t ldr;
+    const double *AZ;  // nullptr: step 0
+    int64_t ldaz;
+    double *D;
+    int64_t ldd;
+    const double *Zin;
+    int64_t ldzin;
+    double *Zout;
+    int64_t ldzout;
+};
+
+// at most two launches, as for_column_blocks; the 16-byte path needs every
+// array the step touches on it
+template <bool DOT>
+static void launch_cheb(const spmv_bjacobi *m, int32_t k, const ChebOperands &o, double *partial, hipStream_t st)
+{
+    const int g = dot_multi_blocks(m->n);
+    const bool step0 = o.AZ == nullptr;
+    const auto launch = [&](auto Wc, int32_t j0, int32_t chunks) {
+        constexpr int W = decltype(Wc)::value;
+        const bool vec = vec_ok(o.R, o.ldr, j0, W) && vec_ok(o.D, o.ldd, j0, W) && vec_ok(o.Zout, o.ldzout, j0, W) &&
+                         (step0 || (vec_ok(o.AZ, o.ldaz, j0, W) && vec_ok(o.Zin, o.ldzin, j0, W)));
+        with_bool(vec, [&](auto V) {
+            with_bool(step0, [&](auto S0) {
+                constexpr bool VEC = decltype(V)::value && W % 2 == 0;
+                constexpr bool STEP0 = decltype(S0)::value;
+                hipLaunchKernelGGL((bjacobi_cheb_kernel<W, VEC, DOT, STEP0>), dim3(g, (unsigned)chunks), dim3(kBlock),
+                                   0, st, m->n, m->bs, j0, k, o.a, o.b, m->inv, o.R, o.ldr, o.AZ, o.ldaz, o.D, o.ldd,
+                                   o.Zin, o.ldzin, o.Zout, o.ldzout, partial);
+            });
+        });
+    };
+    const int32_t whole = k / kVecW, rest = k % kVecW;
+    if (whole > 0)
+        launch(std::integral_constant<int, kVecW>{}, 0, whole);
+    if (rest > 0)
+        with_int<1, 2, 3, 4, 5, 6, 7>(rest, [&](auto Wc) { launch(Wc, whole * kVecW, 1); });
+}
+
+// the refusals of both step calls
+static bool cheb_bad(const spmv_bjacobi *m, int32_t k, const ChebOperands &o)
+{
+    if (!m || k < 1 || o.ldr < k || o.ldd < k || o.ldzout < k)
+        return true;
+    if (o.AZ && (o.ldaz < k || o.ldzin < k))
+        return true;
+    if (m->n > 0 && (!o.R || !o.D || !o.Zout || (o.AZ && !o.Zin)))
+        return true;
+    return o.AZ && o.Zin && o.Zin == o.Zout && o.ldzin != o.ldzout;
+}
+
 }  // namespace spmv
 
 using namespace spmv;
@@ -391,6 +585,57 @@ extern "C" int spmv_bjacobi_apply_dot_multi(const spmv_bjacobi *m, int32_t k, co
     hipLaunchKernelGGL(dot_multi_final_kernel, dim3(2 * (unsigned)k), dim3(1024), 0, st, dot_multi_blocks(m->n),
                        (const double *)ws, out);
     SPMV_CHECK_LAUNCH("bjacobi_apply_dot kernels");
+    return SPMV_SUCCESS;
+}
+
+static ChebOperands cheb_operands(double a, double b, const double *R, int64_t ldr, const double *AZ, int64_t ldaz,
+                                  double *D, int64_t ldd, const double *Zin, int64_t ldzin, double *Zout,
+                                  int64_t ldzout)
+{
+    if (!AZ)  // step 0 reads neither: no stray operand reaches the kernel
+        return ChebOperands{a, b, R, ldr, nullptr, 0, D, ldd, nullptr, 0, Zout, ldzout};
+    return ChebOperands{a, b, R, ldr, AZ, ldaz, D, ldd, Zin, ldzin, Zout, ldzout};
+}
+
+extern "C" int spmv_bjacobi_cheb_step_multi(const spmv_bjacobi *m, int32_t k, double a, double b, const double *R,
+                                            int64_t ldr, const double *AZ, int64_t ldaz, double *D, int64_t ldd,
+                                            const double *Zin, int64_t ldzin, double *Zout, int64_t ldzout,
+                                            void *stream)
+{
+    const ChebOperands o = cheb_operands(a, b, R, ldr, AZ, ldaz, D, ldd, Zin, ldzin, Zout, ldzout);
+    if (cheb_bad(m, k, o))
+        return fail_msg(SPMV_OTHER_ERROR, "spmv_bjacobi_cheb_step_multi: bad arguments (k >= 1, every ld >= k, no "
+                                          "NULL array, Zout == Zin with one ld)");
+    if (m->n == 0)
+        return SPMV_SUCCESS;
+    DeviceGuard guard(m->device);
+    if (guard.rc() != SPMV_SUCCESS)
+        return guard.rc();
+    launch_cheb<false>(m, k, o, nullptr, (hipStream_t)stream);
+    SPMV_CHECK_LAUNCH("bjacobi_cheb_kernel");
+    return SPMV_SUCCESS;
+}
+
+extern "C" int spmv_bjacobi_cheb_step_dot_multi(const spmv_bjacobi *m, int32_t k, double a, double b,
+                                                const double *R, int64_t ldr, const double *AZ, int64_t ldaz,
+                                                double *D, int64_t ldd, const double *Zin, int64_t ldzin,
+                                                double *Zout, int64_t ldzout, double *out, void *ws, size_t ws_bytes,
+                                                void *stream)
+{
+    const ChebOperands o = cheb_operands(a, b, R, ldr, AZ, ldaz, D, ldd, Zin, ldzin, Zout, ldzout);
+    if (cheb_bad(m, k, o) || !out)
+        return fail_msg(SPMV_OTHER_ERROR, "spmv_bjacobi_cheb_step_dot_multi: bad arguments (k >= 1, every ld >= k, "
+                                          "no NULL array, Zout == Zin with one ld)");
+    if (!ws || ws_bytes < spmv_bjacobi_ws_bytes(m->n, k))
+        return fail_msg(SPMV_OTHER_ERROR, "spmv_bjacobi_cheb_step_dot_multi: workspace too small");
+    DeviceGuard guard(m->device);
+    if (guard.rc() != SPMV_SUCCESS)
+        return guard.rc();
+    const hipStream_t st = (hipStream_t)stream;
+    launch_cheb<true>(m, k, o, (double *)ws, st);
+    hipLaunchKernelGGL(dot_multi_final_kernel, dim3(2 * (unsigned)k), dim3(1024), 0, st, dot_multi_blocks(m->n),
+                       (const double *)ws, out);
+    SPMV_CHECK_LAUNCH("bjacobi_cheb_step_dot kernels");
     return SPMV_SUCCESS;
 }
 

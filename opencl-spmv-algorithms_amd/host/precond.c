@@ -2,8 +2,9 @@
  * precond.c — the host statement of the block-Jacobi preconditioner
  * (spmv_host.h): spmv_bjacobi_build extracts the bs x bs diagonal blocks of a
  * CSR matrix and inverts each, spmv_cpu_bjacobi_apply_multi is Z = M^-1 R on
- * row-major blocks of k vectors.  The device object of csrc/precond.hip
- * follows both step for step; never a device fallback.
+ * row-major blocks of k vectors, spmv_cpu_bjacobi_cheb_step_multi one step of
+ * the Chebyshev recurrence over M^-1.  The device object of csrc/precond.hip
+ * follows all three step for step; never a device fallback.
  *
  * One block: D (bs x bs, a short last block completed with the identity) is
  * reduced next to an identity, [D | I] -> [I | D^-1], by row operations in the
@@ -139,6 +140,43 @@ int spmv_cpu_bjacobi_apply_multi(int64_t n, int32_t bs, const double *inv, int32
             for (int32_t c = 1; c < nb; ++c)
                 s = fma(a[c], R[(r0 + c) * ldr + j], s);
             Z[i * ldz + j] = s;
+        }
+    }
+    return SPMV_SUCCESS;
+}
+
+/* One step of the Chebyshev recurrence over M^-1 (spmv_host.h).  A block's
+ * rows of R and AZ are read before any of its rows of D and Zout is written,
+ * and an element of D or Zin is read only by the row that rewrites it, so
+ * Zout == Zin needs no copy. */
+int spmv_cpu_bjacobi_cheb_step_multi(int64_t n, int32_t bs, const double *inv, int32_t k, double a, double b,
+                                     const double *R, int64_t ldr, const double *AZ, int64_t ldaz, double *D,
+                                     int64_t ldd, const double *Zin, int64_t ldzin, double *Zout, int64_t ldzout)
+{
+    if (n < 0 || bs < 1 || bs > BJ_MAX || k < 1 || ldr < k || ldd < k || ldzout < k ||
+        (AZ && (ldaz < k || ldzin < k)) || (n > 0 && (!inv || !R || !D || !Zout || (AZ && !Zin))) ||
+        (AZ && Zin == Zout && Zin && ldzin != ldzout))
+        return SPMV_OTHER_ERROR;
+    for (int64_t i = 0; i < n; ++i) {
+        const int64_t r0 = i / bs * bs;
+        const int32_t nb = (int32_t)(n - r0 < bs ? n - r0 : bs);
+        const double *w = inv + i * bs;
+        for (int32_t j = 0; j < k; ++j) {
+            double t = AZ ? R[r0 * ldr + j] - AZ[r0 * ldaz + j] : R[r0 * ldr + j];
+            double s = w[0] * t;
+            for (int32_t c = 1; c < nb; ++c) {
+                t = AZ ? R[(r0 + c) * ldr + j] - AZ[(r0 + c) * ldaz + j] : R[(r0 + c) * ldr + j];
+                s = fma(w[c], t, s);
+            }
+            const double bsum = b * s;
+            if (!AZ) {
+                D[i * ldd + j] = bsum;
+                Zout[i * ldzout + j] = bsum;
+            } else {
+                const double d = fma(a, D[i * ldd + j], bsum);
+                D[i * ldd + j] = d;
+                Zout[i * ldzout + j] = Zin[i * ldzin + j] + d;
+            }
         }
     }
     return SPMV_SUCCESS;

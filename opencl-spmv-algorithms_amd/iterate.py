@@ -47,6 +47,10 @@ very shard the operator uploads.  It is fully parallel (no level schedules,
 nothing that waits on another workgroup), keeps every scalar in device memory,
 and its fused kernel also returns the two dot products a preconditioned
 iteration needs, so PCG launches as many kernels per iteration as CG.
+build_operator(chebyshev=deg) puts a Chebyshev polynomial of that degree in
+M^-1 A over it (Chebyshev): the stronger preconditioner that keeps to the same
+rule.  Its coefficients are host floats computed before the solve, so an inner
+step is one product and one fused kernel, with no reduction.
 
 The device work goes through a `kernels` object (HipKernels by default).
 Tests substitute a numpy double to exercise the multi-rank orchestration on
@@ -290,6 +294,26 @@ class HipKernels:
     def precond_ws(self, M, n, k):
         return M.ws(n, k)
 
+    # one step of the Chebyshev recurrence over M^-1 (Chebyshev below): AZ =
+    # None is step 0, D = Zout = b M^-1 R; otherwise D = a D + b M^-1 (R - AZ),
+    # Zout = Zin + D (Zout may be Zin).  a and b are host floats.
+    def _cheb_args(self, M, a, b, R, AZ, D, Zin, Zout):
+        if AZ is None:
+            Zin = None
+        ld = [0 if t is None else self._ld(t) for t in (R, AZ, D, Zin, Zout)]
+        return (M.handle, R.shape[1], float(a), float(b), sa._ptr(R), ld[0], sa._ptr(AZ), ld[1], sa._ptr(D), ld[2],
+                sa._ptr(Zin), ld[3], sa._ptr(Zout), ld[4])
+
+    def cheb_step(self, M, n, a, b, R, AZ, D, Zin, Zout) -> None:
+        sa._check(self.lib.spmv_bjacobi_cheb_step_multi(*self._cheb_args(M, a, b, R, AZ, D, Zin, Zout), self._s()),
+                  "spmv_bjacobi_cheb_step_multi")
+
+    def cheb_step_dot(self, M, n, a, b, R, AZ, D, Zin, Zout, out, ws) -> None:
+        """cheb_step, and out[:k] = column sums of R Zout, out[k:2k] of R R."""
+        sa._check(self.lib.spmv_bjacobi_cheb_step_dot_multi(*self._cheb_args(M, a, b, R, AZ, D, Zin, Zout),
+                                                            sa._ptr(out), sa._ptr(ws), ws.numel(), self._s()),
+                  "spmv_bjacobi_cheb_step_dot_multi")
+
 
 # --------------------------------------------------------------- operator
 @dataclass
@@ -303,7 +327,8 @@ class DistOperator:
     device: object = None
     remote: object = None  # kernels of the remote-column part (split shards only)
     overlap: bool = False  # split shards: run the local part while the all-gather is in flight
-    precond: object = None  # sa.BlockJacobi over this rank's rows (build_operator(bjacobi=bs)), or None
+    # sa.BlockJacobi over this rank's rows (build_operator(bjacobi=bs)), a Chebyshev over one (chebyshev=deg), or None
+    precond: object = None
 
     @property
     def world(self) -> int:
@@ -324,7 +349,8 @@ class DistOperator:
 
 def build_operator(m: sa.Coo, rank: int = 0, world: int = 1, fmt: str = "csr", device="cuda:0", align: int = 1024,
                    split: bool = False, overlap: bool = False, expand_symmetric: bool = False,
-                   symmetric: str | None = None, bjacobi: int | None = None, **fmt_kw) -> DistOperator:
+                   symmetric: str | None = None, bjacobi: int | None = None, chebyshev: int | None = None,
+                   cheb_ratio: float = 30.0, cheb_boost: float = 1.1, cheb_bounds=None, **fmt_kw) -> DistOperator:
     """Partition, renumber and upload this rank's shard (HIP kernels).
     split (implied by overlap): local / remote column parts
     (split_local_remote), each its own device matrix.
@@ -342,7 +368,52 @@ def build_operator(m: sa.Coo, rank: int = 0, world: int = 1, fmt: str = "csr", d
     (sa.BlockJacobi) from the very shard that is uploaded, whatever fmt, and
     stores it in the operator's `precond`, which cg and cg_multi then use.
     Its blocks are cut from this rank's rows, so they never span two ranks; a
-    split shard builds it from its local part."""
+    split shard builds it from its local part.
+    chebyshev (a degree, 1..16): the preconditioner becomes a Chebyshev
+    polynomial of that degree in M^-1 A over the block-Jacobi M (Chebyshev;
+    bjacobi=None then means bs = 1, point Jacobi): `precond` is the Chebyshev
+    object and `precond.M` the sa.BlockJacobi.  Unsplit operators only.
+    cheb_bounds=(lmin, lmax), 0 < lmin < lmax, is taken as given.  Otherwise
+    lmax = cheb_boost * estimate_lmax(op, M) (10 steps of the power method;
+    with world > 1 every rank must be building its operator, since the
+    estimate all-reduces over torch.distributed) and lmin = lmax / cheb_ratio.
+    10 steps, 1.1 and 30 are the conventions of Ifpack2's and hypre's
+    Chebyshev smoothers, not measurements of this project's.  The power method
+    approaches the largest eigenvalue from below and AN UNDERESTIMATED lmax
+    MAKES THE PRECONDITIONER INDEFINITE (CG may then break down or stall):
+    that is what cheb_boost guards against; raise it, or pass cheb_bounds,
+    for a matrix on which ten steps are too few."""
+    def refuse_cheb(why):
+        return sa.SpmvError(sa.OTHER_ERROR, "build_operator", f"chebyshev={chebyshev!r}: {why}")
+
+    if chebyshev is None:
+        if cheb_bounds is not None:
+            raise sa.SpmvError(sa.OTHER_ERROR, "build_operator", "cheb_bounds without chebyshev=degree")
+    else:
+        if not isinstance(chebyshev, (int, np.integer)) or isinstance(chebyshev, bool) or not 1 <= chebyshev <= 16:
+            raise refuse_cheb("must be a degree in 1..16")
+        if split or overlap:
+            raise refuse_cheb("no split / overlap operators")
+        if cheb_bounds is not None:
+            try:
+                lmin, lmax = (float(v) for v in cheb_bounds)
+            except (TypeError, ValueError):
+                raise refuse_cheb(f"cheb_bounds must be (lmin, lmax), not {cheb_bounds!r}") from None
+            if not (np.isfinite(lmax) and 0.0 < lmin < lmax):
+                raise refuse_cheb(f"cheb_bounds must satisfy 0 < lmin < lmax, not {cheb_bounds!r}")
+        elif not (np.isfinite(cheb_ratio) and cheb_ratio > 1.0 and np.isfinite(cheb_boost) and cheb_boost > 0.0):
+            raise refuse_cheb("cheb_ratio must be > 1 and cheb_boost > 0")
+        if bjacobi is None:
+            bjacobi = 1
+        op = build_operator(m, rank, world, fmt, device, align, False, False, expand_symmetric, symmetric, bjacobi,
+                            **fmt_kw)
+        M = op.precond
+        if cheb_bounds is None:
+            comm = Comm(sa._torch().distributed) if world > 1 else Comm()
+            lmax = float(cheb_boost) * estimate_lmax(op, M, comm)
+            lmin = lmax / float(cheb_ratio)
+        op.precond = Chebyshev(M, int(chebyshev), lmin, lmax)
+        return op
     if bjacobi is not None and (not isinstance(bjacobi, (int, np.integer)) or isinstance(bjacobi, bool)
                                 or not 1 <= bjacobi <= 16):
         raise sa.SpmvError(sa.OTHER_ERROR, "build_operator", f"bjacobi must be a block size in 1..16, not {bjacobi!r}")
@@ -536,6 +607,8 @@ def cg(op: DistOperator, b_loc, comm: Comm | None = None, tol: float = 1e-10, ma
         M = _precond_of(op, precond)
         if M is None:
             return _cg(op, b_loc, comm, tol, maxit, check_every)
+        if isinstance(M, Chebyshev):
+            M.check(op)
         comm = comm or Comm()
         full, send = _gathered_pair(op, comm)
         X, its, rel = _pcg(op, comm, M, b_loc.unsqueeze(1), full, send, False, tol, maxit, check_every)
@@ -697,6 +770,144 @@ def _cg_multi(op: DistOperator, B_loc, comm: Comm | None = None, tol: float = 1e
     return X, it, rel(rr.cpu().numpy())
 
 
+# ------------------------------------------- Chebyshev over block Jacobi
+def chebyshev_coefficients(degree: int, lmin: float, lmax: float):
+    """The `degree` pairs (a_i, b_i) of the Chebyshev recurrence for A z = r
+    over B = M^-1 A with spectrum bounds (lmin, lmax), as host floats:
+    theta = (lmax + lmin) / 2, delta = (lmax - lmin) / 2, sigma = theta / delta,
+    rho_0 = 1 / sigma;  step 0: (0, 1 / theta);  step i >= 1:
+    rho_i = 1 / (2 sigma - rho_(i-1)), a_i = rho_i rho_(i-1), b_i = 2 rho_i / delta."""
+    theta, delta = (lmax + lmin) / 2.0, (lmax - lmin) / 2.0
+    sigma = theta / delta
+    rho = 1.0 / sigma
+    coef = [(0.0, 1.0 / theta)]
+    for _ in range(1, degree):
+        rho_new = 1.0 / (2.0 * sigma - rho)
+        coef.append((rho_new * rho, 2.0 * rho_new / delta))
+        rho = rho_new
+    return coef
+
+
+class Chebyshev:
+    """z = p(M^-1 A) M^-1 r: `degree` steps of the Chebyshev recurrence for
+    A z = r over B = M^-1 A, M a block-Jacobi preconditioner (sa.BlockJacobi,
+    or a test double of it), with the bounds (lmin, lmax) of B's spectrum:
+        step 0:      d = (1/theta) M^-1 r,  z = d
+        step i >= 1: d = a_i d + b_i M^-1 (r - A z),  z = z + d
+    (chebyshev_coefficients).  degree applications of M^-1 and degree - 1
+    products; a step is one fused kernel (kernels.cheb_step), so an inner step
+    costs a product and a vector kernel and no reduction: the coefficients are
+    host floats, known before the solve.  The polynomial is fixed, hence a
+    legitimate (linear, symmetric) preconditioner for CG; it is positive
+    definite when lmax bounds B's spectrum from above.  AN UNDERESTIMATED lmax
+    MAKES IT INDEFINITE and CG may then break down: estimate_lmax's value is
+    raised by a safety factor for that reason (build_operator's cheb_boost).
+    lmin is NOT an estimate of B's smallest eigenvalue: the smoother
+    convention lmax / ratio (ratio about 30) gives fewer CG iterations than
+    the exact value.
+
+    The products run through the operator's own path (_Apply: the all-gather,
+    then spmm, or spmv under cg), so the iterate Z lives in a send / full
+    buffer pair of this object's own, allocated on the first apply for a given
+    operator and width and reused; the last step reads it and writes the
+    caller's Z, together with the two dot products of a PCG iteration
+    (kernels.cheb_step_dot).  Unsplit operators only."""
+
+    def __init__(self, M, degree: int, lmin: float, lmax: float):
+        if not isinstance(degree, (int, np.integer)) or isinstance(degree, bool) or not 1 <= degree <= 16:
+            raise sa.SpmvError(sa.OTHER_ERROR, "Chebyshev", f"degree must be an integer in 1..16, not {degree!r}")
+        lmin, lmax = float(lmin), float(lmax)
+        if not (np.isfinite(lmax) and 0.0 < lmin < lmax):
+            raise sa.SpmvError(sa.OTHER_ERROR, "Chebyshev", f"bounds must satisfy 0 < lmin < lmax, not ({lmin}, {lmax})")
+        self.M, self.degree, self.lmin, self.lmax = M, int(degree), lmin, lmax
+        self.coef = chebyshev_coefficients(self.degree, lmin, lmax)
+        self._state = None  # (operator and ranks, {(width, multi): buffers}, operator)
+
+    @staticmethod
+    def check(op) -> None:
+        """Refuses a split / overlap operator, before any device work."""
+        if op.remote is not None:
+            raise sa.SpmvError(sa.OTHER_ERROR, "Chebyshev", "split / overlap operators are not supported")
+
+    def ws(self, kernels, n, k):
+        return kernels.precond_ws(self.M, n, k)
+
+    def _buffers(self, op, comm, nv, multi):
+        """(send, az, D, product) for blocks of nv columns: made on the first
+        apply of that width on this operator, then reused."""
+        owner = (id(op), id(comm.dist), comm.world)
+        if self._state is None or self._state[0] != owner:
+            self._state = (owner, {}, op)  # the operator is kept so that its id stays its own
+        made = self._state[1]
+        if (nv, multi) not in made:
+            torch = sa._torch()
+
+            def zeros(r):
+                return torch.zeros((r, nv) if multi else (r,), dtype=torch.float64, device=op.device)
+
+            send = zeros(op.pad)
+            full = zeros(op.world * op.pad) if comm.world > 1 else send
+            D = torch.zeros((max(op.rows, 1), nv), dtype=torch.float64, device=op.device)
+            made[nv, multi] = (send, zeros(max(op.rows, 1)), D, _Apply(op, comm, full, send, multi=multi))
+        return made[nv, multi]
+
+    def apply_dot(self, op, comm, R, Z, out, ws, multi: bool) -> None:
+        """Z = p(M^-1 A) M^-1 R for the (rows, nv) block R, out[:nv] = column
+        sums of R Z, out[nv:] of R R: 2 degree - 1 launches of the matrix and
+        step kernels for nv <= 8, plus the final launch of the sums."""
+        k, M, rows = op.kernels, self.M, op.rows
+        send, az, D, product = self._buffers(op, comm, int(R.shape[1]), multi)
+        if self.degree == 1:
+            a, b = self.coef[0]
+            k.cheb_step_dot(M, rows, a, b, R, None, D, None, Z, out, ws)
+            return
+        Zs, AZ = (t if multi else t.unsqueeze(1) for t in (send[:rows], az))
+        a, b = self.coef[0]
+        k.cheb_step(M, rows, a, b, R, None, D, None, Zs)
+        for a, b in self.coef[1:-1]:
+            product(az)  # gathers Zs
+            k.cheb_step(M, rows, a, b, R, AZ, D, Zs, Zs)
+        a, b = self.coef[-1]
+        product(az)
+        k.cheb_step_dot(M, rows, a, b, R, AZ, D, Zs, Z, out, ws)
+
+
+def estimate_lmax(op: DistOperator, M, comm: Comm | None = None, iters: int = 10) -> float:
+    """An estimate of the largest eigenvalue of M^-1 A (M a block-Jacobi
+    preconditioner of the operator's rows) by `iters` steps of the power
+    method from power_iteration's deterministic start vector: x <- M^-1 A x /
+    ||M^-1 A x||.  Returns the last growth factor ||M^-1 A x|| / ||x||, which
+    approaches the eigenvalue from below on the test matrices: multiply it by
+    a safety factor before it bounds a Chebyshev polynomial (Chebyshev).  Built
+    from the solver's kernels; one host read, at the end."""
+    Chebyshev.check(op)
+    if iters < 1:
+        raise sa.SpmvError(sa.OTHER_ERROR, "estimate_lmax", "iters must be >= 1")
+    with _kernel_stream(op):
+        torch = sa._torch()
+        comm = comm or Comm()
+        k, rows = op.kernels, op.rows
+        full, send = _gathered_pair(op, comm)
+        x = send[:rows]
+        gidx = np.arange(op.lo, op.lo + rows)
+        x.copy_(torch.from_numpy(1.0 + (gidx % 7) / 7.0))
+        ws = k.dot_ws(rows)
+        pws = k.precond_ws(M, rows, 1)
+        s, unused = _zeros(op, 1), _zeros(op, 2)
+        k.dot(rows, x, x, s, ws)
+        comm.allreduce(s)
+        k.scale_rsqrt(rows, s, x, x)  # ||x|| = 1 from here on
+        y, z = _zeros(op, max(rows, 1)), _zeros(op, max(rows, 1))
+        product = _Apply(op, comm, full, send)
+        for _ in range(iters):
+            product(y)  # gathers x
+            k.precond_apply_dot(M, rows, y.unsqueeze(1), z.unsqueeze(1), unused, pws)
+            k.dot(rows, z, z, s, ws)
+            comm.allreduce(s)
+            k.scale_rsqrt(rows, s, z, x)
+        return float(np.sqrt(float(s.item())))
+
+
 # ------------------------------------------------------- preconditioned CG
 def _pcg(op: DistOperator, comm: Comm, M, B, full, send, multi: bool, tol: float, maxit: int, check_every: int):
     """Preconditioned CG (x0 = 0) for the nv columns of B (rows, nv) with the
@@ -721,6 +932,8 @@ def _pcg(op: DistOperator, comm: Comm, M, B, full, send, multi: bool, tol: float
     k = op.kernels
     rows = op.rows
     nv = int(B.shape[1])
+    if isinstance(M, Chebyshev):
+        M.check(op)
 
     def zeros(*shape):
         return torch.zeros(shape, dtype=torch.float64, device=op.device)
@@ -736,12 +949,21 @@ def _pcg(op: DistOperator, comm: Comm, M, B, full, send, multi: bool, tol: float
     AP = block(ap)
     apply = _Apply(op, comm, full, send, multi=multi)
     ws = k.dot_multi_ws(rows, nv)
-    pws = k.precond_ws(M, rows, nv)
+    if isinstance(M, Chebyshev):
+        pws = M.ws(k, rows, nv)
+
+        def precond_apply_dot(R, Z, out):
+            M.apply_dot(op, comm, R, Z, out, pws, multi)
+    else:
+        pws = k.precond_ws(M, rows, nv)
+
+        def precond_apply_dot(R, Z, out):
+            k.precond_apply_dot(M, rows, R, Z, out, pws)
     pAp = zeros(nv)
     # (rz, rr) of the last and of the coming residual: two tensors of 2 nv
     # scalars, each with views of its halves (no slicing inside the loop)
     (s, rz, rr), (s_new, rz_new, rr_new) = ((t, t[:nv], t[nv:]) for t in (zeros(2 * nv), zeros(2 * nv)))
-    k.precond_apply_dot(M, rows, R, Z, s, pws)
+    precond_apply_dot(R, Z, s)
     comm.allreduce(s)
     bb = rr.cpu().numpy().copy()
 
@@ -761,7 +983,7 @@ def _pcg(op: DistOperator, comm: Comm, M, B, full, send, multi: bool, tol: float
         comm.allreduce(pAp)
         k.axpy_ratio_multi(rows, rz, pAp, 1.0, P, X)  # x_j += alpha_j p_j
         k.axpy_ratio_multi(rows, rz, pAp, -1.0, AP, R)  # r_j -= alpha_j Ap_j
-        k.precond_apply_dot(M, rows, R, Z, s_new, pws)  # z = M^-1 r, (rz', rr)
+        precond_apply_dot(R, Z, s_new)  # z = M^-1 r, (rz', rr)
         comm.allreduce(s_new)
         k.xpay_ratio_multi(rows, rz_new, rz, Z, P)  # p_j = z_j + beta_j p_j
         (s, rz, rr), (s_new, rz_new, rr_new) = (s_new, rz_new, rr_new), (s, rz, rr)

@@ -315,6 +315,11 @@ HIP_SYMBOLS = {
     "spmv_bjacobi_ws_bytes": (ctypes.c_size_t, [_c_i64, _c_i32]),
     "spmv_bjacobi_apply_dot_multi": (ctypes.c_int, [_vp, _c_i32, _vp, _c_i64, _vp, _c_i64, _vp, _vp, ctypes.c_size_t,
                                                     _vp]),
+    "spmv_bjacobi_cheb_step_multi": (ctypes.c_int, [_vp, _c_i32, ctypes.c_double, ctypes.c_double, _vp, _c_i64, _vp,
+                                                    _c_i64, _vp, _c_i64, _vp, _c_i64, _vp, _c_i64, _vp]),
+    "spmv_bjacobi_cheb_step_dot_multi": (ctypes.c_int, [_vp, _c_i32, ctypes.c_double, ctypes.c_double, _vp, _c_i64,
+                                                        _vp, _c_i64, _vp, _c_i64, _vp, _c_i64, _vp, _c_i64, _vp, _vp,
+                                                        ctypes.c_size_t, _vp]),
     "spmv_bjacobi_destroy": (ctypes.c_int, [_vp]),
     "spmv_gather": (ctypes.c_int, [_c_i64, _vp, _vp, _vp, ctypes.c_int, _vp]),
     "spmv_device_count": (ctypes.c_int, [ctypes.POINTER(ctypes.c_int)]),
@@ -364,6 +369,9 @@ HOST_SYMBOLS = {
     "spmv_cpu_csr_sym_multi": (ctypes.c_int, [_c_i64, _vp, _vp, _vp, _c_i32, _vp, _c_i64, _vp, _c_i64]),
     "spmv_bjacobi_build": (ctypes.c_int, [_c_i64, _vp, _vp, _vp, _c_i32, _c_i64, _c_i32, _vp, ctypes.POINTER(_c_i64)]),
     "spmv_cpu_bjacobi_apply_multi": (ctypes.c_int, [_c_i64, _c_i32, _vp, _c_i32, _vp, _c_i64, _vp, _c_i64]),
+    "spmv_cpu_bjacobi_cheb_step_multi": (ctypes.c_int, [_c_i64, _c_i32, _vp, _c_i32, ctypes.c_double, ctypes.c_double,
+                                                        _vp, _c_i64, _vp, _c_i64, _vp, _c_i64, _vp, _c_i64, _vp,
+                                                        _c_i64]),
     "spmv_csr_sort_rows": (ctypes.c_int, [_c_i64, _vp, _vp, _vp]),
     "spmv_csr_row_stats": (ctypes.c_int, [_c_i64, _vp, ctypes.POINTER(_c_i64), ctypes.POINTER(_c_i64), ctypes.POINTER(ctypes.c_double)]),
     "spmv_csr_pick_variant": (ctypes.c_int, [_c_i64, _vp]),
@@ -682,6 +690,45 @@ def cpu_bjacobi_apply_multi(n: int, bs: int, inv: np.ndarray, R: np.ndarray, Z: 
     ldr, ldz = (a.strides[0] // 8 if a.shape[0] > 1 else k for a in (R, Z))  # one row: its stride is never used
     _check_host(host_lib().spmv_cpu_bjacobi_apply_multi(n, bs, _ptr(inv), k, _ptr(R), ldr, _ptr(Z), ldz),
                 "spmv_cpu_bjacobi_apply_multi")
+
+
+def cpu_bjacobi_cheb_step_multi(n: int, bs: int, inv: np.ndarray, a: float, b: float, R: np.ndarray, AZ, D: np.ndarray,
+                                Zin, Zout: np.ndarray, k: int | None = None) -> None:
+    """One host step of the Chebyshev recurrence over M^-1
+    (spmv_cpu_bjacobi_cheb_step_multi) with inv from bjacobi_build_host.
+    AZ = None is step 0 (Zin may then be None as well); every array given
+    (>= n rows) is a 2-D float64 array with unit inner stride; k defaults to
+    R's width.  Zout may be Zin itself.  Only D[:n, :k] and Zout[:n, :k] are
+    written."""
+    what = "cpu_bjacobi_cheb_step_multi"
+    if AZ is None:
+        Zin = None
+    elif Zin is None:
+        raise SpmvError(OTHER_ERROR, what, "a general step (AZ given) needs Zin")
+    given = [t for t in (R, AZ, D, Zin, Zout) if t is not None]
+    for t in given:
+        if not isinstance(t, np.ndarray) or t.dtype != np.float64 or t.ndim != 2:
+            raise SpmvError(OTHER_ERROR, what, "R, AZ, D, Zin and Zout must be 2-D float64 arrays")
+        if t.shape[1] > 1 and t.strides[1] != 8 or t.strides[0] % 8:
+            raise SpmvError(OTHER_ERROR, what, "the arrays need unit inner stride")
+        if t.shape[0] < n:
+            raise SpmvError(OTHER_ERROR, what, "an array has too few rows")
+    k = R.shape[1] if k is None else int(k)
+    if any(k > t.shape[1] for t in given):
+        raise SpmvError(OTHER_ERROR, what, "an array has fewer than k columns")
+    inv = np.ascontiguousarray(inv, np.float64)
+    if 1 <= bs <= 16 and inv.size < (max(n, 0) + bs - 1) // bs * bs * bs:
+        raise SpmvError(OTHER_ERROR, what, "inv is too short")
+
+    def ld(t):  # one row: its stride is never used
+        return 0 if t is None else t.strides[0] // 8 if t.shape[0] > 1 else k
+
+    def p(t):
+        return None if t is None else _ptr(t)
+
+    _check_host(host_lib().spmv_cpu_bjacobi_cheb_step_multi(n, bs, _ptr(inv), k, float(a), float(b), p(R), ld(R), p(AZ),
+                                                            ld(AZ), p(D), ld(D), p(Zin), ld(Zin), p(Zout), ld(Zout)),
+                "spmv_cpu_bjacobi_cheb_step_multi")
 
 
 def csr_sort_rows(n_rows: int, ptr, col, val) -> None:
@@ -1522,6 +1569,43 @@ class BlockJacobi:
     def ws(self, n: int, k: int):
         torch = _torch()
         return torch.empty(hip_lib().spmv_bjacobi_ws_bytes(n, k), dtype=torch.uint8, device=self.device)
+
+    def _cheb_args(self, what, a, b, R, AZ, D, Zin, Zout):
+        """The checks of _blocks on every block of a Chebyshev step (AZ =
+        None: step 0, Zin is then ignored); returns the C arguments from k to
+        ldzout."""
+        if AZ is None:
+            Zin = None
+        elif Zin is None:
+            raise SpmvError(OTHER_ERROR, what, "a general step (AZ given) needs Zin")
+        k, ldr, ldd = self._blocks(what, R, D)
+        lds = {}
+        for name, t in (("AZ", AZ), ("Zin", Zin), ("Zout", Zout)):
+            lds[name] = 0 if t is None else self._blocks(what, R, t)[2]
+        return (k, float(a), float(b), _ptr(R), ldr, _ptr(AZ), lds["AZ"], _ptr(D), ldd, _ptr(Zin), lds["Zin"],
+                _ptr(Zout), lds["Zout"])
+
+    def cheb_step(self, a, b, R, AZ, D, Zin, Zout, stream=None) -> None:
+        """One step of the Chebyshev recurrence over M^-1
+        (spmv_bjacobi_cheb_step_multi) on `stream`: AZ = None is step 0,
+        D = Zout = b M^-1 R; otherwise D = a D + b M^-1 (R - AZ) and
+        Zout = Zin + D.  Zout may be Zin itself."""
+        args = self._cheb_args("BlockJacobi.cheb_step", a, b, R, AZ, D, Zin, Zout)
+        _check(hip_lib().spmv_bjacobi_cheb_step_multi(self.handle, *args, self._stream(stream)),
+               "spmv_bjacobi_cheb_step_multi")
+
+    def cheb_step_dot(self, a, b, R, AZ, D, Zin, Zout, out, ws, stream=None) -> None:
+        """cheb_step, and out[:k] = column sums of R Zout, out[k:2k] of R R; ws
+        from ws(n, k)."""
+        torch = _torch()
+        args = self._cheb_args("BlockJacobi.cheb_step_dot", a, b, R, AZ, D, Zin, Zout)
+        k = args[0]
+        if not isinstance(out, torch.Tensor) or out.dtype != torch.float64 or not out.is_contiguous() or \
+                out.numel() < 2 * k or out.device != R.device or ws.device != R.device:
+            raise SpmvError(OTHER_ERROR, "BlockJacobi.cheb_step_dot", "out must hold 2k float64 scalars on the device")
+        _check(hip_lib().spmv_bjacobi_cheb_step_dot_multi(self.handle, *args, _ptr(out), _ptr(ws),
+                                                          ws.numel() * ws.element_size(), self._stream(stream)),
+               "spmv_bjacobi_cheb_step_dot_multi")
 
 
 def set_option(name: str, value: int | None) -> None:

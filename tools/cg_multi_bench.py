@@ -41,6 +41,21 @@ reasoning) it builds ONE operator with build_operator(bjacobi=BS) and reports
 --trace N (with --bjacobi) runs nothing but 200 calls each of
 dot_multi(R, R) and of the fused apply_dot on N rows for k in {1, 2, 4, 8}: the
 workload of a kernel-trace run that compares the two kernels.
+
+--chebyshev DEG (with --bjacobi BS) measures the Chebyshev polynomial
+preconditioner of degree DEG over block Jacobi against block-Jacobi PCG (one
+JSON line).  On the same three matrices it builds ONE operator with
+build_operator(bjacobi=BS, chebyshev=DEG) (bounds: 1.1 x the power method's
+estimate and that over 30, reported; --cheb-lmax X: X and X / 30 as given) and, for k in {1, 2, 4, 8} right-hand
+sides, compares cg_multi(precond=op.precond.M), which is block-Jacobi PCG,
+same launches and bits as an operator built with bjacobi alone, with cg_multi
+under the polynomial:
+    per outer iteration: tol = 0, the windows as above;
+    to --tol: the iterations each needs (at most --maxit) and the wall time
+        of the solve, warm, median of three.
+--trace N with --chebyshev runs nothing but 200 calls each of the general step
+(Zout == Zin) and of its dot form on N rows for k in {1, 2, 4, 8}: the workload
+of a kernel-trace run against the byte model of (48 k + 8 BS) bytes per row.
 """
 from __future__ import annotations
 
@@ -162,12 +177,20 @@ def main():
     ap.add_argument("--tol", type=float, default=1e-10, help="--bjacobi: tolerance of the solves that count iterations")
     ap.add_argument("--maxit", type=int, default=20000)
     ap.add_argument("--trace", type=int, default=0, help="--bjacobi: rows of the kernel-trace workload (nothing else runs)")
+    ap.add_argument("--chebyshev", type=int, default=0,
+                    help="--bjacobi: degree of the Chebyshev polynomial measured against block-Jacobi PCG")
+    ap.add_argument("--cheb-lmax", type=float, default=0.0,
+                    help="--chebyshev: take this upper bound (and it over 30) instead of the power method's estimate")
     a = ap.parse_args()
     import torch
 
     if not torch.cuda.is_available():
         sys.exit("cg_multi_bench: no GPU")
     dev = torch.device("cuda:0")
+    if a.chebyshev and not a.bjacobi:
+        sys.exit("cg_multi_bench: --chebyshev needs --bjacobi BS")
+    if a.chebyshev:
+        return chebyshev_main(a, torch, dev)
     if a.bjacobi:
         return precond_main(a, torch, dev)
     out = {"tool": "cg_multi_bench", "device": sa.device_name(0), "window_s": a.window, "windows": WINDOWS,
@@ -279,6 +302,78 @@ def precond_main(a, torch, dev):
                              "solve_ms": round(t0.elapsed_time(t1), 3)}
         res["to_tol"] = to_tol
         del op
+    print(json.dumps(out))
+
+
+def chebyshev_main(a, torch, dev):
+    bs, deg = a.bjacobi, a.chebyshev
+    rng = np.random.default_rng(7)
+    ks = (1,) + KS
+    if a.trace:
+        n = a.trace
+        M = sa.BlockJacobi.from_coo(block_diagonal(n, bs), bs, dev)
+        for k in ks:
+            R, AZ, D, Z = (torch.from_numpy(rng.uniform(-1, 1, (n, k))).to(dev) for _ in range(4))
+            out = torch.zeros(2 * k, dtype=torch.float64, device=dev)
+            ws = M.ws(n, k)
+            for _ in range(200):
+                M.cheb_step(0.25, 1e-3, R, AZ, D, Z, Z)
+            for _ in range(200):
+                M.cheb_step_dot(0.25, 1e-3, R, AZ, D, Z, Z, out, ws)
+        torch.cuda.synchronize()
+        print(json.dumps({"tool": "cg_multi_bench", "trace_rows": n, "bjacobi": bs, "chebyshev": deg, "calls": 200}))
+        return
+    out = {"tool": "cg_multi_bench", "device": sa.device_name(0), "bjacobi": bs, "chebyshev": deg,
+           "window_s": a.window, "windows": WINDOWS, "iters": a.iters, "check_every": a.check_every, "tol": a.tol,
+           "maxit": a.maxit, "unit": "ms per outer iteration, all k columns", "results": {}}
+    cases = []
+    for name in a.matrices.split(",") + ["congruence"]:
+        if name == "laplacian":
+            cases.append((name, laplacian_2d(a.grid)))
+        elif name == "cantlike_sym":
+            cases.append((name, cantlike_sym()))
+        elif name == "congruence":
+            cases.append((name, block_congruence(a.congruence_grid, bs)))
+        else:
+            sys.exit(f"cg_multi_bench: unknown matrix {name}")
+    for name, m in cases:
+        bounds = (a.cheb_lmax / 30.0, a.cheb_lmax) if a.cheb_lmax > 0.0 else None
+        op = it.build_operator(m, 0, 1, "csr", dev, bjacobi=bs, chebyshev=deg, cheb_bounds=bounds)
+        cheb = op.precond
+        n = m.n_rows
+        res = out["results"].setdefault(name, {"rows": n, "stored_entries": m.nnz, "lmin": cheb.lmin,
+                                               "lmax": cheb.lmax, "bounds_given": bounds is not None})
+        kw = dict(tol=0.0, maxit=a.iters, check_every=a.check_every)
+        for k in ks:
+            B = torch.from_numpy(rng.uniform(-1, 1, (n, k))).to(dev)
+            fa = lambda: it.cg_multi(op, B, precond=cheb.M, **kw)  # noqa: E731  the yardstick: block-Jacobi PCG
+            fb = lambda: it.cg_multi(op, B, **kw)  # noqa: E731
+            assert fa()[1] == a.iters and fb()[1] == a.iters
+            torch.cuda.synchronize()
+            na, nb = calls_for(torch, fa, a.window), calls_for(torch, fb, a.window)
+            wa, wb = [], []
+            for _ in range(WINDOWS):
+                wa.append(window_ms(torch, fa, na) / (na * a.iters))
+                wb.append(window_ms(torch, fb, nb) / (nb * a.iters))
+            ma, mb = statistics.median(wa), statistics.median(wb)
+            r = {"bj_ms": round(ma, 5), "bj_spread_ms": round(max(wa) - min(wa), 5), "cheb_ms": round(mb, 5),
+                 "cheb_spread_ms": round(max(wb) - min(wb), 5), "solves": [na, nb], "cheb_over_bj": round(mb / ma, 3)}
+            for label, pre in (("bj", cheb.M), ("cheb", None)):
+                times = []
+                for _ in range(3):
+                    torch.cuda.synchronize()
+                    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    t0.record()
+                    _, its, rel = it.cg_multi(op, B, tol=a.tol, maxit=a.maxit, check_every=a.check_every, precond=pre)
+                    t1.record()
+                    t1.synchronize()
+                    times.append(t0.elapsed_time(t1))
+                r[label + "_to_tol"] = {"iterations": its, "reached": bool((rel <= a.tol).all()),
+                                        "rel_max": float(rel.max()), "solve_ms": round(statistics.median(times), 3),
+                                        "solve_spread_ms": round(max(times) - min(times), 3)}
+            r["time_to_tol_cheb_over_bj"] = round(r["cheb_to_tol"]["solve_ms"] / r["bj_to_tol"]["solve_ms"], 3)
+            res[str(k)] = r
+        del op, cheb
     print(json.dumps(out))
 
 
