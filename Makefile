@@ -21,6 +21,12 @@ ROCM     ?= /opt/rocm
 
 CFLAGS   := -O3 -std=c11 -Wall -Wextra -Werror -Wshadow -fPIC -fopenmp -Iinclude
 HIPFLAGS := -O3 -std=c++17 -Wall -Wextra -fPIC --offload-arch=$(ARCH) -Iinclude
+# kernarg preload: the leading 14 dwords of a kernel's arguments arrive in
+# SGPRs at wave launch instead of by a first s_load round trip (each code
+# object keeps the loads as a header for firmware that does not preload);
+# csr_xwin_kernel's parameter order is chosen for it (csrc/csr.hip).  For the
+# library's kernels (csrc/) only: the probes stay as they were measured.
+KERNARG_PRELOAD := -mllvm -amdgpu-kernarg-preload-count=16
 ifeq ($(DEBUG), yes)
 CFLAGS   += -g
 HIPFLAGS += -g
@@ -47,7 +53,7 @@ HIP_OBJ  := $(patsubst $(PKG)/csrc/%.hip,build/hip/%.o,$(HIP_SRC))
 
 build/hip/%.o: $(PKG)/csrc/%.hip $(HIP_HDR)
 	@mkdir -p build/hip
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+	$(HIPCC) $(HIPFLAGS) $(KERNARG_PRELOAD) -c $< -o $@
 
 # the plans (csrc/plan.hip) call the host rules of libspmv_host.so
 # (variant rules, SELL split plan, tiled-CSR big-tile plan): linked by soname

@@ -180,15 +180,22 @@ int launch_slot_multi(const spmv_dims &d, bool sell, int32_t ki, int32_t C, int6
 // CONTIGUOUS range of logical blocks.  Neighbouring rows/slices then read
 // neighbouring x entries through one XCD's L2.  Placement only changes
 // speed, never results.
-__device__ __forceinline__ int64_t xcd_block(int remap)
+// xcd_block_of(nb): the remap for a grid of nb blocks, 0 = no remap.  For a
+// kernel that gets its grid size as an argument: gridDim.x is a hidden kernel
+// argument, a load of its own in front of everything that needs the block.
+__device__ __forceinline__ int64_t xcd_block_of(uint32_t n_blocks)
 {
     const int64_t b = blockIdx.x;
-    if (!remap)
+    if (!n_blocks)
         return b;
-    const int64_t nb = gridDim.x;
+    const int64_t nb = n_blocks;
     const int64_t q = nb >> 3, r = nb & 7;
     const int64_t xcd = b & 7, idx = b >> 3;
     return xcd < r ? xcd * (q + 1) + idx : r * (q + 1) + (xcd - r) * q + idx;
+}
+__device__ __forceinline__ int64_t xcd_block(int remap)
+{
+    return remap ? xcd_block_of(gridDim.x) : (int64_t)blockIdx.x;
 }
 
 // Streamed-once loads of the matrix arrays.  NT = true issues them

@@ -502,6 +502,15 @@ __global__ __launch_bounds__(kBlock) void csr_col16_kernel(int64_t n_rows, int64
         off[nnz + threadIdx.x] = 0;
 }
 
+// base[byte_off / sizeof(T)] for a wave-uniform base and a per-lane 32-bit
+// byte offset: the compiler keeps the base in SGPRs and emits the load's
+// scalar-base form (global_load … v_off, s[base]), no 64-bit VALU address.
+template <typename T>
+__device__ __forceinline__ T load_at(const T *base, uint32_t byte_off)
+{
+    return *reinterpret_cast<const T *>(reinterpret_cast<const char *>(base) + byte_off);
+}
+
 // The staged kernel with x windows in LDS.  A window covers gpw consecutive
 // row groups (rows_per_window = gpw * 256/L rows), one workgroup per window:
 // the workgroup copies x[win.x .. win.y] into LDS (dynamic, xcap entries)
@@ -524,12 +533,30 @@ __global__ __launch_bounds__(kBlock) void csr_col16_kernel(int64_t n_rows, int64
 // the later MODE 4, MODE 3 with the window's first chunk issued in the
 // prologue behind the x-range and offset loads: 15.6 against 14.8 us cold on
 // one cant-like matrix, 90 against 72 VGPRs, profiles/round6/csr_prefetch_ab.md.)
+// The MODE 3 prologue, cold, is a chain of memory round trips in front of
+// the first chunk's loads; what it waits for, in order:
+//   1. nothing for the arguments it needs: the library is built with kernarg
+//      preload (Makefile KERNARG_PRELOAD), which delivers the first 14 dwords
+//      of the arguments in SGPRs at wave launch.  Hence the parameter ORDER:
+//      win, row_ptr, n_rows, gpw, n_groups, x, xcap and remap_windows are
+//      those 14 dwords; val, y and the by-value column source follow (a
+//      by-value struct ends the preloaded run, so it stands last) and are
+//      fetched by one s_load beside step 2's.  remap_windows is the grid
+//      size itself (0: no remap): gridDim is a hidden argument behind all of
+//      these, one more load in front of win[wi].  (Firmware that does not
+//      preload runs the s_loads the compiler keeps in front of the entry.)
+//   2. win[wi] and row_ptr[n_rows], two scalar loads; the first U·256 row
+//      offsets are requested before the wait for them (their addresses need
+//      only arguments), the x window right after it;
+//   3. the offsets and the window (2 + 8 loads per thread, each a scalar
+//      base plus a 32-bit lane offset), all requested before the first LDS
+//      store, then ONE barrier.
+// profiles/round8/ab_csr_prologue.md has the ISA checks and the figures.
 template <int L, int R, bool NT, typename V, int MODE, typename Cols>
 __global__ __launch_bounds__(kBlock) void csr_xwin_kernel(
-    int64_t n_rows, int64_t n_groups, int64_t gpw, const int64_t *__restrict__ row_ptr,
-    const Cols cols, const V *__restrict__ val,
-    const double *__restrict__ x, double *__restrict__ y, const int2 *__restrict__ win, int32_t xcap,
-    int remap)
+    const int2 *__restrict__ win, const int64_t *__restrict__ row_ptr, int64_t n_rows, int64_t gpw,
+    int64_t n_groups, const double *__restrict__ x, int32_t xcap, uint32_t remap_windows,
+    const V *__restrict__ val, double *__restrict__ y, const Cols cols)
 {
     static_assert(MODE == 0 || MODE == 3, "csr_xwin_kernel: MODE 0 or 3");
     CSR_STAMP(0);
@@ -541,42 +568,64 @@ __global__ __launch_bounds__(kBlock) void csr_xwin_kernel(
     const int64_t nz = row_ptr[n_rows];
     // remap: consecutive windows on one XCD, so the overlapping x ranges of
     // neighbouring windows are copied from that XCD's L2
-    const int64_t wi = xcd_block(remap);
+    const int64_t wi = xcd_block_of(remap_windows);
     const int64_t g_beg = wi * gpw;
     const int64_t g_end = (wi + 1) * gpw < n_groups ? (wi + 1) * gpw : n_groups;
     const int2 wnd = win[wi];
-    const int32_t span = wnd.y - wnd.x + 1;
-    const bool staged = span > 0 && span <= xcap;  // uniform per workgroup
     if constexpr (MODE == 3) {
+        // win[wi] is requested above this line and first used below the next
+        // such line, behind the offsets' loads: left alone, the scheduler
+        // either waits for it in front of them or requests it behind them
+        __builtin_amdgcn_sched_barrier(0);
         // offsets r0 .. r0 + nr of the window's rows (clamped past n_rows),
         // then the x range: every load issued before the stores
         const int64_t r0 = g_beg * RPB;
         const int32_t nr = (int32_t)((g_end - g_beg) * RPB) + 1;
         constexpr int U = 2;  // offsets per thread per pass (nr <= U·256 in one pass)
         constexpr int XU = 8;  // window entries per thread (copy_window's default)
-        if (nr <= U * kBlock && span <= XU * kBlock) {
-            // one pass, branch-free: the offsets' and the window's loads all
-            // go out before the first store (with the loop below the compiler
-            // waited for the offsets before requesting the window)
-            int64_t o[U];
-            double xv[XU];
+        // First pass, branch-free: the first U·256 offsets' and the window's
+        // loads all go out before the first store (inside a loop over the
+        // passes the compiler waited for the offsets before requesting the
+        // window).  Addresses: a wave-uniform 64-bit base (SGPRs) plus a
+        // 32-bit byte offset per lane, one or two VALU instructions per
+        // load.  The offsets' addresses need the kernel arguments alone (row
+        // min(r0 + i, n_rows), i <= 511), so they stand in front of the
+        // first use of win[wi]; the window's need wnd on top (entry
+        // min(i, xl), xl <= 2,047 in a window the branch-free copy holds).
+        int64_t o[U];
+        const int64_t *rbase = row_ptr + (r0 < n_rows ? r0 : n_rows);
+        const int64_t rleft = n_rows - r0;  // rows from r0 to the clamp
+        const uint32_t rl8 = rleft >= U * kBlock ? U * kBlock * 8u : rleft > 0 ? (uint32_t)rleft * 8u : 0u;
+        const uint32_t t8 = threadIdx.x * 8u;
 #pragma unroll
-            for (int k = 0; k < U; ++k) {
-                const int64_t r = r0 + threadIdx.x + k * kBlock;
-                o[k] = row_ptr[r < n_rows ? r : n_rows];
-            }
-            const int32_t xl = span > 0 ? span - 1 : 0;  // clamped (loaded, never stored past span)
-#pragma unroll
-            for (int k = 0; k < XU; ++k) {
-                const int32_t i = (int32_t)threadIdx.x + k * kBlock;
-                xv[k] = x[wnd.x + (i < xl ? i : xl)];
-            }
+        for (int k = 0; k < U; ++k) {
+            const uint32_t i8 = t8 + k * kBlock * 8u;
+            o[k] = load_at(rbase, i8 < rl8 ? i8 : rl8);
+        }
+        __builtin_amdgcn_sched_barrier(0);  // win[wi] is first used below
+        const int32_t span = wnd.y - wnd.x + 1;
+        const bool staged = span > 0 && span <= xcap;  // uniform per workgroup
+        auto store_offsets = [&] {
 #pragma unroll
             for (int k = 0; k < U; ++k) {
                 const int32_t i = (int32_t)threadIdx.x + k * kBlock;
                 if (i < nr)
                     s_off[i] = o[k];
             }
+        };
+        // (the two cases share no registers past this branch: where the
+        // window's values lived across its end, the compiler waited for the
+        // offsets before it requested the window)
+        if (span <= XU * kBlock) {  // uniform: the branch-free copy holds the window
+            double xv[XU];
+            const uint32_t xl8 = span > 0 ? (uint32_t)(span - 1) * 8u : 0u;  // clamped (loaded, never stored past span)
+            const double *xbase = x + wnd.x;
+#pragma unroll
+            for (int k = 0; k < XU; ++k) {
+                const uint32_t i8 = t8 + k * kBlock * 8u;
+                xv[k] = load_at(xbase, i8 < xl8 ? i8 : xl8);
+            }
+            store_offsets();
             if (staged) {
 #pragma unroll
                 for (int k = 0; k < XU; ++k) {
@@ -585,23 +634,28 @@ __global__ __launch_bounds__(kBlock) void csr_xwin_kernel(
                         s_x[i] = xv[k];
                 }
             }
-        } else {  // a window too big for one pass
-        for (int32_t b = 0; b < nr; b += U * kBlock) {
-            int64_t o[U];
+        } else {
+            if (staged)
+                copy_window(s_x, x, wnd.x, span);
+            store_offsets();
+            // vmcnt(0): nothing of this case is in flight where the cases
+            // join, or the compiler guards the other case's registers by
+            // waiting for the offsets before it requests the window
+            __builtin_amdgcn_s_waitcnt(0x0f70);
+        }
+        // the further passes of a window of more than U·256 - 1 rows
+        for (int32_t b = U * kBlock; b < nr; b += U * kBlock) {
 #pragma unroll
             for (int k = 0; k < U; ++k) {
                 const int64_t r = r0 + b + threadIdx.x + k * kBlock;
                 o[k] = row_ptr[r < n_rows ? r : n_rows];
             }
-            if (staged && b == 0)
-                copy_window(s_x, x, wnd.x, span);
 #pragma unroll
             for (int k = 0; k < U; ++k) {
                 const int32_t i = b + (int32_t)threadIdx.x + k * kBlock;
                 if (i < nr)
                     s_off[i] = o[k];
             }
-        }
         }
         __syncthreads();  // window and offsets visible
         CSR_STAMP(1);
@@ -620,6 +674,8 @@ __global__ __launch_bounds__(kBlock) void csr_xwin_kernel(
                                                                XGlobal{x}, y, n_rows, nz);
         return;
     }
+    const int32_t span = wnd.y - wnd.x + 1;
+    const bool staged = span > 0 && span <= xcap;  // uniform per workgroup
     if (staged)
         for (int32_t i = threadIdx.x; i < span; i += kBlock)
             s_x[i] = x[wnd.x + i];
@@ -899,11 +955,13 @@ static void launch_csr_xwin(const spmv_dims &d, const int64_t *row_ptr, const Co
     if (mode == 3 && csr_xwin_lds(mode, xcap, gpw, RPB) + sizeof(double2) * kBlock * R * 2 > 64 * 1024)
         mode = 0;
     const size_t lds = csr_xwin_lds(mode, xcap, gpw, RPB);
-    const int remap = csr_xwin_remap_rule(xcap, gpw * RPB, n_win) ? 1 : 0;
+    // the kernel's remap argument is the grid size itself (0: round robin)
+    const uint32_t remap_windows = csr_xwin_remap_rule(xcap, gpw * RPB, n_win) ? (uint32_t)n_win : 0u;
     const hipStream_t st = (hipStream_t)d.stream;
     with_int<3, 0>(mode, [&](auto M) {
         hipLaunchKernelGGL((csr_xwin_kernel<L, R, NT, V, decltype(M)::value, Cols>), dim3((unsigned)n_win),
-                           dim3(kBlock), lds, st, d.n_rows, groups, gpw, row_ptr, cols, val, x, y, win, xcap, remap);
+                           dim3(kBlock), lds, st, win, row_ptr, d.n_rows, gpw, groups, x, xcap, remap_windows, val, y,
+                           cols);
     });
 }
 

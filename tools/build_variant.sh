@@ -8,6 +8,8 @@ set -eu
 cd "$(dirname "$0")/.."
 name=$1; shift
 defs=${*:-}
+# the product's kernarg preload flag (Makefile KERNARG_PRELOAD); PRELOAD= builds without it
+preload=${PRELOAD--mllvm -amdgpu-kernarg-preload-count=16}
 d=build/var_$name
 mkdir -p "$d" lab
 pids=()
@@ -18,7 +20,7 @@ for f in opencl-spmv-algorithms_amd/csrc/*.hip; do
   if [ "$name" = stamps_csr ] && [ "$base" = csr ]; then inc=(-include tools/lab_stamps_csr.h); fi
   if [ "$name" = stamps_coo ] && [ "$base" = staged ]; then inc=(-include tools/lab_stamps_coo.h); fi
   # shellcheck disable=SC2086
-  /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -Iinclude "${inc[@]}" $defs -c "$f" -o "$d/$base.o" &
+  /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -Iinclude $preload "${inc[@]}" $defs -c "$f" -o "$d/$base.o" &
   pids+=($!)
 done
 for p in "${pids[@]}"; do wait "$p"; done
