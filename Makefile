@@ -41,7 +41,7 @@ LIB_HIP  := $(LIBDIR)/libspmv_hip.so
 LIB_HOST := $(LIBDIR)/libspmv_host.so
 ORACLE   := oracle/liboracle.so
 
-.PHONY: all default lib oracle probes lab test-san test-san-transpose test-san-transpose-multi test-san-multi-plan test-san-symmetric test-san-symmetric-multi test-san-precond test-san-cheb test-cpu test-gpu clean $(TARGETS)
+.PHONY: all default lib oracle probes lab test-san test-san-transpose test-san-transpose-multi test-san-multi-plan test-san-symmetric test-san-symmetric-multi test-san-precond test-san-cheb test-san-bicgstab test-cpu test-gpu clean $(TARGETS)
 
 default: all
 all: lib $(TARGETS) probes
@@ -211,6 +211,18 @@ build/san/cheb_harness: tests/san/cheb_harness.c $(HOST_SRC) include/spmv_host.h
 
 test-san-cheb: build/san/cheb_harness
 	$(SANENV) ASAN_OPTIONS=detect_leaks=1:exitcode=99 build/san/cheb_harness
+
+# the host statements of BiCGSTAB's two fused vector updates
+# (spmv_cpu_bicgstab_update_multi, spmv_cpu_bicgstab_dir_multi) under ASan +
+# UBSan: a stand-alone program with exactly-sized buffers, ld == k and ld > k,
+# Sh == R, zero denominators, n = 0 and the refused inputs
+# (tests/san/bicgstab_harness.c)
+build/san/bicgstab_harness: tests/san/bicgstab_harness.c $(HOST_SRC) include/spmv_host.h include/spmv_rc.h
+	@mkdir -p build/san
+	$(CC) -std=c11 -Wall -Wextra -Werror -fopenmp -Iinclude $(SANFLAGS) $< $(HOST_SRC) -o $@ -lm
+
+test-san-bicgstab: build/san/bicgstab_harness
+	$(SANENV) ASAN_OPTIONS=detect_leaks=1:exitcode=99 build/san/bicgstab_harness
 
 test-gpu: all oracle
 	python -m pytest tests/ -x -q -m gpu

@@ -430,6 +430,56 @@ int spmv_axpy_ratio_multi(int64_t n, int32_t k, const double *num, const double 
                           const double *X, int64_t ldx, double *Y, int64_t ldy, int device, void *stream);
 int spmv_xpay_ratio_multi(int64_t n, int32_t k, const double *num, const double *den, const double *X,
                           int64_t ldx, double *Y, int64_t ldy, int device, void *stream);
+/* The fused block vector kernels of BiCGSTAB (iterate.bicgstab,
+ * iterate.bicgstab_multi), by the conventions of the block vector kernels
+ * above: row-major blocks V[i*ld + j], j < k <= ld, 8-byte alignment only;
+ * nothing outside [i*ld, i*ld + k), i < n, is read or written; asynchronous on
+ * `stream`, no allocation, no synchronisation (capturable); at most two
+ * launches, plus the final one of a dot form.  ratio(a, b) below is a / b, and
+ * 0.0 WHEN b == 0.0 (the rule of spmv_axpy_ratio_multi): a breakdown of the
+ * recurrence makes a column stand still, never NaN.  Every scalar argument is
+ * a device array of k doubles.  SPMV_OTHER_ERROR, before anything is written,
+ * for n < 0, k < 1, a leading dimension below k, a NULL argument that would be
+ * read or written or a workspace that is too small.
+ *
+ * spmv_dot2_multi: out[j] = sum_i A[i][j] B[i][j] and out[k + j] = sum_i
+ * A[i][j] C[i][j] in one pass over A, through spmv_dot_multi's fixed tree: the
+ * 2k results are bit for bit what spmv_dot_multi(A, B) and spmv_dot_multi(A, C)
+ * give.  C may be A itself (it is then not read a second time).  ws holds
+ * spmv_dot_multi_ws_bytes(n, 2k) bytes; n == 0 writes 2k zeros.
+ *
+ * spmv_bicgstab_update_dot_multi: with alpha_j = ratio(a_num[j], a_den[j]) and
+ * omega_j = ratio(w_num[j], w_den[j]),
+ *   X[i][j] = fma(omega_j, Sh[i][j], fma(alpha_j, Ph[i][j], X[i][j]))
+ *   R[i][j] = fma(-omega_j, T[i][j], R[i][j])
+ * the device form of spmv_cpu_bicgstab_update_multi (spmv_host.h), which fixes
+ * every bit of X and R whatever k, the leading dimensions, the alignment or
+ * the load width; and in the same pass out[j] = sum_i R0[i][j] R[i][j] and
+ * out[k + j] = sum_i R[i][j]^2 over the NEW R, bit for bit what
+ * spmv_dot_multi(R0, R) and spmv_dot_multi(R, R) give afterwards.  Sh may be R
+ * itself, with the same leading dimension (the unpreconditioned iteration: the
+ * old R is what multiplies omega_j); two leading dimensions are refused.  Every
+ * other overlap between Ph, Sh, T, R0, X, R, out and ws is the caller's error.
+ * ws holds spmv_dot_multi_ws_bytes(n, 2k) bytes; n == 0 writes 2k zeros.
+ *
+ * spmv_bicgstab_dir_multi: with beta_j = ratio(rho_new[j], rv[j]) *
+ * ratio(tt[j], ts[j]) and omega_j = ratio(ts[j], tt[j]),
+ *   P[i][j] = fma(beta_j, fma(-omega_j, V[i][j], P[i][j]), R[i][j])
+ * the device form of spmv_cpu_bicgstab_dir_multi.  V, R and P must not
+ * overlap.  n == 0 writes nothing.                                         */
+int spmv_dot2_multi(int64_t n, int32_t k, const double *A, int64_t lda, const double *B, int64_t ldb,
+                    const double *C, int64_t ldc, double *out, void *ws, size_t ws_bytes, int device,
+                    void *stream);
+int spmv_bicgstab_update_dot_multi(int64_t n, int32_t k, const double *a_num, const double *a_den,
+                                   const double *w_num, const double *w_den, const double *Ph,
+                                   int64_t ldph, const double *Sh, int64_t ldsh, const double *T,
+                                   int64_t ldt, const double *R0, int64_t ldr0, double *X, int64_t ldx,
+                                   double *R, int64_t ldr, double *out, void *ws, size_t ws_bytes,
+                                   int device, void *stream);
+int spmv_bicgstab_dir_multi(int64_t n, int32_t k, const double *rho_new, const double *rv,
+                            const double *tt, const double *ts, const double *V, int64_t ldv,
+                            const double *R, int64_t ldr, double *P, int64_t ldp, int device,
+                            void *stream);
 /* Block-Jacobi preconditioner M = blockdiag(D_0, D_1, ...), bs x bs blocks of
  * the diagonal, 1 <= bs <= 16, for the CG solvers of iterate.py (cg, cg_multi).
  * spmv_bjacobi_build (spmv_host.h) defines the blocks (col_base,

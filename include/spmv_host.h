@@ -409,6 +409,31 @@ int spmv_cpu_bjacobi_cheb_step_multi(int64_t n, int32_t bs, const double *inv, i
                                      double b, const double *R, int64_t ldr, const double *AZ,
                                      int64_t ldaz, double *D, int64_t ldd, const double *Zin,
                                      int64_t ldzin, double *Zout, int64_t ldzout);
+/* The two vector statements of a BiCGSTAB iteration (iterate.bicgstab_multi) on
+ * row-major blocks of k >= 1 vectors (V[i*ld + j], i < n, j < k <= ld), with
+ * HOST arrays of k scalars.  ratio(a, b) is a / b, and 0.0 when b == 0.0.
+ * update: alpha_j = ratio(a_num[j], a_den[j]), omega_j = ratio(w_num[j], w_den[j]),
+ *   X[i][j] = fma(omega_j, Sh[i][j], fma(alpha_j, Ph[i][j], X[i][j]))
+ *   R[i][j] = fma(-omega_j, T[i][j], R[i][j])
+ *   Sh may be R itself (same leading dimension): an element of Sh is read
+ *   before that element of R is written.  No other overlap is allowed.
+ * dir: beta_j = ratio(rho_new[j], rv[j]) * ratio(tt[j], ts[j]),
+ *      omega_j = ratio(ts[j], tt[j]),
+ *   P[i][j] = fma(beta_j, fma(-omega_j, V[i][j], P[i][j]), R[i][j])
+ * These fix the bits of every element: the CPU statements of
+ * spmv_bicgstab_update_dot_multi and spmv_bicgstab_dir_multi (spmv_ext.h; the
+ * sums of the former are fixed by spmv_dot_multi).  Nothing is read or written
+ * outside columns [0, k) of a row or at or past row n.  SPMV_OTHER_ERROR,
+ * before anything is written, for a negative n, k < 1, a leading dimension
+ * below k, a NULL array that would be read or written, or Sh == R with two
+ * leading dimensions.                                                       */
+int spmv_cpu_bicgstab_update_multi(int64_t n, int32_t k, const double *a_num, const double *a_den,
+                                   const double *w_num, const double *w_den, const double *Ph,
+                                   int64_t ldph, const double *Sh, int64_t ldsh, const double *T,
+                                   int64_t ldt, double *X, int64_t ldx, double *R, int64_t ldr);
+int spmv_cpu_bicgstab_dir_multi(int64_t n, int32_t k, const double *rho_new, const double *rv,
+                                const double *tt, const double *ts, const double *V, int64_t ldv,
+                                const double *R, int64_t ldr, double *P, int64_t ldp);
 /* Y = A^T X for k >= 1 vectors stored row-major, the layout of
  * spmv_plan_run_t_multi (spmv.h): X[r*ldx + j], r < n_rows; Y[c*ldy + j],
  * c < n_cols; j < k; ldx >= k, ldy >= k.  Serial: zeroes Y[c*ldy + j], j < k,

@@ -86,20 +86,26 @@ inline bool vec_ok(const double *p, int64_t ld, int32_t j0, int w)
 }
 
 // f(W, VEC, j0, chunks) for the whole blocks of kVecW columns, then for the
-// k % kVecW columns left: at most two launches
-template <typename F>
-inline void for_column_blocks(int32_t k, const double *a, int64_t lda, const double *b, int64_t ldb, F &&f)
+// k % kVecW columns left: at most two launches.  ok(j0, w) says whether EVERY
+// operand of the launch that starts at column j0 with w columns per thread
+// passes vec_ok
+template <typename OK, typename F>
+inline void for_column_blocks_if(int32_t k, OK &&ok, F &&f)
 {
     const int32_t whole = k / kVecW, rest = k % kVecW;
     if (whole > 0)
-        with_bool(vec_ok(a, lda, 0, kVecW) && vec_ok(b, ldb, 0, kVecW),
-                  [&](auto V) { f(std::integral_constant<int, kVecW>{}, V, 0, whole); });
+        with_bool(ok(0, kVecW), [&](auto V) { f(std::integral_constant<int, kVecW>{}, V, 0, whole); });
     if (rest > 0) {
         const int32_t j0 = whole * kVecW;
-        with_bool(vec_ok(a, lda, j0, rest) && vec_ok(b, ldb, j0, rest), [&](auto V) {
-            with_int<1, 2, 3, 4, 5, 6, 7>(rest, [&](auto Wc) { f(Wc, V, j0, 1); });
-        });
+        with_bool(ok(j0, rest), [&](auto V) { with_int<1, 2, 3, 4, 5, 6, 7>(rest, [&](auto Wc) { f(Wc, V, j0, 1); }); });
     }
+}
+
+// the same for a kernel with two operands
+template <typename F>
+inline void for_column_blocks(int32_t k, const double *a, int64_t lda, const double *b, int64_t ldb, F &&f)
+{
+    for_column_blocks_if(k, [&](int32_t j0, int w) { return vec_ok(a, lda, j0, w) && vec_ok(b, ldb, j0, w); }, f);
 }
 
 }  // namespace spmv

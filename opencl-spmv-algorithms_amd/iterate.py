@@ -1,5 +1,5 @@
-"""iterate.py — iterated SpMV over row shards: power iteration, CG and
-multi-right-hand-side CG.
+"""iterate.py — iterated SpMV over row shards: power iteration, CG,
+multi-right-hand-side CG and BiCGSTAB.
 
 SURVEY.md §8f row 3: "Iterated SpMV (power iteration / CG) reusing the y
 all-gather as the next x".  The reference stops after one SpMV (reference
@@ -51,6 +51,12 @@ build_operator(chebyshev=deg) puts a Chebyshev polynomial of that degree in
 M^-1 A over it (Chebyshev): the stronger preconditioner that keeps to the same
 rule.  Its coefficients are host floats computed before the solve, so an inner
 step is one product and one fused kernel, with no reduction.
+
+Non-symmetric matrices (bicgstab, bicgstab_multi): right-preconditioned
+BiCGSTAB on the same layout, products and device-resident scalars, one
+recurrence per column, with three fused block kernels of its own
+(spmv_dot2_multi, spmv_bicgstab_update_dot_multi, spmv_bicgstab_dir_multi) so
+that an iteration is 10 launches; block Jacobi is its preconditioner.
 
 The device work goes through a `kernels` object (HipKernels by default).
 Tests substitute a numpy double to exercise the multi-rank orchestration on
@@ -284,12 +290,43 @@ class HipKernels:
         nbytes = self.lib.spmv_dot_multi_ws_bytes(n, k)
         return torch.empty(nbytes, dtype=torch.uint8, device=self.dev)
 
+    # the fused block kernels of BiCGSTAB (_bicgstab): out holds 2k scalars,
+    # ws dot_multi_ws(n, 2k)
+    def dot2_multi(self, n, A, B, C, out, ws) -> None:
+        """out[:k] = column sums of A B, out[k:2k] of A C (C may be A)."""
+        sa._check(self.lib.spmv_dot2_multi(n, A.shape[1], sa._ptr(A), self._ld(A), sa._ptr(B), self._ld(B),
+                                           sa._ptr(C), self._ld(C), sa._ptr(out), sa._ptr(ws), ws.numel(),
+                                           self.dev.index or 0, self._s()), "spmv_dot2_multi")
+
+    def bicgstab_update_dot(self, n, a_num, a_den, w_num, w_den, Ph, Sh, T, R0, X, R, out, ws) -> None:
+        """X += alpha Ph + omega Sh, R -= omega T (alpha = a_num / a_den,
+        omega = w_num / w_den, 0 for a zero denominator; Sh may be R), and
+        out[:k] = column sums of R0 R, out[k:2k] of R R over the new R."""
+        sa._check(self.lib.spmv_bicgstab_update_dot_multi(
+            n, X.shape[1], sa._ptr(a_num), sa._ptr(a_den), sa._ptr(w_num), sa._ptr(w_den), sa._ptr(Ph), self._ld(Ph),
+            sa._ptr(Sh), self._ld(Sh), sa._ptr(T), self._ld(T), sa._ptr(R0), self._ld(R0), sa._ptr(X), self._ld(X),
+            sa._ptr(R), self._ld(R), sa._ptr(out), sa._ptr(ws), ws.numel(), self.dev.index or 0, self._s()),
+            "spmv_bicgstab_update_dot_multi")
+
+    def bicgstab_dir(self, n, rho_new, rv, tt, ts, V, R, P) -> None:
+        """P = R + beta (P - omega V), beta = (rho_new / rv) (tt / ts), omega =
+        ts / tt (each ratio 0 for a zero denominator)."""
+        sa._check(self.lib.spmv_bicgstab_dir_multi(n, P.shape[1], sa._ptr(rho_new), sa._ptr(rv), sa._ptr(tt),
+                                                   sa._ptr(ts), sa._ptr(V), self._ld(V), sa._ptr(R), self._ld(R),
+                                                   sa._ptr(P), self._ld(P), self.dev.index or 0, self._s()),
+                  "spmv_bicgstab_dir_multi")
+
     # the preconditioner M (sa.BlockJacobi over this rank's n rows):
     # Z = M^-1 R, out[:k] = column sums of R Z, out[k:2k] of R R
     def precond_apply_dot(self, M, n, R, Z, out, ws) -> None:
         sa._check(self.lib.spmv_bjacobi_apply_dot_multi(M.handle, R.shape[1], sa._ptr(R), self._ld(R), sa._ptr(Z),
                                                         self._ld(Z), sa._ptr(out), sa._ptr(ws), ws.numel(), self._s()),
                   "spmv_bjacobi_apply_dot_multi")
+
+    def precond_apply(self, M, n, R, Z) -> None:
+        """Z = M^-1 R alone (BiCGSTAB needs no sums of it)."""
+        sa._check(self.lib.spmv_bjacobi_apply_multi(M.handle, R.shape[1], sa._ptr(R), self._ld(R), sa._ptr(Z),
+                                                    self._ld(Z), self._s()), "spmv_bjacobi_apply_multi")
 
     def precond_ws(self, M, n, k):
         return M.ws(n, k)
@@ -664,13 +701,13 @@ def cg_multi(op: DistOperator, B_loc, comm: Comm | None = None, tol: float = 1e-
         return _cg_multi(op, B_loc, comm, tol, maxit, check_every, _precond_of(op, precond))
 
 
-def _check_block(op, B_loc) -> int:
+def _check_block(op, B_loc, who: str = "cg_multi") -> int:
     """B_loc must be a contiguous float64 (rows, k >= 1) tensor on the
     operator's device; returns k."""
     torch = sa._torch()
 
     def refuse(why):
-        return sa.SpmvError(sa.OTHER_ERROR, "cg_multi", why)
+        return sa.SpmvError(sa.OTHER_ERROR, who, why)
 
     if not isinstance(B_loc, torch.Tensor) or B_loc.dtype != torch.float64:
         raise refuse("B_loc must be a float64 tensor")
@@ -992,3 +1029,161 @@ def _pcg(op: DistOperator, comm: Comm, M, B, full, send, multi: bool, tol: float
             if (rr.cpu().numpy() <= tol * tol * bb).all():
                 break
     return X, it, rel(rr.cpu().numpy())
+
+
+# ----------------------------------------------------------------- BiCGSTAB
+def bicgstab(op: DistOperator, b_loc, comm: Comm | None = None, tol: float = 1e-10, maxit: int = 1000,
+             check_every: int = 10, precond=None):
+    """BiCGSTAB for a general (non-symmetric) square matrix, x0 = 0, on the
+    operator's kernel stream: _bicgstab through the block kernels with k = 1,
+    ld = 1 and the operator's single-vector product, so split and overlap
+    operators work.  precond as for cg (_precond_of): a block-Jacobi
+    preconditioner, applied from the right; a Chebyshev one is refused.
+    Returns (x_local, iterations, rel) with rel the TRUE relative residual
+    ||b - A x|| / ||b||: after a breakdown (_bicgstab) it is what shows that
+    the column has not converged."""
+    with _kernel_stream(op):
+        M = _bicgstab_precond(op, precond)
+        X, its, rel = _bicgstab(op, comm or Comm(), M, b_loc.unsqueeze(1), False, tol, maxit, check_every)
+        return X[:, 0], its, float(rel[0])
+
+
+def bicgstab_multi(op: DistOperator, B_loc, comm: Comm | None = None, tol: float = 1e-10, maxit: int = 1000,
+                   check_every: int = 10, precond=None):
+    """BiCGSTAB for k right-hand sides at once: k independent recurrences, one
+    per column of the row-major (rows, k) block B_loc, sharing two multi-vector
+    products per iteration (_bicgstab); NOT a block method.  Unsplit operators
+    whose matrix has a multi-vector run, as cg_multi.  Returns (X_local
+    (rows, k), iterations, rel: numpy (k,) of the true ||b_j - A x_j|| / ||b_j||)."""
+    with _kernel_stream(op):
+        M = _bicgstab_precond(op, precond)
+        if op.remote is not None:
+            raise sa.SpmvError(sa.OTHER_ERROR, "bicgstab_multi", "split / overlap operators are not supported")
+        if not getattr(op.kernels, "multi_supported", False):
+            raise sa.SpmvError(sa.OTHER_ERROR, "bicgstab_multi",
+                               "the operator's matrix has no multi-vector run (CSR, ELL and SELL plans have one)")
+        _check_block(op, B_loc, "bicgstab_multi")
+        return _bicgstab(op, comm or Comm(), M, B_loc, True, tol, maxit, check_every)
+
+
+def _bicgstab_precond(op, precond):
+    """_precond_of, refusing a Chebyshev polynomial before any device work: its
+    bounds assume a real positive spectrum, which a non-symmetric matrix does
+    not have."""
+    M = _precond_of(op, precond)
+    if isinstance(M, Chebyshev):
+        raise sa.SpmvError(sa.OTHER_ERROR, "bicgstab",
+                           "a Chebyshev preconditioner needs a real positive spectrum: use block Jacobi or none")
+    return M
+
+
+def _bicgstab(op: DistOperator, comm: Comm, M, B, multi: bool, tol: float, maxit: int, check_every: int):
+    """Right-preconditioned BiCGSTAB (x0 = 0, shadow residual r^ = b) for the nv
+    columns of B (rows, nv), one recurrence per column.  `multi`: the products
+    are spmm on (.., nv) blocks, otherwise spmv on vectors (nv = 1, any
+    operator).  M: a block-Jacobi preconditioner or None.  Returns (X (rows, nv),
+    iterations, rel: numpy (nv,)).
+
+    Per iteration, with ratio(a, b) = a / b and 0 WHEN b == 0 (the rule of the
+    block ratio kernels):
+        p^ = M^-1 p;  v = A p^;  rv = r^.v                 product, dot_multi (2)
+        r -= alpha v              alpha = ratio(rho, rv)   axpy_ratio_multi (1)
+        s^ = M^-1 r;  t = A s^;  ts = t.r, tt = t.t        product, dot2_multi (2)
+        x += alpha p^ + omega s^, r -= omega t,            bicgstab_update_dot (2)
+          rho' = r^.r, rr = r.r   omega = ratio(ts, tt)
+        p = r + beta (p - omega v)                         bicgstab_dir (1)
+          beta = ratio(rho', rv) ratio(tt, ts)   (= (rho'/rho)(alpha/omega))
+    10 launches for nv <= 8 without a preconditioner, 12 with one.  Every
+    scalar is a k-vector in device memory; (ts, tt) and (rho', rr) travel in one
+    all-reduce each, so there are three per iteration.  The host reads rr every
+    `check_every` iterations and stops when EVERY column has rr_j <= tol^2 bb_j,
+    or at maxit.
+
+    Without M, p^ is p and s^ is r: P and R are then the own blocks of the two
+    gathered buffer pairs themselves, and the update kernel is called with
+    Sh = R.  With M, p^ and s^ live in the pairs and P, R apart.
+
+    Breakdown.  rv = 0, ts = 0 (hence omega = 0) or rho' = 0 on a column that
+    has not converged is BiCGSTAB's breakdown.  The guarded ratios then make
+    that column stand still or stagnate; nothing becomes NaN, the other columns
+    go on, and THERE IS NO RESTART.  The stop test runs on the recurrence's
+    rr, which can also drift from the true residual, so the returned rel is
+    computed afresh, ||b_j - A x_j|| / ||b_j|| from one extra product and one
+    dot_multi after the loop (0.0 for a zero column): read it to see whether a
+    column converged.  A column with b_j = 0 keeps x_j = 0 exactly."""
+    torch = sa._torch()
+    k = op.kernels
+    rows = op.rows
+    nv = int(B.shape[1])
+
+    def zeros(*shape):
+        return torch.zeros(shape, dtype=torch.float64, device=op.device)
+
+    def block(t):  # a product vector as a (.., 1) block with ld = 1
+        return t if multi else t.unsqueeze(1)
+
+    def pair():  # (product over the pair, its own block's rows as a block)
+        send = zeros(op.pad, nv) if multi else zeros(op.pad)
+        if comm.world > 1:
+            full = zeros(op.world * op.pad, nv) if multi else zeros(op.world * op.pad)
+        else:
+            full = send
+        return _Apply(op, comm, full, send, multi=multi), block(send[:rows])
+
+    def product_vector():
+        v = zeros(max(rows, 1), nv) if multi else zeros(max(rows, 1))
+        return v, block(v)
+
+    apply_p, Ph = pair()
+    apply_s, Sh = pair()
+    P, R = (Ph, Sh) if M is None else (zeros(max(rows, 1), nv), zeros(max(rows, 1), nv))
+    v, V = product_vector()
+    t, T = product_vector()
+    X = zeros(rows, nv)
+    R0 = B.clone()
+    R[:rows].copy_(B)
+    P[:rows].copy_(B)
+    ws = k.dot_multi_ws(rows, 2 * nv)
+    rv, tst = zeros(nv), zeros(2 * nv)
+    ts, tt = tst[:nv], tst[nv:]
+    # (rho, rr) of the last and of the coming residual, as in _pcg
+    (s, rho, rr), (s_new, rho_new, rr_new) = ((u, u[:nv], u[nv:]) for u in (zeros(2 * nv), zeros(2 * nv)))
+    k.dot2_multi(rows, R0, R0, R0, s, ws)  # rho = rr = b.b
+    comm.allreduce(s)
+    bb = rr.cpu().numpy().copy()
+    if not (bb > 0.0).any():
+        return X, 0, np.zeros(nv)
+    it = 0
+    while it < maxit:
+        if M is not None:
+            k.precond_apply(M, rows, P, Ph)
+        apply_p(v)  # gathers p^
+        k.dot_multi(rows, R0, V, rv, ws)
+        comm.allreduce(rv)
+        k.axpy_ratio_multi(rows, rho, rv, -1.0, V, R)  # r_j -= alpha_j v_j: r holds s
+        if M is not None:
+            k.precond_apply(M, rows, R, Sh)
+        apply_s(t)  # gathers s^
+        k.dot2_multi(rows, T, R, T, tst, ws)
+        comm.allreduce(tst)
+        k.bicgstab_update_dot(rows, rho, rv, ts, tt, Ph, Sh, T, R0, X, R, s_new, ws)
+        comm.allreduce(s_new)
+        k.bicgstab_dir(rows, rho_new, rv, tt, ts, V, R, P)
+        (s, rho, rr), (s_new, rho_new, rr_new) = (s_new, rho_new, rr_new), (s, rho, rr)
+        it += 1
+        if it % check_every == 0 or it == maxit:
+            if (rr.cpu().numpy() <= tol * tol * bb).all():
+                break
+    # the true residual b - A x: x through the first pair, fma(-1, A x, b) is exact
+    Ph[:rows].copy_(X)
+    apply_p(v)
+    T[:rows].copy_(B)
+    one = zeros(nv) + 1.0
+    k.axpy_ratio_multi(rows, one, one, -1.0, V, T)
+    k.dot_multi(rows, T, T, rv, ws)
+    comm.allreduce(rv)
+    res = rv.cpu().numpy()
+    rel = np.zeros(nv)
+    live = bb > 0.0
+    rel[live] = np.sqrt(np.maximum(res[live], 0.0) / bb[live])
+    return X, it, rel

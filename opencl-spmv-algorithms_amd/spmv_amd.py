@@ -308,6 +308,13 @@ HIP_SYMBOLS = {
                                              _c_i64, ctypes.c_int, _vp]),
     "spmv_xpay_ratio_multi": (ctypes.c_int, [_c_i64, ctypes.c_int32, _vp, _vp, _vp, _c_i64, _vp, _c_i64,
                                              ctypes.c_int, _vp]),
+    "spmv_dot2_multi": (ctypes.c_int, [_c_i64, ctypes.c_int32, _vp, _c_i64, _vp, _c_i64, _vp, _c_i64, _vp, _vp,
+                                       ctypes.c_size_t, ctypes.c_int, _vp]),
+    "spmv_bicgstab_update_dot_multi": (ctypes.c_int, [_c_i64, ctypes.c_int32, _vp, _vp, _vp, _vp, _vp, _c_i64, _vp,
+                                                      _c_i64, _vp, _c_i64, _vp, _c_i64, _vp, _c_i64, _vp, _c_i64, _vp,
+                                                      _vp, ctypes.c_size_t, ctypes.c_int, _vp]),
+    "spmv_bicgstab_dir_multi": (ctypes.c_int, [_c_i64, ctypes.c_int32, _vp, _vp, _vp, _vp, _vp, _c_i64, _vp, _c_i64,
+                                               _vp, _c_i64, ctypes.c_int, _vp]),
     "spmv_bjacobi_create": (ctypes.c_int, [Dims, _vp, _vp, _vp, _c_i32, _c_i64, _c_i32, _PP]),
     "spmv_bjacobi_get_info": (ctypes.c_int, [_vp, ctypes.POINTER(BjacobiInfo)]),
     "spmv_bjacobi_inverse": (ctypes.c_int, [_vp, _PP]),
@@ -372,6 +379,10 @@ HOST_SYMBOLS = {
     "spmv_cpu_bjacobi_cheb_step_multi": (ctypes.c_int, [_c_i64, _c_i32, _vp, _c_i32, ctypes.c_double, ctypes.c_double,
                                                         _vp, _c_i64, _vp, _c_i64, _vp, _c_i64, _vp, _c_i64, _vp,
                                                         _c_i64]),
+    "spmv_cpu_bicgstab_update_multi": (ctypes.c_int, [_c_i64, _c_i32, _vp, _vp, _vp, _vp, _vp, _c_i64, _vp, _c_i64, _vp,
+                                                      _c_i64, _vp, _c_i64, _vp, _c_i64]),
+    "spmv_cpu_bicgstab_dir_multi": (ctypes.c_int, [_c_i64, _c_i32, _vp, _vp, _vp, _vp, _vp, _c_i64, _vp, _c_i64, _vp,
+                                                   _c_i64]),
     "spmv_csr_sort_rows": (ctypes.c_int, [_c_i64, _vp, _vp, _vp]),
     "spmv_csr_row_stats": (ctypes.c_int, [_c_i64, _vp, ctypes.POINTER(_c_i64), ctypes.POINTER(_c_i64), ctypes.POINTER(ctypes.c_double)]),
     "spmv_csr_pick_variant": (ctypes.c_int, [_c_i64, _vp]),
@@ -729,6 +740,50 @@ def cpu_bjacobi_cheb_step_multi(n: int, bs: int, inv: np.ndarray, a: float, b: f
     _check_host(host_lib().spmv_cpu_bjacobi_cheb_step_multi(n, bs, _ptr(inv), k, float(a), float(b), p(R), ld(R), p(AZ),
                                                             ld(AZ), p(D), ld(D), p(Zin), ld(Zin), p(Zout), ld(Zout)),
                 "spmv_cpu_bjacobi_cheb_step_multi")
+
+
+def _bicgstab_blocks(what: str, n: int, k, blocks, scalars):
+    """The checks of the two BiCGSTAB host statements: 2-D float64 blocks with
+    unit inner stride and >= n rows, k (default: the first block's width)
+    columns in each, float64 arrays of >= k scalars.  Returns (k, ld(block))."""
+    for t in blocks:
+        if not isinstance(t, np.ndarray) or t.dtype != np.float64 or t.ndim != 2:
+            raise SpmvError(OTHER_ERROR, what, "the blocks must be 2-D float64 arrays")
+        if t.shape[1] > 1 and t.strides[1] != 8 or t.strides[0] % 8:
+            raise SpmvError(OTHER_ERROR, what, "the blocks need unit inner stride")
+        if t.shape[0] < n:
+            raise SpmvError(OTHER_ERROR, what, "a block has too few rows")
+    k = blocks[0].shape[1] if k is None else int(k)
+    if any(k > t.shape[1] for t in blocks):
+        raise SpmvError(OTHER_ERROR, what, "a block has fewer than k columns")
+    for c in scalars:
+        if not isinstance(c, np.ndarray) or c.dtype != np.float64 or c.ndim != 1 or c.size < k or \
+                (c.size > 1 and c.strides[0] != 8):
+            raise SpmvError(OTHER_ERROR, what, "the scalars must be contiguous float64 arrays of k entries")
+    return k, lambda t: t.strides[0] // 8 if t.shape[0] > 1 else k  # one row: its stride is never used
+
+
+def cpu_bicgstab_update_multi(n: int, a_num, a_den, w_num, w_den, Ph, Sh, T, X, R, k: int | None = None) -> None:
+    """Host statement of BiCGSTAB's fused update (spmv_cpu_bicgstab_update_multi):
+    with alpha_j = a_num[j] / a_den[j] and omega_j = w_num[j] / w_den[j] (0 for
+    a zero denominator), X = fma(omega, Sh, fma(alpha, Ph, X)) and
+    R = fma(-omega, T, R) on 2-D float64 blocks (>= n rows, unit inner stride);
+    Sh may be R itself.  Only X[:n, :k] and R[:n, :k] are written."""
+    k, ld = _bicgstab_blocks("cpu_bicgstab_update_multi", n, k, (Ph, Sh, T, X, R), (a_num, a_den, w_num, w_den))
+    _check_host(host_lib().spmv_cpu_bicgstab_update_multi(n, k, _ptr(a_num), _ptr(a_den), _ptr(w_num), _ptr(w_den),
+                                                          _ptr(Ph), ld(Ph), _ptr(Sh), ld(Sh), _ptr(T), ld(T), _ptr(X),
+                                                          ld(X), _ptr(R), ld(R)), "spmv_cpu_bicgstab_update_multi")
+
+
+def cpu_bicgstab_dir_multi(n: int, rho_new, rv, tt, ts, V, R, P, k: int | None = None) -> None:
+    """Host statement of BiCGSTAB's direction update (spmv_cpu_bicgstab_dir_multi):
+    P = fma(beta, fma(-omega, V, P), R) with beta_j = (rho_new[j] / rv[j]) *
+    (tt[j] / ts[j]) and omega_j = ts[j] / tt[j] (0 for a zero denominator).
+    Only P[:n, :k] is written."""
+    k, ld = _bicgstab_blocks("cpu_bicgstab_dir_multi", n, k, (V, R, P), (rho_new, rv, tt, ts))
+    _check_host(host_lib().spmv_cpu_bicgstab_dir_multi(n, k, _ptr(rho_new), _ptr(rv), _ptr(tt), _ptr(ts), _ptr(V),
+                                                       ld(V), _ptr(R), ld(R), _ptr(P), ld(P)),
+                "spmv_cpu_bicgstab_dir_multi")
 
 
 def csr_sort_rows(n_rows: int, ptr, col, val) -> None:
