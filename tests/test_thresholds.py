@@ -8,10 +8,23 @@ restatement of sell_split_fix_kernel's run-end search finds every run's end,
 and its earlier form (lo kept after a coarse pass without a match) reported
 c + 65,537 for exactly the run lengths [65,474, 65,536] and, one pass
 further, c + 131,073 for [131,010, 131,072].
+
+The staged family (coo_staged_kernel, coo_carry_kernel, coo_tail_kernel,
+cmrs_tiled_kernel and the two window kernels): every constant and launch rule
+that tests/thresholds.py restates is held against the defining line of the
+sources (test_restated_constants_match_the_sources: the plan reports none of
+them, so a stale restatement would otherwise fail no test); the constructors
+deliver the tile spans, tails, carry runs, placements and x windows they
+promise; a numpy model of coo_carry_kernel gives the int64 reference on the
+carry arrays of carry_run_matrix, plain and k-major, and four one-line
+mutations of it do not; a word count of coo_staged_kernel's three row paths
+stays inside s_start[RC + 1] at every span under test and leaves it when the
+bitmap path's upper line moves one row up.
 """
 from __future__ import annotations
 
 import math
+from pathlib import Path
 
 import numpy as np
 import pytest
@@ -162,6 +175,282 @@ def test_bigplan_draws_both_lines(order):
     assert L.spmv_csr_tiled_bigplan(m.n_rows, sa._ptr(ptr), th.TILE, 65536, None) == tiles + 1 + (tiles + 1) % 2
 
 
+# ------------------------------------ the staged family: restated constants
+def test_restated_constants_match_the_sources():
+    """Every constant and rule thresholds.py restates, on its defining line of
+    csrc/: the plan reports no COO lanes, tile or row cap, so nothing else
+    would notice a restatement gone stale."""
+    src = Path(sa.__file__).resolve().parent / "csrc"
+    text = {f: (src / f).read_text() for f in ("staged.hip", "coo.hip", "common.h", "sell.hip")}
+    lines = {
+        "common.h": [f"constexpr int kWave = {th.K_WAVE};", f"constexpr int kBlock = {th.K_BLOCK};",
+                     f"constexpr int32_t kStagedXwinCap = {th.XWIN_CAP};"],
+        "sell.hip": [f"constexpr int kSellFixThreads = {th.FIX_THREADS};", f"int64_t lo = c + 1, step = {th.FIX_STEP};"],
+        "coo.hip": [f"int32_t rr[{th.CARRY_SHORT}];", f"const bool lng = head && rr[{th.CARRY_SHORT - 1}] == r;",
+                    f"for (int k = 0; k < {th.CARRY_SHORT} && rr[k] == r; ++k)",
+                    f"base += {th.CARRY_ROUND // th.K_WAVE} * kWave", "const bool head = t < n_tiles && r >= 0 && prev != r;",
+                    "q[u] = i < n_tiles ? carry_row[i] : -2;"],
+        "staged.hip": [
+            f"constexpr int kCooRowCap = {th.COO_ROW_CAP};", f"constexpr int kCooRowCapShort = {th.COO_ROW_CAP_SHORT};",
+            f"constexpr int kCooTailCap = {th.COO_TAIL_CAP};", f"constexpr int kCooR = {th.COO_R};",
+            f"constexpr int kTiledRowCap = {th.ROW_CAP};", f"constexpr int kTiledBigRowCap = {th.BIG_ROW_CAP};",
+            f"constexpr int kTiledR = {th.TILE // (2 * th.K_BLOCK)};",
+            "int64_t csr_tiled_tile(int64_t, int64_t) { return 2 * kBlock * kTiledR; }",
+            "int64_t coo_staged_tile() { return 2 * kBlock * kCooR; }",
+            # coo_lanes, coo_hot_r, cmrs_tiled_r
+            f"return mean >= {th.MEAN_LANES_8} ? 8 : mean >= {th.MEAN_LANES_4} ? 4 : 2;",
+            f"return n_rows > 0 && (double)nnz < {th.MEAN_BIG_TILE} * (double)n_rows ? 1 : kCooR;",
+            f"return n_rows > 0 && (double)nnz >= {th.MEAN_BIG_TILE} * (double)n_rows ? 3 : 1;",
+            # which RC a launch takes: the default, or by lane count
+            "int RC = kCooRowCap>",
+            "constexpr int RC = LL == 2 ? kCooRowCap : kCooRowCapShort;",
+            "go(coo_staged_kernel<LL, R, false, false, true, XGlobal, true, RC>);",
+            "go(coo_staged_kernel<LL, RR, false, true>);",
+            "go(coo_staged_kernel<LL, RR, false, false, true, XGlobal, false, RC>);",
+            "(coo_staged_kernel<decltype(Lc)::value, decltype(Rc)::value, false, false, true, XHot>)",
+            "(coo_staged_kernel<4, R, true, false, false, XGlobal, true>)", "(coo_staged_kernel<4, R, true, false>)",
+            "(coo_staged_kernel<4, R, true, false, true, XHot>)",
+            "const int64_t tile = tails ? coo_staged_tile() : coo_hot_tile(d.n_rows, d.nnz);",
+            # the three row paths and their storage
+            "__shared__ int32_t s_start[RC + 1];", "heads = span >= 0 && span <= RC;",
+            "constexpr int FW = (2 * kBlock * R + 63) / 64 * 2;",
+            "if (!heads && span > RC && span <= 32 * (int64_t)(RC + 1 - FW)) {",
+            "constexpr int TP = TAIL ? (kCooTailCap + 1) / 2 : 0;",
+            "while (k <= kCooTailCap && t1 + k < nnz && row[t1 + k] == last)",
+            # the k-major carries, the strip-run geometry and its windows
+            "carry_row[(int64_t)g * tiles + tile] = cr;", "int l = spmv_csr_auto_lanes(d.n_rows, d.nnz);",
+            "while (l > 1 && l * h > kBlock)", "*G = kBlock / (l * h) > 0 ? kBlock / (l * h) : 1;",
+            "const int64_t c0 = b & ~(int64_t)31;",
+            "r = block_col_range(col, c0 >= 2 ? c0 - 2 : 0, e + 1 < nz ? e + 1 : nz);",
+            "staged = span > 0 && span <= xcap;", "staged = span > 0 && span <= xcap && span <= 8 * kBlock;",
+        ],
+    }
+    for f, want in lines.items():
+        for line in want:
+            assert text[f].count(line) >= 1, f"update tests/thresholds.py with the kernel: {f} no longer has `{line}`"
+    assert th.BIG_TILE == 2 * th.K_BLOCK * th.COO_R and th.TILE == 2 * th.K_BLOCK and th.FIX_PASS == 65_536
+    assert 8 * th.K_BLOCK == th.XWIN_CAP  # cmrs_staged_kernel's one-pass window copy holds a window at the cap
+    # the derived edges, as the kernels' comments name them
+    assert th.first_words(th.TILE) == 16 and th.first_words(th.BIG_TILE) == 48
+    assert [th.span_edges(rc, t) for rc in (250, 1024) for t in (th.TILE, th.BIG_TILE)] == [
+        (250, 251, 7520, 7521), (250, 251, 6496, 6497), (1024, 1025, 32288, 32289), (1024, 1025, 31264, 31265)]
+    assert [th.coo_row_cap(la, L) for la in ("carry", "single") for L in (2, 4, 8)] == [1024, 250, 250] * 2
+    assert [th.coo_row_cap(la, 4) for la in ("xwin", "hot", "acc")] == [1024] * 3
+    assert [th.coo_lanes(1000, n) for n in (11_999, 12_000, 47_999, 48_000)] == [2, 4, 4, 8]
+    assert [th.carry_tile(1000, n) for n in (95_999, 96_000)] == [512, 1536]
+
+
+# ---------------------------------------------------- COO tiles by their span
+@pytest.mark.parametrize("name", sorted(th.SPAN_CASES))
+def test_coo_span_matrix_delivers_its_spans(name):
+    launch, lanes, tile, final = th.SPAN_CASES[name]
+    info, e, (mr, x, ref, bound) = th.coo_span_case(name)
+    m, rc = e.m, info["rc"]
+    lo, lo1, hi, hi1 = info["edges"]
+    assert (lo, lo1, hi, hi1) == (rc, rc + 1, 32 * (rc + 1 - th.first_words(tile)), 32 * (rc + 1 - th.first_words(tile)) + 1)
+    assert sorted(info["spans"]) == [lo, lo1, lo1, hi, hi1]
+    assert [th.staged_row_path(s, rc, tile) for s in (lo, lo1, hi, hi1)] == ["heads", "bitmap", "bitmap", "search"]
+    row = np.sort(m.row)
+    spans = th.coo_tile_spans(row, tile)
+    assert [int(spans[t]) for t in info["under"]] == list(info["spans"])
+    for t, s in zip(info["under"], info["spans"]):  # the definition once more, from the entries
+        t1 = min((t + 1) * tile, m.nnz)
+        assert row[t1 - 1] - row[t * tile - 1] == s and np.unique(row[t * tile:t1]).size <= 3
+    assert th.coo_lanes(m.n_rows, m.nnz) == lanes and info["lanes"] == lanes
+    if launch == "single":
+        plan = th.coo_tail_plan(row)
+        assert plan.max() == th.COO_TAIL_CAP and sorted(plan[list(info["under"])])[-2:] == [79, 80]
+    else:
+        assert th.carry_tile(m.n_rows, m.nnz) == tile
+        assert len(th.carry_runs(row, tile)) >= (4 if final else 5)
+    lens = np.bincount(m.row, minlength=m.n_rows)
+    assert (lens[-37:] == 0).all() and lens[-38] > 0 and (lens == 0).sum() == sum(s - 2 for s in info["spans"]) + 37
+    assert (info["under"][-1] == info["tiles"] - 1) == final and (m.nnz % tile == 0) == final
+    assert m.nnz <= 2_000_000 and e.a >= 20
+    assert th.coo_span_case(name)[1] is e  # made once
+
+
+def test_span_cases_get_no_hot_column_table_by_rule():
+    """hot=None leaves these matrices without a table (as the SELL cases): the
+    cases without a `hot` keyword take the launches SPAN_CASES names."""
+    for name in ("carry-L4", "wide-L4", "single-L8"):
+        m = th.coo_span_case(name)[1].m
+        assert sa.hot_columns(m.n_cols, m.col, 0)[0] == 0
+    m = th.coo_span_case("wide-L4")[1].m
+    assert sa.hot_columns(m.n_cols, m.col, 64)[0] == 64
+    for m in (th.carry_case(th.TILE)[1].m, th.hyb_tail_case()[1].m, th.coo_tail_case(False)[1].m):
+        assert sa.hot_columns(m.n_cols, m.col, 0)[0] == 0
+
+
+def test_staged_row_paths_stay_inside_s_start():
+    """The words of s_start[RC + 1] the three row paths touch, for a full tile
+    at every span under test: within RC + 1, exactly RC + 1 at the bitmap
+    path's upper edge, and RC + 2 there if that line lay one row higher."""
+    for name, (launch, lanes, tile, final) in th.SPAN_CASES.items():
+        rc = th.coo_row_cap(launch, lanes)
+        lo, lo1, hi, hi1 = th.span_edges(rc, tile)
+        words = [th.staged_lds_words(s, tile, rc, tile) for s in (lo, lo1, hi, hi1)]
+        assert words == [rc + 1, (lo1 + 31) // 32 + th.first_words(tile), rc + 1, 0], (name, words)
+        assert max(words) <= rc + 1
+        assert th.staged_lds_words(hi1, tile, rc, tile, upper=hi1) == rc + 2 > rc + 1, name
+        assert th.staged_lds_words(lo1, tile, rc, tile, upper=hi1) <= rc + 1
+    assert th.first_words(th.BIG_TILE) <= th.COO_ROW_CAP + 1  # the accumulate kernel: row-first words only
+
+
+# ------------------------------------------------------- single-pass tails
+def test_coo_tail_matrix_delivers_its_tails():
+    (plan, e, _), (plan81, e81, _) = th.coo_tail_case(False), th.coo_tail_case(True)
+    assert plan.tolist() == [80, 0, 2, 0, 79, 0, 1, 0] and plan81.tolist() == [81, 0, 2, 0, 79, 0, 1, 0]
+    m, m81 = e.m, e81.m
+    assert m.nnz % 2 == 1 and m.nnz == m81.nnz and m.n_rows == m81.n_rows and np.array_equal(m.col, m81.col)
+    assert m.row[-1] == m.row[7 * th.BIG_TILE - 1] != m.row[7 * th.BIG_TILE - 2 - th.BIG_TILE]  # the tail of 1: nnz - 1
+    diff = np.flatnonzero(np.bincount(m.row, minlength=m.n_rows) != np.bincount(m81.row, minlength=m.n_rows))
+    assert diff.tolist() == [3, 4]
+    assert th.coo_tail_case(False)[1] is e
+
+
+# ---------------------------------------------------------------- HYB tail
+def test_hyb_tail_span_matrix_delivers_its_spans():
+    info, e, _ = th.hyb_tail_case()
+    m = e.m
+    lens = np.bincount(m.row, minlength=m.n_rows)
+    assert lens.min() == th.HYB_K and info["spans"] == (1024, 1025, 1025, 40_000)
+    assert np.array_equal(info["no_tail"], np.flatnonzero(lens == th.HYB_K)) and info["no_tail"].size > 42_000
+    ptr, col, val = sa.csr_from_coo(m)
+    hb = sa.hyb_build(m.n_rows, ptr, col, val, ki=2, K=th.HYB_K)
+    tr = hb["tail_row"][: hb["tail_nnz"]]
+    spans = th.coo_tile_spans(tr, th.BIG_TILE)
+    assert [int(spans[t]) for t in info["under"]] == [1024, 1025, 1025, 40_000]
+    assert [th.staged_row_path(s, th.COO_ROW_CAP, th.BIG_TILE) for s in (1024, 1025, 40_000)] == ["heads", "bitmap", "search"]
+    assert th.coo_tail_plan(tr).max() == 80 and len(th.carry_runs(tr, th.BIG_TILE)) >= 4
+    assert th.hyb_tail_case()[1] is e
+
+
+# -------------------------------------------------------------- carry runs
+@pytest.mark.parametrize("tile", [th.TILE, th.BIG_TILE])
+def test_carry_run_matrix_delivers_its_runs(tile):
+    info, e, _ = th.carry_case(tile)
+    m = e.m
+    want = [1, 7, 8, 9, 255, 256, 257, 511, 512, 513] if tile == th.TILE else [7, 8, 9, 255, 256, 257]
+    assert [k for _, k, _ in info["long_rows"]] == want
+    runs = th.carry_runs(np.sort(m.row), tile)
+    assert runs == info["runs"] == th.carry_runs(np.asarray(sa.csr_from_coo(m)[0]), tile)
+    lens = np.bincount(m.row, minlength=m.n_rows)
+    for r, k, head in info["long_rows"]:
+        assert lens[r] == tile * k + 7 and (head, k) in runs and r % 64 in (0, 63)
+    heads = {k: head for _, k, head in info["long_rows"]}
+    assert heads[8] % 64 == 0 and heads[9] // 64 == heads[8] // 64  # two wave-path heads in one wave
+    assert heads[255] % 64 == 63 and heads[256] % 256 == 255
+    assert sum(runs[-1]) == info["tiles"] == -(-m.nnz // tile) and runs[-1][1] == want[-1]
+    assert th.carry_tile(m.n_rows, m.nnz) == tile and m.nnz <= 2_000_000
+    assert lens.max() > np.bincount(m.col).max()  # integerize sizes its sums by the longest row
+    # the HYB tail of the long rows (1,536-entry tiles whatever the matrix) has runs on both sides of 8 and of 256
+    ptr, col, val = sa.csr_from_coo(m)
+    hb = sa.hyb_build(m.n_rows, ptr, col, val, ki=2, K=th.HYB_K)
+    tail = [n for _, n in th.carry_runs(hb["tail_row"][: hb["tail_nnz"]], th.BIG_TILE)]
+    assert min(tail) < th.CARRY_SHORT <= max(tail)
+    if tile == th.BIG_TILE:
+        assert {7, 8, 9, 255, 256, 257} <= set(tail)
+    assert th.carry_case(tile)[1] is e
+
+
+def _model_rows(cr, cv, y0, ref, **kw):
+    """Rows where the carry model's y differs from the int64 reference."""
+    return exact.exact_bad_rows(th.carry_model(cr, cv, y0.copy(), **kw), ref)
+
+
+def _stale(cr, cv, n=300):
+    """The arrays with n more elements behind them that continue the last
+    carry: what an unchecked load past n_tiles may find."""
+    return np.concatenate((cr, np.full(n, cr[-1]))), np.concatenate((cv, np.ones(n)))
+
+
+@pytest.mark.parametrize("tile", [th.TILE, th.BIG_TILE])
+def test_carry_model_gives_the_reference(tile):
+    """coo_carry_kernel's order of work in numpy, on the carries of the integer
+    copy: the COO / CSR layout and, for 512-entry tiles, cmrs_tiled_kernel's
+    k-major one at h = 8 and h = 64."""
+    _, e, _ = th.carry_case(tile)
+    cr, cv, y0 = th.carry_arrays(e.m, e.x, tile)
+    assert exact.exact_bad_rows(y0, e.ref).size >= len(th.CARRY_RUNS[tile])  # the carries are needed
+    assert _model_rows(cr, cv, y0, e.ref).size == 0
+    crs, cvs = _stale(cr, cv)
+    assert _model_rows(crs, cvs, y0, e.ref, n_tiles=cr.size).size == 0
+    if tile == th.TILE:
+        for h in (8, 64):
+            kr, kv, ky, tiles = th.cmrs_carry_arrays(e.m, e.x, h, tile)
+            assert kr.size == h * tiles and kr[-1] >= 0  # a run ends on the array's last element
+            assert exact.exact_bad_rows(ky, e.ref).size > 0 and _model_rows(kr, kv, ky, e.ref).size == 0
+
+
+@pytest.mark.parametrize("tile", [th.TILE, th.BIG_TILE])
+@pytest.mark.parametrize("mutate", ["one_round", "short", "unbounded", "first_head"])
+def test_carry_model_mutations_fail_here(tile, mutate):
+    """Each one-line mutation of the model changes rows of carry_run_matrix:
+    one round only loses the runs of more than 256 tiles (a run of exactly 256
+    needs the second round only to find its end), the short path alone every
+    run of 9 or more, loads past n_tiles add to the run that ends on the last
+    tile, and a wave that serves only its first wave-path head loses the runs
+    of 9 and of 255 tiles, whose heads share a wave with the run of 8."""
+    info, e, _ = th.carry_case(tile)
+    cr, cv, y0 = th.carry_arrays(e.m, e.x, tile)
+    crs, cvs = _stale(cr, cv)
+    bad = _model_rows(crs, cvs, y0, e.ref, n_tiles=cr.size, mutate=mutate)
+    rows = {k: r for r, k, _ in info["long_rows"]}
+    if mutate == "one_round":
+        assert set(bad) == {r for k, r in rows.items() if k > th.CARRY_ROUND}
+    elif mutate == "short":
+        assert set(bad) == {r for k, r in rows.items() if k > th.CARRY_SHORT}  # a run of exactly 8: still right
+    elif mutate == "unbounded":
+        assert bad.tolist() == [info["long_rows"][-1][0]]
+    else:
+        long_heads = [(r, hd) for r, k, hd in info["long_rows"] if k >= th.CARRY_SHORT]
+        later = {r for i, (r, hd) in enumerate(long_heads) if any(h2 // th.K_WAVE == hd // th.K_WAVE for _, h2 in long_heads[:i])}
+        assert set(bad) == later == {rows[9], rows[th.CARRY_ROUND - 1]}
+
+
+def test_carry_model_mutations_on_one_row():
+    """What exact.generated("one_row") could tell before: its one run (39
+    continuation tiles of 512 entries, 13 of 1,536) stays inside the first
+    round, and it is the only one, so a wave path that stops after one round
+    or serves one head per wave passes it: no matrix of the suite had run the
+    second round or two wave-path heads in one wave.  It has no run of 7, 8 or
+    9 tiles either.  Its run is longer than 8 and ends on the last tile, so
+    the other two mutations already change it."""
+    e = exact.integerize(exact.generated("one_row"), seed=5)
+    for tile, run in ((th.TILE, 39), (th.BIG_TILE, 13)):
+        cr, cv, y0 = th.carry_arrays(e.m, e.x, tile)
+        assert th.runs_of(cr) == [(1, run)] and th.CARRY_SHORT < run < th.CARRY_ROUND
+        crs, cvs = _stale(cr, cv)
+        assert _model_rows(cr, cv, y0, e.ref).size == 0
+        assert _model_rows(crs, cvs, y0, e.ref, n_tiles=cr.size, mutate="one_round").size == 0
+        assert _model_rows(crs, cvs, y0, e.ref, n_tiles=cr.size, mutate="first_head").size == 0
+        assert _model_rows(crs, cvs, y0, e.ref, n_tiles=cr.size, mutate="short").tolist() == [1]
+        assert _model_rows(crs, cvs, y0, e.ref, n_tiles=cr.size, mutate="unbounded").tolist() == [1]
+
+
+# --------------------------------------------------------------- x windows
+def test_window_matrices_deliver_their_windows():
+    want = [100, 100, 2048, 100, 2049, 100, 1, 100, 100]
+    spans, e, _ = th.window_case("coo")
+    assert spans.tolist() == want and th.carry_tile(e.m.n_rows, e.m.nnz) == th.TILE
+    assert np.array_equal(th.tile_windows(sa.coo_sort_by_row(e.m)[1], th.TILE), spans)
+    spans, e, _ = th.window_case("cmrs")
+    m, _, G = th.cmrs_window_matrix()
+    assert spans.tolist() == want and m is not None and G * th.CMRS_WINDOW_H * len(want) > m.n_rows > G * th.CMRS_WINDOW_H * (len(want) - 1)
+    ptr, col, _ = sa.csr_from_coo(m)
+    # the entries outside a run that its chunks load widen no window: without them every span is the same
+    own = [int(col[ptr[s]:ptr[min(s + G * 8, m.n_rows)]].max() - col[ptr[s]:ptr[min(s + G * 8, m.n_rows)]].min()) + 1
+           for s in range(0, m.n_rows, G * 8)]
+    assert own == want
+    assert th.window_case("cmrs")[1] is e
+
+
 def test_references_are_shared():
     a = th.tiles_case("followed")
     assert th.tiles_case("followed")[2] is a[2] and not a[2].ref.flags.writeable
+    for make in (lambda: th.coo_span_case("carry-L2"), lambda: th.coo_tail_case(True), th.hyb_tail_case,
+                 lambda: th.carry_case(th.BIG_TILE), lambda: th.window_case("coo")):
+        b = make()
+        assert make()[1] is b[1] and make()[2][2] is b[2][2]
+        assert not b[1].ref.flags.writeable and not b[1].m.val.flags.writeable and not b[2][0].val.flags.writeable

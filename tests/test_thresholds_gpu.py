@@ -13,6 +13,27 @@
                           workgroups of the dot at n = 2,097,152, 4096 of the
                           updates at 4,194,304; vec_multi.hip: 1024 at 524,288
                           and 4096 at 4,194,304)
+  coo_staged_kernel       tiles spanning RC, RC + 1, 32 (RC + 1 - FW) and one
+                          more row (RC = 1024 or 250; FW = 16 or 48 words):
+                          the key-change table, the two bitmaps that fill
+                          s_start to its last word, the binary searches; for
+                          the carry pass at 2, 4 and 8 lanes and both tile
+                          sizes, with x windows, with the hot table, and for
+                          the single pass; single-pass tails of 1, 2, 79 and
+                          80 entries, one on the lone last entry, and the
+                          refusal of 81; the accumulate form under a HYB tail
+                          at spans of 1024, 1025 and 40,000 rows
+  coo_carry_kernel        runs of 1, 7, 8, 9, 255, 256, 257, 511, 512 and 513
+                          continuation tiles (tile order up to 7, the wave
+                          path from 8, rounds of 256), heads on the last lane
+                          of a wave and of a workgroup, two in one wave, the
+                          last run ending on the last tile: behind the tiled
+                          CSR (fp64 and fp32 values), COO, a HYB tail and the
+                          tiled CMRS, whose k-major carries end on the array's
+                          last element
+  x windows               a COO tile and a CMRS strip run spanning exactly
+                          kStagedXwinCap = 2048 columns (staged in LDS), 2049
+                          (gathered from global memory) and one, in one launch
 
 Every output starts as NaN (or lies between guard elements), every SpMV is
 checked with tests/exact.py's two rules, bit-exact on the integer copy and
@@ -359,3 +380,212 @@ def test_single_vector_kernels_at_the_grid_clamp(torch_dev, n):
     torch.cuda.synchronize()
     assert same_bits(live(ty), x[order])
     assert same_bits(tx.cpu().numpy(), x) and np.array_equal(to.cpu().numpy(), order)
+
+
+# ------------------------------------------ 4. the staged COO / CMRS family
+def run_both(torch_dev, e, real, fmt, kw, what, label, plan_check=None, ref_of=None):
+    """The integer copy (bit-exact) and the real copy (the fp64 bound) through
+    sa.to_device(m, fmt, **kw), each twice into NaN; -> {is integer copy: y}."""
+    torch, dev = torch_dev
+    mr, x, ref, bound = real
+    out = {}
+    for m, xin in ((e.m, e.x), (mr, x)):
+        dm = sa.to_device(m, fmt, dev, **kw)
+        if plan_check is not None:
+            plan_check(dm)
+        y = run_twice(torch, dev, dm, m, xin, what)
+        if m is e.m:
+            exact.assert_exact(y, e.ref, what)
+        else:
+            mm, rr, bb = (mr, ref, bound) if ref_of is None else ref_of()
+            note(label, exact.assert_fp64(y, mm, x, ref=rr, bound=bb, what=what))
+        out[m is e.m] = y
+        del dm
+    return out
+
+
+def empty_rows_are_plus_zero(y, m, what):
+    empty = np.bincount(m.row, minlength=m.n_rows) == 0
+    assert empty.any() and (y[empty] == 0.0).all() and not np.signbit(y[empty]).any(), f"{what}: an empty row is not +0.0"
+
+
+SPAN_RUNS = [(name, {} if th.SPAN_CASES[name][0] == "single" else {"coo_tail": False})
+             for name in sorted(th.SPAN_CASES) if name != "wide-L4"]
+
+
+@pytest.mark.parametrize("name,kw", SPAN_RUNS, ids=[n for n, _ in SPAN_RUNS])
+def test_coo_staged_row_paths_at_their_spans(torch_dev, name, kw):
+    """Tiles spanning RC, RC + 1, 32 (RC + 1 - FW) and 32 (RC + 1 - FW) + 1
+    rows (asserted by the constructor, with the lanes, the tile and the RC
+    the launch takes), one of them once more behind a continued first row;
+    their last rows run into the next tile (a carry, or a single-pass tail of
+    up to 80), in the -final cases the last of them closes the matrix and
+    owns the trailing empty rows.  An off-by-one at either line moves one
+    row's entry or runs over s_start: both change the integer sums."""
+    launch, lanes, tile, final = th.SPAN_CASES[name]
+    info, e, real = th.coo_span_case(name)
+    assert info["rc"] == th.coo_row_cap(launch, lanes) and info["tile"] == tile and info["lanes"] == lanes
+    assert sorted(set(info["spans"])) == list(info["edges"])
+
+    def plan_check(dm):
+        p = dm.params
+        assert p["kernel"] == "coo_staged_kernel" and p["H"] == 0 and bool(p["single_pass"]) == (launch == "single"), p
+
+    what = f"coo {name}"
+    ys = run_both(torch_dev, e, real, "coo", kw, what, "coo single pass" if launch == "single" else "coo carry pass",
+                  plan_check)
+    for y in ys.values():
+        empty_rows_are_plus_zero(y, e.m, what)
+
+
+def test_coo_staged_row_paths_with_x_windows_and_hot_table(torch_dev):
+    """One matrix (4 lanes, 512-entry tiles, spans around 1024 and 32,288)
+    through the x-window launch and the hot-column launch, both RC = 1024, and
+    the plain carry pass, RC = 250, whose bitmap and search paths the same
+    tiles take: the same bits from all three."""
+    info, e, real = th.coo_span_case("wide-L4")
+    assert info["rc"] == th.COO_ROW_CAP == th.coo_row_cap("hot", 4) and info["lanes"] == 4 and info["tile"] == th.TILE
+    assert [th.staged_row_path(s, th.coo_row_cap("carry", 4), th.TILE) for s in info["edges"]] == [
+        "bitmap", "bitmap", "search", "search"]
+    want = {"plain": 0, "xwin": 0, "hot": 64}
+    kws = {"plain": {"coo_tail": False}, "xwin": {"xwin": True, "coo_tail": False}, "hot": {"hot": 64}}
+    got = {}
+    for form, kw in kws.items():
+        def plan_check(dm, form=form):
+            p = dm.params
+            assert p["H"] == want[form] and not p["single_pass"], p
+            assert ("x windows" in p["plan"]) == (form == "xwin") and (p["xcap"] > 0) == (form == "xwin"), p
+
+        got[form] = run_both(torch_dev, e, real, "coo", kw, f"coo wide-L4 {form}", f"coo {form} launch", plan_check)
+        for y in got[form].values():
+            empty_rows_are_plus_zero(y, e.m, form)
+    for integer in (True, False):
+        assert same_bits(got["plain"][integer], got["xwin"][integer]), "x windows change bits"
+        assert same_bits(got["plain"][integer], got["hot"][integer]), "the hot table changes bits"
+
+
+def test_coo_single_pass_tails_at_the_cap(torch_dev):
+    """Tails of 80, 2, 79 and 1 entries (the last on nnz - 1 of an odd nnz):
+    the default plan is the single pass.  With one tail of 81 the single pass
+    is refused by name and the default falls back to the carry pass."""
+    torch, dev = torch_dev
+    plan, e, real = th.coo_tail_case(False)
+    assert plan.max() == th.COO_TAIL_CAP and e.m.nnz % 2 == 1
+
+    def single(dm):
+        assert dm.params["single_pass"] and dm.params["H"] == 0, dm.params
+
+    run_both(torch_dev, e, real, "coo", {}, "coo tails up to 80", "coo single pass", single)
+    run_both(torch_dev, e, real, "coo", {"coo_tail": True}, "coo tails up to 80, forced", "coo single pass", single)
+    plan, e, real = th.coo_tail_case(True)
+    assert plan.max() == th.COO_TAIL_CAP + 1
+    with pytest.raises(sa.SpmvError, match=f"more than {th.COO_TAIL_CAP} entries"):
+        sa.to_device(e.m, "coo", dev, coo_tail=True)
+
+    def carry(dm):
+        assert not dm.params["single_pass"] and dm.params["H"] == 0, dm.params
+
+    run_both(torch_dev, e, real, "coo", {}, "coo tail of 81", "coo carry pass", carry)
+
+
+HYB_FORMS = {"single-pass tail": {}, "carry pass": {"coo_tail": False}, "hot table": {"hot": 64},
+             "no x windows": {"xwin": False}}
+
+
+@pytest.mark.parametrize("form", sorted(HYB_FORMS))
+def test_hyb_tail_accumulate_at_its_spans(torch_dev, form):
+    """The accumulate kernel (4 lanes, 1,536-entry tiles, RC = 1024) under an
+    ELL part of K = 2: tail tiles spanning 1024, 1025 (twice) and 40,000 rows,
+    asserted on hyb_build's tail_row.  A row without tail entries keeps its
+    ELL sum: the integer check sees a zero written over it."""
+    info, e, real = th.hyb_tail_case()
+    assert info["spans"] == (th.COO_ROW_CAP, th.COO_ROW_CAP + 1, th.COO_ROW_CAP + 1, 40_000)
+    kw = HYB_FORMS[form]
+
+    def plan_check(dm):
+        p = dm.params
+        assert p["K"] == th.HYB_K and p["tail_nnz"] == e.m.nnz - th.HYB_K * e.m.n_rows and p["H"] == kw.get("hot", 0), p
+        assert ("tails" in dm.arrays) == (form in ("single-pass tail", "no x windows")), sorted(dm.arrays)
+        assert ("win" in dm.arrays) == (form == "single-pass tail"), sorted(dm.arrays)
+
+    y = run_both(torch_dev, e, real, "hyb", dict(kw, hyb_k=th.HYB_K), f"hyb {form}", "hyb tail (accumulate)", plan_check)
+    assert (y[True][info["no_tail"]] == e.ref[info["no_tail"]]).all()
+
+
+@functools.lru_cache(maxsize=None)
+def f32_reference(tile):
+    """The real copy of carry_case(tile) as csrf32 stores it, with its reference and bound."""
+    _, _, (mr, x, _, _) = th.carry_case(tile)
+    m32 = exact.rounded_f32(mr)
+    return m32, exact.exact_reference(m32, x), exact.fp64_bound(m32, x)
+
+
+CARRY_CONSUMERS = [
+    ("csr", th.TILE, {"variant": 4, "hot": 0}, "csr_tiled_kernel"),
+    ("csr", th.TILE, {"variant": 4, "hot": 64}, "csr_tiled_kernel"),
+    ("csrf32", th.TILE, {"variant": 4, "hot": 0}, None),
+    ("coo", th.TILE, {"coo_tail": False}, "coo_staged_kernel"),
+    ("coo", th.BIG_TILE, {"coo_tail": False}, "coo_staged_kernel"),
+    ("coo", th.TILE, {"xwin": True, "coo_tail": False}, "coo_staged_kernel"),
+    ("coo", th.TILE, {"hot": 64}, "coo_staged_kernel"),
+    ("hyb", th.BIG_TILE, {"hyb_k": th.HYB_K, "coo_tail": False}, None),
+    ("cmrs", th.TILE, {"cmrs_variant": 1, "h": 8}, "cmrs_tiled_kernel"),
+    ("cmrs", th.TILE, {"cmrs_variant": 1, "h": 64}, "cmrs_tiled_kernel"),
+]
+
+
+def _consumer_id(c):
+    return f"{c[0]}-tile{c[1]}-" + "-".join(f"{k}{v}" for k, v in c[2].items())
+
+
+@pytest.mark.parametrize("consumer", CARRY_CONSUMERS, ids=[_consumer_id(c) for c in CARRY_CONSUMERS])
+def test_carry_runs_at_the_wave_path_lines(torch_dev, consumer):
+    """coo_carry_kernel behind each of its callers, on rows that continue over
+    exactly 1, 7, 8, 9, 255, 256, 257 (and with 512-entry tiles 511, 512, 513)
+    tiles, placed as the constructor asserts: a run read one tile short or
+    long, a second round not taken, or a load past the last tile changes the
+    integer sum of a long row."""
+    fmt, tile, kw, kernel = consumer
+    info, e, real = th.carry_case(tile)
+    lengths = {n for _, n in info["runs"]}
+    assert {7, 8, 9, th.CARRY_ROUND - 1, th.CARRY_ROUND, th.CARRY_ROUND + 1} <= lengths
+    assert (2 * th.CARRY_ROUND + 1 in lengths) == (tile == th.TILE) and sum(info["runs"][-1]) == info["tiles"]
+
+    def plan_check(dm):
+        p = dm.params
+        assert p["H"] == kw.get("hot", 0), p
+        if kernel is not None:
+            assert p["kernel"] == kernel, p
+        if fmt == "coo":
+            assert not p["single_pass"] and ("x windows" in p["plan"]) == bool(kw.get("xwin")), p
+        if fmt == "csrf32":
+            assert p["variant"] == 4, p
+        if fmt == "hyb":
+            assert "tails" not in dm.arrays and p["tail_nnz"] > th.CARRY_ROUND * th.BIG_TILE, p
+
+    ref_of = (lambda: f32_reference(tile)) if fmt == "csrf32" else None
+    run_both(torch_dev, e, real, fmt, kw, f"carry runs behind {_consumer_id(consumer)}", f"carry pass behind {fmt}",
+             plan_check, ref_of)
+
+
+@pytest.mark.parametrize("fmt", ["coo", "cmrs"])
+def test_staged_x_window_cap(torch_dev, fmt):
+    """One launch with a window of exactly 2048 columns (staged in LDS), one of
+    2049 (gathered from global memory), one of a single column and narrow
+    ones, by the restated window kernels; the same bits without windows."""
+    spans, e, real = th.window_case(fmt)
+    assert sorted(set(spans.tolist())) == [1, 100, th.XWIN_CAP, th.XWIN_CAP + 1]
+    kw = {"coo_tail": False} if fmt == "coo" else {"cmrs_variant": 0, "h": th.CMRS_WINDOW_H}
+    kernel = "coo_staged_kernel" if fmt == "coo" else "cmrs_staged_kernel"
+
+    def windows(dm):
+        p = dm.params
+        assert p["kernel"] == kernel and p["xcap"] == th.XWIN_CAP and "x windows" in p["plan"] and p["H"] == 0, p
+
+    def none(dm):
+        assert dm.params["kernel"] == kernel and "x windows" not in dm.params["plan"], dm.params
+
+    on = run_both(torch_dev, e, real, fmt, dict(kw, xwin=True), f"{fmt} x windows at the cap", f"{fmt} x-window cap", windows)
+    off = run_both(torch_dev, e, real, fmt, dict(kw, xwin=False), f"{fmt} without x windows", f"{fmt} x-window cap", none)
+    for integer in (True, False):
+        assert same_bits(on[integer], off[integer]), f"{fmt}: x windows change bits"

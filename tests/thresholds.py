@@ -19,7 +19,28 @@ test can assert that it ran the case it meant:
                     spmv_csr_tiled_bigplan (host/formats.c) draws the same two
                     lines.
 
-Neither needs a GPU.  The matrices are made once per argument set and never
+The staged family (csrc/staged.hip, csrc/coo.hip) has its own constructors,
+with the kernels' constants and launch rules restated below (the plan reports
+none of them; tests/test_thresholds.py holds every restated line against the
+sources):
+
+  coo_span_matrix       COO tiles that span given numbers of rows (prev, last]:
+                        coo_staged_kernel takes its key-change table up to RC
+                        rows, the row-first and span bitmaps (both inside
+                        s_start[RC + 1]) up to 32 (RC + 1 - FW), two binary
+                        searches per row beyond
+  coo_tail_matrix       single-pass tiles whose last rows run 1, 2, 79 and 80
+                        entries past the tile (kCooTailCap = 80), one ending
+                        on the lone last entry of an odd nnz; or one of 81
+  hyb_tail_span_matrix  a HYB tail (the accumulate kernel) whose tiles span
+                        1024, 1025 and 40,000 rows
+  carry_run_matrix      rows over given numbers of continuation tiles:
+                        coo_carry_kernel sums a run of up to 7 in tile order
+                        and a run of 8 or more over the wave, 256 tiles a round
+  coo_window_matrix,    x windows of exactly kStagedXwinCap = 2048 columns, of
+  cmrs_window_matrix    2049 and of one, in one launch
+
+None needs a GPU.  The matrices are made once per argument set and never
 changed.
 """
 from __future__ import annotations
@@ -37,6 +58,19 @@ FIX_PASS = FIX_THREADS * FIX_STEP  # chunks one full coarse pass covers: 65,536
 TILE = 512              # staged.hip: 2 * kBlock * kTiledR entries per tile
 ROW_CAP = 1024          # staged.hip kTiledRowCap
 BIG_ROW_CAP = 65536     # staged.hip kTiledBigRowCap
+K_BLOCK = 256           # common.h kBlock
+K_WAVE = 64             # common.h kWave
+COO_ROW_CAP = 1024      # staged.hip kCooRowCap
+COO_ROW_CAP_SHORT = 250  # staged.hip kCooRowCapShort
+COO_TAIL_CAP = 80       # staged.hip kCooTailCap
+COO_R = 3               # staged.hip kCooR
+XWIN_CAP = 2048         # common.h kStagedXwinCap
+CARRY_SHORT = 8         # coo.hip coo_carry_kernel: rr[8], lng = rr[7] == r
+CARRY_ROUND = 4 * K_WAVE  # coo.hip coo_carry_kernel: base += 4 * kWave
+BIG_TILE = 2 * K_BLOCK * COO_R  # staged.hip coo_staged_tile(): 1536 entries
+MEAN_LANES_8 = 48.0     # staged.hip coo_lanes
+MEAN_LANES_4 = 12.0     # staged.hip coo_lanes
+MEAN_BIG_TILE = 96.0    # staged.hip coo_hot_r, cmrs_tiled_r
 
 
 def _freeze(m: sa.Coo) -> sa.Coo:
@@ -222,3 +256,614 @@ def owned_rows(n_rows: int, row_ptr: np.ndarray) -> np.ndarray:
     lo = np.searchsorted(row_ptr[:n_rows], np.arange(tiles, dtype=np.int64) * TILE, side="left")
     hi = np.concatenate((lo[1:], [n_rows]))  # the last tile: through n_rows - 1
     return (hi - lo).astype(np.int64)
+
+
+# ------------------------------------------- staged COO: launch rules restated
+def coo_lanes(n_rows: int, nnz: int) -> int:
+    """staged.hip coo_lanes: lanes per row of every COO launch but the accumulate one."""
+    mean = nnz / n_rows if n_rows > 0 else 0.0
+    return 8 if mean >= MEAN_LANES_8 else 4 if mean >= MEAN_LANES_4 else 2
+
+
+def carry_tile(n_rows: int, nnz: int) -> int:
+    """staged.hip coo_hot_r / cmrs_tiled_r: entries per tile of the COO carry
+    pass (plain, x windows, hot table) and of the tiled CMRS; the single pass
+    and the HYB tail always cut BIG_TILE."""
+    return TILE if n_rows > 0 and nnz < MEAN_BIG_TILE * n_rows else BIG_TILE
+
+
+def coo_row_cap(launch: str, lanes: int) -> int:
+    """RC of the coo_staged_kernel instantiation a launch takes (launch_coo_staged,
+    launch_coo_staged_hot, launch_coo_staged_acc*): the non-temporal carry pass
+    and the single pass pick it by lane count, every other launch has the default."""
+    if launch in ("carry", "single"):
+        return COO_ROW_CAP if lanes == 2 else COO_ROW_CAP_SHORT
+    assert launch in ("xwin", "hot", "acc"), launch
+    return COO_ROW_CAP
+
+
+def first_words(tile: int) -> int:
+    """FW of coo_staged_kernel: 32-bit words of a tile's row-first bitmap."""
+    return (tile + 63) // 64 * 2
+
+
+def bitmap_rows(rc: int, tile: int) -> int:
+    """The widest span the bitmap path takes: its span bitmap and the row-first
+    words then fill s_start[rc + 1] to the last word."""
+    return 32 * (rc + 1 - first_words(tile))
+
+
+def span_edges(rc: int, tile: int) -> tuple:
+    """Both sides of the two lines coo_staged_kernel<..., RC = rc> draws."""
+    return (rc, rc + 1, bitmap_rows(rc, tile), bitmap_rows(rc, tile) + 1)
+
+
+def staged_row_path(span: int, rc: int, tile: int, upper: int | None = None) -> str:
+    upper = bitmap_rows(rc, tile) if upper is None else upper
+    return "heads" if span <= rc else "bitmap" if span <= upper else "search"
+
+
+def staged_lds_words(span: int, n: int, rc: int, tile: int, upper: int | None = None) -> int:
+    """Words of s_start the row phase of a non-accumulate tile of n entries
+    touches (the highest index + 1): the key-change table writes [0, span], the
+    bitmap path ceil(span / 32) span words and behind them two words per 64
+    entries, the search path none."""
+    path = staged_row_path(span, rc, tile, upper)
+    if path == "heads":
+        return span + 1
+    if path == "bitmap":
+        return (span + 31) // 32 + 2 * ((n + 63) // 64)
+    return 0
+
+
+def coo_tile_spans(row: np.ndarray, tile: int) -> np.ndarray:
+    """span of every tile as coo_staged_kernel computes it: rows in (prev, last],
+    row[t1 - 1] - (row[t0 - 1] if t0 else -1), over the row-sorted entries."""
+    nnz = row.size
+    tiles = (nnz + tile - 1) // tile
+    last = row[np.minimum((np.arange(tiles, dtype=np.int64) + 1) * tile, nnz) - 1].astype(np.int64)
+    return last - np.concatenate(([-1], last[:-1]))
+
+
+def coo_tail_plan(row: np.ndarray, tile: int = BIG_TILE) -> np.ndarray:
+    """coo_tail_kernel restated: for every full tile with entries behind it, how
+    many of them continue its last row, counted up to COO_TAIL_CAP + 1."""
+    nnz = row.size
+    tiles = (nnz + tile - 1) // tile
+    out = np.zeros(tiles, np.int64)
+    for t in range(tiles):
+        t1 = (t + 1) * tile
+        if t1 < nnz:
+            other = row[t1:t1 + COO_TAIL_CAP + 1] != row[t1 - 1]
+            out[t] = int(np.argmax(other)) if other.any() else other.size
+    return out
+
+
+def _sorted_rows(lens: np.ndarray) -> np.ndarray:
+    return np.repeat(np.arange(lens.size, dtype=np.int32), lens)
+
+
+def _span_layout(spans, tile, overs, cont, flen, bulk, final):
+    """-> (row lengths, tiles under test, the entries each of their last rows
+    runs into the next tile).  `bulk` tile-aligned filler rows of flen entries
+    (flen divides the tile), then for every S of spans a separator tile of
+    filler and the tile under test: a row of 3 entries at the tile's first
+    entry, S - 2 empty rows, a row that fills the tile and runs `over` entries
+    on; behind the tile of S == cont a second one whose first entries continue
+    that row (first_continues) and which spans S rows after it.  A row that
+    ends on the next filler boundary follows each.  The end: a row of 7 and 37
+    empty rows; final: the 37 empty rows directly behind the last tile under
+    test, which then has no overhang and is the matrix's last tile."""
+    assert tile % flen == 0 and all(s >= 2 for s in spans)
+    per = tile // flen
+    lens, under, ran, pos = [], [], [], 0
+    overs = list(overs)
+
+    def filler(k):
+        nonlocal pos
+        lens.extend([flen] * k)
+        pos += k * flen
+
+    filler((bulk + per - 1) // per * per)
+    for i, S in enumerate(spans):
+        filler(per)
+        assert pos % tile == 0
+        carried = 0
+        for second in ((False, True) if S == cont else (False,)):
+            closing = final and i == len(spans) - 1 and (second or S != cont)
+            over = 0 if closing else overs.pop(0)
+            under.append(pos // tile)
+            ran.append(over)
+            lens.extend([3] + [0] * (S - 2) + [tile - carried - 3 + over])
+            pos += tile - carried + over
+            carried = over
+        if carried:
+            if pos % flen:
+                lens.append(-pos % flen)
+                pos += lens[-1]
+            filler((-pos % tile) // flen)
+    if final:
+        assert pos % tile == 0 and under[-1] == pos // tile - 1
+    lens.extend(([] if final else [7]) + [0] * 37)
+    return np.asarray(lens, np.int64), tuple(under), tuple(ran)
+
+
+CARRY_OVERS = (5, 1, 300, 2, 97)  # entries the last rows of the tiles under test run on: the carries
+
+
+def tail_overs(tail: int) -> tuple:
+    return (tail, 1, tail - 1, 2, 37)
+
+
+@functools.lru_cache(maxsize=2)
+def coo_span_matrix(spans: tuple, tile: int, lanes: int, tail: int | None = None, final: bool = False,
+                    cont: int | None = None, n_cols: int = 2000, seed: int = 41):
+    """-> (matrix, info).  COO tiles of `tile` entries spanning exactly `spans`
+    rows (the span `cont`, by default spans[1], twice: once more behind a
+    continued first row), laid out by _span_layout, with as much filler as
+    puts the mean row where coo_lanes gives `lanes` and, for the carry pass (tail None), where
+    carry_tile gives `tile`; tail: the single pass (always BIG_TILE), whose
+    tiles under test have last rows running up to `tail` entries on.  Asserts
+    the spans, the lanes, the tile and, for the single pass, the tail plan."""
+    single = tail is not None
+    cont = spans[1] if cont is None else cont
+    assert tile in (TILE, BIG_TILE) and (not single or tile == BIG_TILE)
+    if not single and tile == BIG_TILE:
+        assert lanes == 8
+        target, flen = MEAN_BIG_TILE, tile // 2
+    else:
+        target, flen = {8: (MEAN_LANES_8, 256), 4: (MEAN_LANES_4, 128), 2: (None, tile)}[lanes]
+    overs = tail_overs(tail) if single else CARRY_OVERS
+    lens, under, ran = _span_layout(spans, tile, overs, cont, flen, 0, final)
+    if target is not None:  # filler rows until the mean row is 4 % above the target
+        want = 1.04 * target
+        bulk = max(0, int(np.ceil((want * lens.size - lens.sum()) / (flen - want))))
+        lens, under, ran = _span_layout(spans, tile, overs, cont, flen, bulk, final)
+    n_rows, nnz = lens.size, int(lens.sum())
+    row = _sorted_rows(lens)
+    wanted = tuple(s for s in spans for _ in range(2 if s == cont else 1))
+    got = coo_tile_spans(row, tile)
+    assert tuple(int(got[t]) for t in under) == wanted, (got[list(under)], wanted)
+    assert coo_lanes(n_rows, nnz) == lanes, (n_rows, nnz, lanes)
+    second = under[wanted.index(cont) + 1]
+    assert row[second * tile] == row[second * tile - 1]  # first_continues
+    if single:
+        plan = coo_tail_plan(row)
+        assert plan.max() == tail <= COO_TAIL_CAP and tuple(int(plan[t]) for t in under) == ran, (plan.max(), ran)
+    else:
+        assert carry_tile(n_rows, nnz) == tile, (n_rows, nnz, tile)
+        assert all(row[(t + 1) * tile] == row[(t + 1) * tile - 1] for t, o in zip(under, ran) if o)  # carries
+    assert (under[-1] == got.size - 1 and nnz % tile == 0) == final
+    assert nnz <= 2_000_000
+    rng = np.random.default_rng(seed + lanes + tile + (7 if final else 0))
+    m = _freeze(sa.Coo(n_rows, n_cols, row, rng.integers(0, n_cols, nnz).astype(np.int32),
+                       rng.uniform(-1.0, 1.0, nnz), False,
+                       f"COO tiles of {tile} spanning {list(wanted)} rows, {lanes} lanes"
+                       f"{', single pass' if single else ''}{', final' if final else ''}"))
+    return m, dict(spans=wanted, under=under, ran=ran, lanes=lanes, tile=tile, tiles=int(got.size))
+
+
+# name: (the launch whose RC places the spans, lanes, tile, final).  "wide-L4"
+# serves the x-window and the hot-column launch (RC = 1024 at 4 lanes) and,
+# for the bits, the plain carry pass (RC = 250: its bitmap and search paths).
+SPAN_CASES = {
+    "carry-L2": ("carry", 2, TILE, False),
+    "carry-L2-final": ("carry", 2, TILE, True),
+    "carry-L4": ("carry", 4, TILE, False),
+    "carry-L8": ("carry", 8, TILE, False),
+    "carry-L8-big": ("carry", 8, BIG_TILE, False),
+    "wide-L4": ("xwin", 4, TILE, False),
+    "single-L2": ("single", 2, BIG_TILE, False),
+    "single-L2-final": ("single", 2, BIG_TILE, True),
+    "single-L4": ("single", 4, BIG_TILE, False),
+    "single-L8": ("single", 8, BIG_TILE, False),
+}
+
+
+def _case(m: sa.Coo, seed: int):
+    """(integer copy with its int64 reference, (real copy, x, reference, bound))"""
+    mr, x, _ = exact.realize(m, seed=seed + 1)
+    return exact.integerize(m, seed=seed), (mr, x, exact.exact_reference(mr, x), exact.fp64_bound(mr, x))
+
+
+@functools.lru_cache(maxsize=None)
+def coo_span_case(name: str):
+    """-> (info, integer copy, (real copy, x, reference, bound)) of SPAN_CASES[name]:
+    the spans RC, RC + 1, 32 (RC + 1 - FW) and one more (final: the upper bitmap
+    edge last); computed once, shared by the CPU and GPU tests."""
+    launch, lanes, tile, final = SPAN_CASES[name]
+    rc = coo_row_cap(launch, lanes)
+    e = span_edges(rc, tile)
+    spans = (e[1], e[3], e[0], e[2]) if final else e
+    m, info = coo_span_matrix(spans, tile, lanes, COO_TAIL_CAP if launch == "single" else None, final, e[1])
+    return dict(info, rc=rc, launch=launch, edges=e), *_case(m, 300 + sorted(SPAN_CASES).index(name))
+
+
+# --------------------------------------------------- single-pass tails at the cap
+@functools.lru_cache(maxsize=None)
+def coo_tail_matrix(over_cap: bool = False, n_cols: int = 3000):
+    """-> (matrix, tail plan).  1,536-entry tiles 0, 2, 4 and 6 end in rows that
+    run 80 (over_cap: 81), 2, 79 and 1 entries on; the last of them ends on
+    nnz - 1, the lone entry of an odd nnz.  Both forms have the same rows but
+    for the two around the first tile end, and the same columns and values."""
+    tails = [COO_TAIL_CAP + (1 if over_cap else 0), 2, COO_TAIL_CAP - 1, 1]
+    lens = []
+    for i, k in enumerate(tails):
+        lens += [100, 0, 0, BIG_TILE - 100 + k] + ([BIG_TILE - k] if i < len(tails) - 1 else [])
+    lens = np.asarray(lens + [0] * 5, np.int64)
+    row, nnz = _sorted_rows(lens), int(lens.sum())
+    plan = coo_tail_plan(row)
+    assert nnz % 2 == 1 and row[-1] == row[6 * BIG_TILE + BIG_TILE - 1] and nnz == 7 * BIG_TILE + 1
+    assert plan.tolist() == [tails[0], 0, 2, 0, COO_TAIL_CAP - 1, 0, 1, 0]
+    assert coo_lanes(lens.size, nnz) == 8
+    rng = np.random.default_rng(43)
+    return _freeze(sa.Coo(lens.size, n_cols, row, rng.integers(0, n_cols, nnz).astype(np.int32),
+                          rng.uniform(-1.0, 1.0, nnz), False, f"single-pass tails {tails}")), plan
+
+
+@functools.lru_cache(maxsize=None)
+def coo_tail_case(over_cap: bool = False):
+    m, plan = coo_tail_matrix(over_cap)
+    return plan, *_case(m, 350 + int(over_cap))
+
+
+# ------------------------------------------------------ HYB tail: accumulate
+HYB_K = 2
+HYB_SPANS = (COO_ROW_CAP, COO_ROW_CAP + 1, 40_000)  # the accumulate bitmap has no upper line
+
+
+@functools.lru_cache(maxsize=None)
+def hyb_tail_span_matrix(n_cols: int = 2000):
+    """-> (matrix, info).  Every row has HYB_K entries for the ELL part; the
+    entries past them are a _span_layout of 1,536-entry tiles spanning
+    HYB_SPANS rows (1025 twice, once behind a continued first row), with
+    overhangs the single-pass tail plan accepts.  The spans and the tail plan
+    are asserted on sa.hyb_build's own tail_row."""
+    lens_t, under, ran = _span_layout(HYB_SPANS, BIG_TILE, tail_overs(COO_TAIL_CAP), HYB_SPANS[1], BIG_TILE, 0, False)
+    lens = lens_t + HYB_K
+    nnz = int(lens.sum())
+    rng = np.random.default_rng(47)
+    m = _freeze(sa.Coo(lens.size, n_cols, _sorted_rows(lens), rng.integers(0, n_cols, nnz).astype(np.int32),
+                       rng.uniform(-1.0, 1.0, nnz), False, f"HYB tail tiles spanning {list(HYB_SPANS)} rows"))
+    ptr, col, val = sa.csr_from_coo(m)
+    hb = sa.hyb_build(m.n_rows, ptr, col, val, ki=2, K=HYB_K)
+    tr = hb["tail_row"][: hb["tail_nnz"]]
+    assert hb["K"] == HYB_K and hb["tail_nnz"] == lens_t.sum() and np.array_equal(tr, _sorted_rows(lens_t))
+    spans = coo_tile_spans(tr, BIG_TILE)
+    wanted = (HYB_SPANS[0], HYB_SPANS[1], HYB_SPANS[1], HYB_SPANS[2])
+    assert tuple(int(spans[t]) for t in under) == wanted, (spans[list(under)], wanted)
+    plan = coo_tail_plan(tr)
+    assert plan.max() == COO_TAIL_CAP and tuple(int(plan[t]) for t in under) == ran
+    assert coo_row_cap("acc", 4) == HYB_SPANS[0]
+    return m, dict(spans=wanted, under=under, ran=ran, no_tail=np.flatnonzero(lens_t == 0))
+
+
+@functools.lru_cache(maxsize=None)
+def hyb_tail_case():
+    m, info = hyb_tail_span_matrix()
+    return info, *_case(m, 360)
+
+
+# ------------------------------------------------------------ carry runs
+def carry_rows(row: np.ndarray, tile: int) -> np.ndarray:
+    """carry_row of the COO and CSR tile passes over row-sorted entries:
+    carry_row[t] = the row of entry t * tile if it continues the row of entry
+    t * tile - 1, else -1."""
+    tiles = (row.size + tile - 1) // tile
+    cr = np.full(tiles, -1, np.int64)
+    t0 = np.arange(1, tiles, dtype=np.int64) * tile
+    cr[1:] = np.where(row[t0] == row[t0 - 1], row[t0], -1)
+    return cr
+
+
+def runs_of(cr: np.ndarray) -> list:
+    """[(head index, run length)] of the runs of equal carries >= 0: what
+    coo_carry_kernel's head test (r >= 0 && prev != r) starts a sum for."""
+    cr = np.asarray(cr, np.int64)
+    cut = np.flatnonzero(np.diff(cr)) + 1
+    start = np.concatenate(([0], cut))
+    length = np.diff(np.concatenate((start, [cr.size])))
+    return [(int(s), int(n)) for s, n in zip(start, length) if cr[s] >= 0]
+
+
+def carry_runs(row_or_ptr: np.ndarray, tile: int) -> list:
+    """runs_of(carry_rows(...)) from the sorted row ids or from row_ptr."""
+    a = np.asarray(row_or_ptr)
+    row = a if a.dtype == np.int32 else _sorted_rows(np.diff(a))
+    return runs_of(carry_rows(row, tile))
+
+
+def _products(m: sa.Coo, x: np.ndarray):
+    order = np.argsort(m.row, kind="stable")
+    return m.row[order].astype(np.int64), m.val[order] * np.asarray(x)[m.col[order]]
+
+
+def carry_arrays(m: sa.Coo, x: np.ndarray, tile: int):
+    """What the tile pass hands coo_carry_kernel -> (carry_row, carry_val, y):
+    y holds every row's entries of the tile it begins in."""
+    row, prod = _products(m, x)
+    cr = carry_rows(row, tile)
+    tid = np.arange(row.size, dtype=np.int64) // tile
+    carried = row == cr[tid]
+    return (cr, np.bincount(tid[carried], weights=prod[carried], minlength=cr.size),
+            np.bincount(row[~carried], weights=prod[~carried], minlength=m.n_rows))
+
+
+def cmrs_carry_arrays(m: sa.Coo, x: np.ndarray, h: int, tile: int):
+    """cmrs_tiled_kernel's carries restated, k-major: the strip that runs into
+    tile t from an earlier one (no strip starts at t's first entry) leaves
+    carry[k * tiles + t] for every row key k with entries in the tile, up to
+    the next strip's start -> (carry_row, carry_val, y, tiles)."""
+    row, prod = _products(m, x)
+    nnz = row.size
+    tiles = (nnz + tile - 1) // tile
+    n_strips = (m.n_rows + h - 1) // h
+    ptr = np.concatenate(([0], np.cumsum(np.bincount(row, minlength=m.n_rows))))
+    sp = np.concatenate((ptr[: m.n_rows: h], [nnz]))
+    assert sp.size == n_strips + 1
+    t0 = np.arange(tiles, dtype=np.int64) * tile
+    s_lo = np.searchsorted(sp[:n_strips], t0, side="left")  # csr_tile_rows_kernel over strip_ptr
+    has = (s_lo > 0) & (sp[s_lo] > t0)
+    end = np.minimum(sp[s_lo], t0 + tile)
+    j = np.arange(nnz, dtype=np.int64)
+    tid = j // tile
+    carried = has[tid] & (j < end[tid])
+    assert (row[carried] // h == s_lo[tid[carried]] - 1).all()
+    idx = (row % h) * tiles + tid
+    cr = np.full(h * tiles, -1, np.int64)
+    cr[idx[carried]] = row[carried]
+    return (cr, np.bincount(idx[carried], weights=prod[carried], minlength=cr.size),
+            np.bincount(row[~carried], weights=prod[~carried], minlength=m.n_rows), tiles)
+
+
+def carry_model(cr, cv, y, n_tiles: int | None = None, mutate: str | None = None):
+    """coo_carry_kernel in numpy, y updated in place: the head test, a run of
+    up to CARRY_SHORT - 1 tiles added in tile order by the head's thread, a
+    longer one lane-strided over the wave in rounds of CARRY_ROUND tiles and
+    then the xor butterfly.  cr and cv may be longer than n_tiles (what lies
+    behind the arrays).  mutate, one line each:
+      "one_round"  the wave path stops after its first round
+      "short"      no run takes the wave path: a run of exactly 8 is summed as a
+                   short one, and of a longer one only rr[0..7] are read
+      "unbounded"  the loads are not held to n_tiles
+      "first_head" only the first wave-path head of a wave's 64 tiles is served"""
+    assert mutate in (None, "one_round", "short", "unbounded", "first_head")
+    cr, cv = np.asarray(cr, np.int64), np.asarray(cv, np.float64)
+    n = cr.size if n_tiles is None else n_tiles
+    lim = cr.size if mutate == "unbounded" else n
+
+    def load(i):  # the guarded loads: -2 / 0.0 past the limit
+        ok = i < lim
+        ic = np.minimum(i, cr.size - 1)
+        return np.where(ok, cr[ic], -2), np.where(ok, cv[ic], 0.0)
+
+    prev = np.concatenate(([-1], cr[: n - 1]))
+    lane = np.arange(K_WAVE, dtype=np.int64)
+    served = set()  # waves whose ballot loop has run once
+    for t in np.flatnonzero((cr[:n] >= 0) & (prev != cr[:n])):  # the heads, wave by wave in lane order
+        rr, vv = load(t + np.arange(CARRY_SHORT, dtype=np.int64))
+        r = int(rr[0])
+        if rr[CARRY_SHORT - 1] != r or mutate == "short":
+            s = 0.0
+            for k in range(CARRY_SHORT):
+                if rr[k] != r:
+                    break
+                s += vv[k]
+            y[r] += s
+            continue
+        if mutate == "first_head" and t // K_WAVE in served:
+            continue
+        served.add(t // K_WAVE)
+        s, base = np.zeros(K_WAVE), int(t)
+        while True:
+            end = np.zeros(K_WAVE, bool)
+            for u in range(CARRY_ROUND // K_WAVE):
+                q, v = load(base + u * K_WAVE + lane)
+                s = s + np.where(q == r, v, 0.0)
+                end |= q != r
+            if end.any() or mutate == "one_round":
+                break
+            base += CARRY_ROUND
+        off = K_WAVE // 2
+        while off:
+            s = s + s[lane ^ off]
+            off //= 2
+        y[r] += s[t % K_WAVE]
+    return y
+
+
+CARRY_N_COLS_STEP = 7919  # a long row's columns: start + 7919 i mod n_cols, distinct while it is no longer than n_cols
+
+
+@functools.lru_cache(maxsize=None)
+def carry_run_matrix(runs: tuple, tile: int, pad: int = 0, trailing: int = 0):
+    """-> (matrix, info).  One long row per item of runs, an int k or (k,
+    residue, modulus): the row begins 100 entries into a tile behind three rows
+    of 5 entries and has tile * k + 7 entries, so it continues over exactly k
+    tiles; with (residue, modulus) rows of up to 100 entries in front put the
+    run's head (its first continuation tile) at a tile index = residue mod
+    modulus.  pad: entries in such rows before everything; trailing: empty
+    rows behind the last long row, whose run ends on the matrix's last tile.
+    At least 60 empty rows in front of the three short ones place the long
+    rows alternately at row ids = 0 and = 63 mod 64, the last at 63: row keys
+    0 and h - 1 of a CMRS strip for h = 8 and h = 64, each strip beginning in
+    its long row's first tile.  Asserts the runs, the placements and the CMRS
+    carries' k-major runs for both h."""
+    items = [(it, None, None) if isinstance(it, int) else it for it in runs]
+    lens, pos, long_rows = [], 0, []
+
+    def short_rows(n):
+        nonlocal pos
+        while n > 0:
+            lens.append(min(100, n))
+            n -= lens[-1]
+            pos += lens[-1]
+
+    short_rows(pad)
+    for i, (k, res, mod) in enumerate(items):
+        T = (pos + 15 - 100 + tile - 1) // tile if pos + 15 > 100 else 0
+        while mod is not None and (T + 1) % mod != res:
+            T += 1
+        short_rows(T * tile + 100 - 15 - pos)
+        key = 63 if i % 2 or i == len(items) - 1 else 0
+        lens.extend([0] * (60 + (key - (len(lens) + 63)) % 64) + [5, 5, 5])
+        assert len(lens) % 64 == key
+        pos += 15
+        assert pos == T * tile + 100
+        long_rows.append((len(lens), k, T + 1))
+        lens.append(tile * k + 7)
+        pos += lens[-1]
+    lens = np.asarray(lens + [0] * trailing, np.int64)
+    n_rows, nnz = lens.size, int(lens.sum())
+    row = _sorted_rows(lens)
+    found = carry_runs(row, tile)
+    tiles = (nnz + tile - 1) // tile
+    for (r, k, head), (_, res, mod) in zip(long_rows, items):
+        assert (head, k) in found and (mod is None or head % mod == res), (r, k, head)
+    heads = [hd for _, k, hd in long_rows if k >= CARRY_SHORT]
+    assert any(a // K_WAVE == b // K_WAVE for a, b in zip(heads, heads[1:]))  # two wave-path heads in one wave
+    assert any(hd % K_WAVE == K_WAVE - 1 for hd in heads) and any(hd % K_BLOCK == K_BLOCK - 1 for hd in heads)
+    assert found[-1] == (long_rows[-1][2], long_rows[-1][1]) and sum(found[-1]) == tiles  # ends on the last tile
+    assert carry_tile(n_rows, nnz) == tile, (n_rows, nnz, tile)
+    n_cols = int(lens.max()) + 12_345
+    n_cols += n_cols % CARRY_N_COLS_STEP == 0
+    rng = np.random.default_rng(53 + tile)
+    col = rng.integers(0, n_cols, nnz).astype(np.int32)
+    ptr = np.concatenate(([0], np.cumsum(lens)))
+    for r, _, _ in long_rows:
+        col[ptr[r]:ptr[r + 1]] = (rng.integers(0, n_cols) + CARRY_N_COLS_STEP * np.arange(lens[r])) % n_cols
+        assert np.unique(col[ptr[r]:ptr[r + 1]]).size == min(lens[r], n_cols)
+    assert np.bincount(col).max() < lens.max()
+    m = _freeze(sa.Coo(n_rows, n_cols, row, col, rng.uniform(-1.0, 1.0, nnz), False,
+                       f"rows over {[k for _, k, _ in long_rows]} continuation tiles of {tile}"))
+    for h in (8, 64):  # the same runs k-major, one in the last segment ending on the array's last element
+        cr, _, _, tl = cmrs_carry_arrays(m, np.ones(n_cols), h, tile)
+        assert tl == tiles and cr.size == h * tiles
+        kruns = runs_of(cr)
+        for r, k, head in long_rows:
+            assert ((r % h) * tiles + head, k) in kruns and r % h in (0, h - 1), (h, r, k)
+        assert sum(kruns[-1]) == cr.size and kruns[-1][1] == long_rows[-1][1]
+    return m, dict(runs=found, long_rows=tuple(long_rows), tiles=tiles, tile=tile)
+
+
+CARRY_RUNS = {
+    TILE: (1, 7, (8, 0, K_WAVE), 9, (CARRY_ROUND - 1, K_WAVE - 1, K_WAVE), (CARRY_ROUND, K_BLOCK - 1, K_BLOCK),
+           CARRY_ROUND + 1, 2 * CARRY_ROUND - 1, 2 * CARRY_ROUND, 2 * CARRY_ROUND + 1),
+    BIG_TILE: (7, (8, 0, K_WAVE), 9, (CARRY_ROUND - 1, K_WAVE - 1, K_WAVE), (CARRY_ROUND, K_BLOCK - 1, K_BLOCK),
+               CARRY_ROUND + 1),
+}
+CARRY_TRAILING = {TILE: 20_000, BIG_TILE: 0}  # empty rows: a mean row below / above 96 entries
+
+
+@functools.lru_cache(maxsize=None)
+def carry_case(tile: int):
+    """-> (info, integer copy, (real copy, x, reference, bound)) of
+    carry_run_matrix(CARRY_RUNS[tile], tile, 33, CARRY_TRAILING[tile])."""
+    m, info = carry_run_matrix(CARRY_RUNS[tile], tile, 33, CARRY_TRAILING[tile])
+    return info, *_case(m, 370 + tile)
+
+
+# ------------------------------------------------------------- x windows
+def tile_windows(col_sorted: np.ndarray, tile: int) -> np.ndarray:
+    """tile_window_kernel restated: columns spanned by every tile of the
+    row-sorted entries (max - min + 1)."""
+    cut = np.arange(0, col_sorted.size, tile)
+    return (np.maximum.reduceat(col_sorted, cut).astype(np.int64) - np.minimum.reduceat(col_sorted, cut) + 1)
+
+
+WINDOW_BASE = 1000  # the column every window of the two matrices below contains
+
+
+def _window_cols(rng, n, kind):
+    """n columns of one tile / strip run: "cap" spans XWIN_CAP columns, "over"
+    one more, "one" a single column, else 100; the first and last columns of
+    the range both occur."""
+    width = {"cap": XWIN_CAP, "over": XWIN_CAP + 1, "one": 1}.get(kind, 100)
+    c = WINDOW_BASE + rng.integers(0, width, n)
+    c[n // 2], c[n // 2 + 1] = WINDOW_BASE, WINDOW_BASE + width - 1
+    return c
+
+
+WINDOW_KINDS = ("", "", "cap", "", "over", "", "one", "", "")  # per tile / strip run; the last one is short
+
+
+@functools.lru_cache(maxsize=None)
+def coo_window_matrix(n_cols: int = 5000):
+    """-> (matrix, window spans).  Rows of 80 entries (a mean row below 96:
+    512-entry tiles, with carries); tile 2's columns span exactly 2048, tile
+    4's 2049, tile 6's one column, the others 100."""
+    rng = np.random.default_rng(59)
+    nnz = (len(WINDOW_KINDS) - 1) * TILE + 37
+    lens = np.asarray([80] * (nnz // 80) + [nnz % 80], np.int64)
+    col = np.concatenate([_window_cols(rng, min(TILE, nnz - t * TILE), kind) for t, kind in enumerate(WINDOW_KINDS)])
+    m = _freeze(sa.Coo(lens.size, n_cols, _sorted_rows(lens), col.astype(np.int32), rng.uniform(-1.0, 1.0, nnz),
+                       False, "COO x windows of 2048, 2049 and 1 columns"))
+    assert carry_tile(m.n_rows, nnz) == TILE and coo_lanes(m.n_rows, nnz) == 8
+    spans = tile_windows(sa.coo_sort_by_row(m)[1], TILE)
+    assert spans.tolist() == [{"cap": XWIN_CAP, "over": XWIN_CAP + 1, "one": 1}.get(k, 100) for k in WINDOW_KINDS]
+    assert len(carry_runs(m.row, TILE)) >= 4
+    return m, spans
+
+
+def cmrs_geometry(n_rows: int, nnz: int, h: int) -> tuple:
+    """staged.hip cmrs_geometry -> (L, G): lanes per row, strips per workgroup."""
+    L = sa.hip_lib().spmv_csr_auto_lanes(n_rows, nnz)
+    while L > 1 and L * h > K_BLOCK:
+        L //= 2
+    return L, max(K_BLOCK // (L * h), 1)
+
+
+def cmrs_windows(ptr: np.ndarray, col: np.ndarray, h: int, G: int) -> np.ndarray:
+    """cmrs_window_kernel restated: columns spanned by the entries a run of G
+    strips loads, from two before its 32-aligned first entry to one past its
+    last (0 for a run without entries)."""
+    n_rows, nnz = ptr.size - 1, int(ptr[-1])
+    sp = np.concatenate((ptr[:n_rows:h], [nnz]))
+    n_strips = sp.size - 1
+    out = []
+    for s0 in range(0, n_strips, G):
+        b, e = int(sp[s0]), int(sp[min(s0 + G, n_strips)])
+        c = col[max((b & ~31) - 2, 0):min(e + 1, nnz)] if b < e else col[:0]
+        out.append(int(c.max()) - int(c.min()) + 1 if c.size else 0)
+    return np.asarray(out, np.int64)
+
+
+CMRS_WINDOW_H = 8
+
+
+@functools.lru_cache(maxsize=None)
+def cmrs_window_matrix(n_cols: int = 5000):
+    """-> (matrix, window spans, G).  Rows of 15 entries behind a first row of
+    22, so a strip run's first entry is not 32-aligned and its window reaches
+    back into the run before; those entries and the one behind each run hold
+    WINDOW_BASE, which every run's range contains.  Run 2 spans exactly 2048
+    columns, run 4 2049, run 6 one column, the others 100; the last run is
+    short."""
+    h = CMRS_WINDOW_H
+    L, G = cmrs_geometry(1000, 15_000, h)
+    n_rows = (len(WINDOW_KINDS) - 1) * G * h + 5
+    lens = np.full(n_rows, 15, np.int64)
+    lens[0] = 22
+    nnz = int(lens.sum())
+    assert cmrs_geometry(n_rows, nnz, h) == (L, G)
+    ptr0 = np.concatenate(([0], np.cumsum(lens)))
+    cut = ptr0[np.minimum(np.arange(len(WINDOW_KINDS) + 1) * G * h, n_rows)]  # the strip runs' entry ranges
+    rng = np.random.default_rng(61)
+    col = np.concatenate([_window_cols(rng, int(cut[w + 1] - cut[w]), kind) for w, kind in enumerate(WINDOW_KINDS)])
+    for b, e in zip(cut[:-1], cut[1:]):
+        col[max((b & ~31) - 2, 0):b] = WINDOW_BASE
+        if e < nnz:
+            col[e] = WINDOW_BASE
+    m = _freeze(sa.Coo(n_rows, n_cols, _sorted_rows(lens), col.astype(np.int32), rng.uniform(-1.0, 1.0, nnz), False,
+                       "CMRS x windows of 2048, 2049 and 1 columns"))
+    ptr, ccol, _ = sa.csr_from_coo(m)
+    spans = cmrs_windows(np.asarray(ptr, np.int64), ccol, h, G)
+    assert np.array_equal(ptr, ptr0) and (cut[1:-1] % 32 != 0).all()
+    assert spans.tolist() == [{"cap": XWIN_CAP, "over": XWIN_CAP + 1, "one": 1}.get(k, 100) for k in WINDOW_KINDS]
+    return m, spans, G
+
+
+@functools.lru_cache(maxsize=None)
+def window_case(fmt: str):
+    m, spans = (coo_window_matrix() if fmt == "coo" else cmrs_window_matrix()[:2])
+    return spans, *_case(m, 380 + len(fmt))
