@@ -336,7 +336,10 @@ int spmv_plan_get_multi_info(const spmv_plan *p, spmv_multi_info *info);
  *     a plan that was not prepared, NULL x with rows present, NULL y with
  *     columns present.
  * The transposed run reads the caller's row_ptr, col and val (never the
- * plan's hot-renumbered column copy).  spmv_plan_get_info and its
+ * plan's hot-renumbered column copy).  In scatter mode an entry whose column
+ * lies outside [0, n_cols) is dropped (the recorded column ranges leave it
+ * out and every add is bounds-checked); copy mode refuses such a matrix at
+ * build time with SPMV_OTHER_ERROR.  spmv_plan_get_info and its
  * owned_bytes do not change: the transposed path reports its own bytes in
  * spmv_transpose_info.                                                     */
 enum spmv_transpose_mode { SPMV_T_NONE = 0, SPMV_T_SCATTER = 1, SPMV_T_COPY = 2 };

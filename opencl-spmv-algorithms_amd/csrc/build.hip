@@ -29,15 +29,20 @@
 namespace spmv {
 
 // ------------------------------------------------------------------ CSR
+// The sort keys.  An index outside [0, n_rows) sets *bad and gets key 0:
+// row_ptr_from_sorted_kernel writes row_ptr[r] for every r up to the largest
+// key, so no key may reach past the n_rows + 1 offsets before the builder
+// returns its error.
 __global__ void coo_rows_check_kernel(int64_t nnz, int64_t n_rows, const int32_t *__restrict__ row,
                                       uint32_t *__restrict__ keys, int *__restrict__ bad)
 {
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nnz; i += stride) {
         const int32_t r = row[i];
-        if (r < 0 || r >= n_rows)
+        const bool out = r < 0 || r >= n_rows;
+        if (out)
             *bad = 1;
-        keys[i] = (uint32_t)(r < 0 ? 0 : r);
+        keys[i] = out ? 0u : (uint32_t)r;
     }
 }
 

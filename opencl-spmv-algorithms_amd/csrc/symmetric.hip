@@ -81,8 +81,12 @@ __global__ __launch_bounds__(kBlock) void csr_sym_range_kernel(int64_t n, int64_
 // cant-like row), so their row products would meet at few accumulator words
 // and the LDS adds of one instruction would run one after another.  Each run
 // of equal keys (lanes in entry order; -1: nothing to add) is summed across
-// the wave by a segmented scan and its last lane alone adds the sum.  Called
-// in uniform control flow (every lane of the wave active).
+// the wave by a segmented scan and its last lane alone adds the sum.  The
+// scan compares a lane's key with the key `off` lanes below only, so equal
+// keys must be contiguous: a lane with nothing to add inside a row keeps the
+// row's key and passes p = 0.0; -1 is for the lanes past the stream's end,
+// the wave's last.  Called in uniform control flow (every lane of the wave
+// active).
 __device__ __forceinline__ void wave_run_add(double *acc, int key, double p)
 {
     const int lane = (int)threadIdx.x % kWave;
@@ -107,7 +111,8 @@ __device__ __forceinline__ void wave_run_add(double *acc, int key, double p)
 // x[c] comes from global memory, the mirrored product goes straight into
 // y[c]; bound = n, a column outside [0, n) is dropped whole.
 // The row products of a wave's 64 consecutive entries are summed per row
-// across the wave before they reach the accumulator (wave_run_add).
+// across the wave before they reach the accumulator (wave_run_add); a dropped
+// entry stays in its row's run with a product of 0.0, as in sym_multi_add.
 template <bool WIN>
 __device__ __forceinline__ void sym_block(const int64_t *s_ptr, int nr, int64_t r0, const int32_t *__restrict__ col,
                                           const double *__restrict__ val, const double *__restrict__ x,
@@ -121,18 +126,22 @@ __device__ __forceinline__ void sym_block(const int64_t *s_ptr, int nr, int64_t 
         if constexpr (WIN) {
             const uint32_t jr = (uint32_t)(r0 + r) - (uint32_t)lo;
             const uint32_t jc = (uint32_t)c - (uint32_t)lo;
-            if (live && jr < bound && jc < bound) {
+            if (live && jr < bound) {
                 key = (int)jr;
-                p = v * xs[jc];
-                if (jc != jr)
-                    atomicAdd(&acc[jc], v * xs[jr]);
+                if (jc < bound) {
+                    p = v * xs[jc];
+                    if (jc != jr)
+                        atomicAdd(&acc[jc], v * xs[jr]);
+                }
             }
         } else {
-            if (live && (uint32_t)c < bound) {
+            if (live) {
                 key = r;
-                p = v * x[c];
-                if ((int64_t)c != r0 + r)
-                    unsafeAtomicAdd(&y[c], v * xs[r]);
+                if ((uint32_t)c < bound) {
+                    p = v * x[c];
+                    if ((int64_t)c != r0 + r)
+                        unsafeAtomicAdd(&y[c], v * xs[r]);
+                }
             }
         }
         wave_run_add(acc, key, p);

@@ -39,13 +39,25 @@ namespace spmv {
 
 constexpr int32_t kTCap = 2048;   // LDS accumulator entries per workgroup (16 KiB)
 
-// column range {lo, hi} of every block of kRbRows rows ({0, -1}: no entries)
-__global__ __launch_bounds__(kBlock) void csr_t_range_kernel(int64_t n_rows, const int64_t *__restrict__ ptr,
+// Column range {lo, hi} of every block of kRbRows rows ({0, -1}: no entry
+// inside [0, n_cols)).  A column outside [0, n_cols) is left out here, as in
+// csr_sym_range_kernel: the flush adds acc[0 .. span) to y[lo .. hi], so the
+// recorded range must lie inside y; the run's bound checks then drop the entry.
+__global__ __launch_bounds__(kBlock) void csr_t_range_kernel(int64_t n_rows, int64_t n_cols,
+                                                             const int64_t *__restrict__ ptr,
                                                              const int32_t *__restrict__ col, int2 *__restrict__ win)
 {
     const int64_t r0 = (int64_t)blockIdx.x * kRbRows;
     const int64_t r1 = r0 + kRbRows < n_rows ? r0 + kRbRows : n_rows;
-    const int2 r = block_col_range(col, ptr[r0], ptr[r1]);
+    int lo = INT32_MAX, hi = INT32_MIN;
+    for (int64_t e = ptr[r0] + threadIdx.x, e1 = ptr[r1]; e < e1; e += kBlock) {
+        const int c = col[e];
+        if (c >= 0 && c < n_cols) {
+            lo = c < lo ? c : lo;
+            hi = c > hi ? c : hi;
+        }
+    }
+    const int2 r = block_minmax(lo, hi);
     if (threadIdx.x == 0)
         win[blockIdx.x] = r;
 }
@@ -273,8 +285,8 @@ int prepare_scatter(spmv_plan *p)
     int rc = t_alloc(&t, &t.win, (size_t)blocks * sizeof(int2));
     if (rc != SPMV_SUCCESS)
         return rc;
-    hipLaunchKernelGGL(csr_t_range_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, st, d.n_rows, p->ptr, p->col,
-                       (int2 *)t.win);
+    hipLaunchKernelGGL(csr_t_range_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, st, d.n_rows, d.n_cols, p->ptr,
+                       p->col, (int2 *)t.win);
     SPMV_CHECK_LAUNCH("csr_t_range_kernel");
     int2 *h = nullptr;
     if ((rc = windows_download(t.win, blocks, st, &h, "spmv_plan_prepare_transpose")) != SPMV_SUCCESS)

@@ -20,6 +20,16 @@ carry arrays of carry_run_matrix, plain and k-major, and four one-line
 mutations of it do not; a word count of coo_staged_kernel's three row paths
 stays inside s_start[RC + 1] at every span under test and leaves it when the
 bitmap path's upper line moves one row up.
+
+The row-block core (rowblock.h, transpose.hip, symmetric.hip), at the end of
+the file: its constants, window rules, width rule and LDS sizes are held
+against the sources in the same test; the stream, cap and dropped families
+deliver their entry counts, layouts, spans and placements; a numpy model of
+rb_row_of equals np.searchsorted on every block and four one-line mutations of
+it do not; a numpy model of wave_run_add gives every row its sum on the valid
+families under both key rules, and on the dropped family only with the rule
+that keeps a dropped entry in its row's run: the earlier rule (key -1) gives
+the probe row 29 products instead of 19.
 """
 from __future__ import annotations
 
@@ -181,8 +191,36 @@ def test_restated_constants_match_the_sources():
     csrc/: the plan reports no COO lanes, tile or row cap, so nothing else
     would notice a restatement gone stale."""
     src = Path(sa.__file__).resolve().parent / "csrc"
-    text = {f: (src / f).read_text() for f in ("staged.hip", "coo.hip", "common.h", "sell.hip")}
+    text = {f: (src / f).read_text() for f in ("staged.hip", "coo.hip", "common.h", "sell.hip", "rowblock.h",
+                                                 "transpose.hip", "symmetric.hip")}
+    width_rule = "const int w = live > 4 ? 3 : live > 2 ? 2 : live - 1;"
     lines = {
+        "rowblock.h": [
+            f"constexpr int kRbRows = {th.RB_ROWS};", "constexpr int kRbPtr = kRbRows + 2;",
+            f"constexpr int kRbU = {th.RB_U};", "constexpr int kTWidths[4] = {" + ", ".join(map(str, th.T_WIDTHS)) + "};",
+            # rb_row_of: seven guarded steps; rb_stream: the two loop forms and their tails
+            "for (int step = kRbRows / 2; step > 0; step >>= 1)", "if (r + step < nr && s_ptr[r + step] <= e)",
+            "for (; e0 + kRbU * kBlock <= end; e0 += kRbU * kBlock) {", "for (; e0 < end; e0 += kBlock) {",
+            "for (; e + (kRbU - 1) * kBlock < end; e += kRbU * kBlock) {", "for (; e < end; e += kBlock)",
+            "for (int i = (int)threadIdx.x; i <= b->nr; i += kBlock)",
+        ],
+        "transpose.hip": [
+            f"constexpr int32_t kTCap = {th.T_CAP};", f"#define SPMV_T_MULTI_CAP {th.T_MULTI_CAP}", width_rule,
+            "return (size_t)(kRbPtr + kRbRows * kv + span * kv) * sizeof(double);",
+            "if (c >= 0 && c < n_cols) {",  # csr_t_range_kernel: the range of the columns inside [0, n_cols)
+            "const bool lds = b.span <= cap;", "const bool lds = span <= cap;",
+            "const WindowTally multi = windows_tally(h, blocks, kTMultiCap / kTWidths[w]);",
+        ],
+        "symmetric.hip": [
+            f"constexpr int32_t kSCap = {th.S_CAP};", f"#define SPMV_S_MULTI_CAP {th.S_MULTI_CAP}", width_rule,
+            "return (size_t)(kRbPtr + 2 * (span > kRbRows ? span : kRbRows) * kv) * sizeof(double);",
+            # csr_sym_range_kernel: the columns inside [0, n), joined with the block's rows
+            "if (c >= 0 && c < n) {", "r.x = r0 < r.x ? (int)r0 : r.x;", "r.y = r1 - 1 > r.y ? (int)(r1 - 1) : r.y;",
+            "const int32_t cap = kSMultiCap / kTWidths[w];", "const bool window = span <= cap;",
+            # wave_run_add: the scan and the run's last lane
+            "for (int off = 1; off < kWave; off <<= 1) {", "if (lane >= off && k == key)",
+            "if (key >= 0 && (lane == kWave - 1 || next != key))",
+        ],
         "common.h": [f"constexpr int kWave = {th.K_WAVE};", f"constexpr int kBlock = {th.K_BLOCK};",
                      f"constexpr int32_t kStagedXwinCap = {th.XWIN_CAP};"],
         "sell.hip": [f"constexpr int kSellFixThreads = {th.FIX_THREADS};", f"int64_t lo = c + 1, step = {th.FIX_STEP};"],
@@ -238,6 +276,13 @@ def test_restated_constants_match_the_sources():
     assert [th.coo_row_cap(la, 4) for la in ("xwin", "hot", "acc")] == [1024] * 3
     assert [th.coo_lanes(1000, n) for n in (11_999, 12_000, 47_999, 48_000)] == [2, 4, 4, 8]
     assert [th.carry_tile(1000, n) for n in (95_999, 96_000)] == [512, 1536]
+    # the row-block core
+    assert th.RB_STEP == 1024 and th.RB_PTR == 130 and 1 << th.RB_SEARCH_STEPS == th.RB_ROWS
+    assert [th.pass_widths(k) for k in (1, 2, 3, 4, 5, 8, 9)] == [
+        [(1, 1)], [(2, 2)], [(3, 4)], [(4, 4)], [(5, 8)], [(8, 8)], [(8, 8), (1, 1)]]
+    assert th.pass_widths(17) == [(8, 8), (8, 8), (1, 1)]
+    assert th.t_multi_lds(1, 8192) == 67_600 and th.sym_multi_lds(1, 4096) == 66_576  # both above 64 KiB
+    assert th.sym_multi_lds(8, 3) == th.sym_multi_lds(8, 128) == (130 + 2 * 128 * 8) * 8  # the wide path's arrays
 
 
 # ---------------------------------------------------- COO tiles by their span
@@ -454,3 +499,253 @@ def test_references_are_shared():
         b = make()
         assert make()[1] is b[1] and make()[2][2] is b[2][2]
         assert not b[1].ref.flags.writeable and not b[1].m.val.flags.writeable and not b[2][0].val.flags.writeable
+
+
+# ======================================================= the row-block core
+# rowblock.h and its eight users (transpose.hip, symmetric.hip): the stream,
+# cap and dropped families of tests/thresholds.py deliver what they promise;
+# numpy models of rb_row_of and wave_run_add give the reference on them, and
+# their one-line mutations (and wave_run_add's earlier key rule) do not.
+STREAMS = [(nr, lower) for nr in th.RB_LAST_ROWS for lower in (False, True)]
+STREAM_IDS = [f"nr{nr}-{'lower' if lower else 'rect'}" for nr, lower in STREAMS]
+
+
+@pytest.mark.parametrize("last_nr,lower", STREAMS, ids=STREAM_IDS)
+def test_rowblock_stream_matrix_delivers_its_blocks(last_nr, lower):
+    m, info = th.rowblock_stream_matrix(last_nr, lower)
+    ptr = th.csr_of(m)[0]
+    assert np.array_equal(ptr, sa.csr_from_coo(m)[0])
+    assert m.n_rows % th.RB_ROWS == last_nr and (m.n_rows == m.n_cols) == lower
+    counts = sorted(E for _, E, _ in info["under"])
+    assert counts == sorted(2 * th.RB_ENTRY_COUNTS)
+    both_sides = lambda line: {line - 1, line, line + 1} <= set(counts)  # noqa: E731
+    assert both_sides(th.K_BLOCK) and both_sides(th.RB_STEP) and both_sides(2 * th.RB_STEP)
+    assert {th.RB_STEP + th.K_BLOCK - 1, th.RB_STEP + th.K_BLOCK, 5 * th.RB_STEP + 1} <= set(counts)
+    for E in th.RB_ENTRY_COUNTS:  # two different layouts per count
+        assert len({la for _, e, la in info["under"] if e == E}) == 2
+    lens = np.diff(ptr)
+    for (b, E, layout), s0 in zip(info["under"], info["starts"]):
+        r0 = b * th.RB_ROWS
+        mine = lens[r0:r0 + th.RB_ROWS]
+        ends = (ptr[r0 + 1:r0 + th.RB_ROWS + 1] - s0)[mine > 0]  # where rows end, from the block's first entry
+        if layout == "first":
+            assert mine[0] == E and mine[1:].sum() == 0
+        elif layout == "last":
+            assert mine[-1] == E and mine[:-1].sum() == 0
+        elif layout == "middle":
+            assert mine[77] == E and mine.sum() == E
+        elif layout == "singles":
+            assert (mine[: min(E, 127)] == 1).all()
+        elif layout == "wave" and E >= 1023:  # a row ends one lane before a wave's last, on it and one past it
+            assert {62, 63, 0} <= set(((ends - 1) % th.K_WAVE).tolist())
+            assert set(mine[mine > 0][:-1].tolist()) == {63, 64, 65}
+        elif layout == "long" and E >= th.RB_LONG_ROW:  # the long row holds a whole unrolled step of the stream
+            a, z = ptr[r0 + 5] - s0, ptr[r0 + 6] - s0
+            assert z - a == th.RB_LONG_ROW and a % th.RB_STEP == 0 and a + th.RB_STEP < z
+        elif layout == "runs":
+            assert mine[:40].sum() == 0 and mine[-40:].sum() == 0 and (mine[40:-40] > 0).sum() == min(E, 48)
+    assert any(la == "wave" and E >= 1023 for _, E, la in info["under"])
+    # the windows: the rules once more by a plain loop, and narrow
+    win = info["windows"]
+    for b in range(win.shape[0]):
+        r0, r1 = b * th.RB_ROWS, min((b + 1) * th.RB_ROWS, m.n_rows)
+        c = m.col[ptr[r0]:ptr[r1]]
+        if c.size == 0:
+            assert tuple(win[b]) == (0, -1) and (b in info["empty"])
+        elif lower:
+            assert tuple(win[b]) == (min(int(c.min()), r0), max(int(c.max()), r1 - 1))
+        else:
+            assert tuple(win[b]) == (int(c.min()), int(c.max()))
+    assert (win[:, 1] - win[:, 0] + 1).max() < 512
+    assert th.rowblock_stream_matrix(last_nr, lower)[0] is m and not m.val.flags.writeable  # made once, read-only
+
+
+def test_rowblock_cap_matrices_deliver_their_spans():
+    m, info = th.rowblock_cap_matrix()
+    assert sorted(s for _, s in info["under"]) == [1024, 1025, 2048, 2049, 4096, 4097, 8192, 8193] == sorted(th.T_CAP_SPANS)
+    e = info["expect"]
+    span = info["windows"][:, 1] - info["windows"][:, 0] + 1
+    assert e["lds_blocks"] == int(((span > 0) & (span <= 2048)).sum()) == 4 and e["flush_entries"] == 1024 + 1025 + 2048 + 9
+    for w, cap in zip(th.T_WIDTHS, (8192, 4096, 2048, 1024)):
+        assert e["multi_lds_blocks"][th.T_WIDTHS.index(w)] == int(((span > 0) & (span <= cap)).sum())
+        assert {cap, cap + 1} <= set(span.tolist())  # both sides of the cap of every width
+    assert np.bincount(m.col).max() >= 4  # overlapping windows: a column is hit from several blocks
+    s, sinfo = th.rowblock_sym_cap_matrix()
+    assert sorted(sp for _, sp, kind in sinfo["under"] if kind == "lower") == sorted(th.S_CAP_SPANS)
+    assert sorted(sp for _, sp, kind in sinfo["under"] if kind == "upper") == sorted(th.S_CAP_SPANS)
+    assert th.S_CAP_SPANS == (512, 513, 1024, 1025, 2048, 2049, 4096, 4097) and s.n_rows == 6221
+    se = sinfo["expect"]
+    sspan = sinfo["windows"][:, 1] - sinfo["windows"][:, 0] + 1
+    rows = np.minimum(th.RB_ROWS, s.n_rows - th.RB_ROWS * np.arange(sspan.size))
+    for i, cap in enumerate((4096, 2048, 1024, 512)):
+        fit, wide = (sspan > 0) & (sspan <= cap), sspan > cap
+        assert se["multi_window_blocks"][i] == int(fit.sum()) and wide.sum() == 2 * (2 * i + 1)
+        assert se["multi_flush_entries"][i] == int(sspan[fit].sum() + rows[wide].sum())
+    assert (se["window_blocks"], se["flush_entries"]) == (se["multi_window_blocks"][1], se["multi_flush_entries"][1])
+    assert sspan[-1] == th.S_CAP_LAST_ROWS == rows[-1]  # the last block: the span equals nr
+    # the expansion is what the half describes: every off-diagonal entry once more
+    ex = sa.expand_symmetric(s)
+    assert ex.nnz == 2 * s.nnz - int((s.row == s.col).sum())
+
+
+def test_rowblock_cases_fit_the_integer_check():
+    """The integer copies fit exact.integerize's budget: |value| < 2^a, |x| <
+    2^b with a + b + ceil(log2(longest row or column + 1)) <= 52 on the matrix
+    (transposed) or on its expansion (symmetric).  The densest column of the
+    cap family is hit from many blocks; the stream family's longest row is the
+    5,121-entry block in one row."""
+    for nr, lower in STREAMS:
+        info, t, s = th.stream_case(nr, lower)
+        assert (t["a"], t["b"]) == (19, 20) and (s is None) == (not lower)  # c = 13: 5,121 entries in one row
+        assert t["ref_i"].shape == (t["mi"].n_cols, th.RB_KMAX) and not t["ref_i"].flags.writeable
+        if s is not None:
+            assert s["a"] + s["b"] + 13 <= 52 and s["ref_i"].shape == (s["mi"].n_rows, th.RB_KMAX)
+    _, t = th.cap_case()
+    densest = int(np.bincount(t["mi"].col).max())
+    assert densest >= 4 and t["a"] + t["b"] + math.ceil(math.log2(max(densest, 65) + 1)) <= 52
+    _, s = th.sym_cap_case()
+    ex = sa.expand_symmetric(s["mi"])
+    longest = int(np.bincount(ex.row).max())
+    # a row of the 4,097-column window: its diagonal and 31 or 32 of the 3,969 far columns, mirrored entries besides
+    assert longest >= 32 and s["a"] + s["b"] + math.ceil(math.log2(longest + 1)) <= 52 and s["a"] >= 20
+    assert th.cap_case()[1] is t and th.sym_cap_case()[1] is s  # computed once
+
+
+# ------------------------------------------------------- rb_row_of, modelled
+def _row_search(m, mutate=None, lanes="uniform"):
+    """-> (entries whose modelled row differs from searchsorted, of them the
+    ones that are lanes past the block's end, the rows the model gave them)."""
+    ptr = th.csr_of(m)[0]
+    wrong = past = 0
+    rows = []
+    for b in range(th.rb_blocks(m.n_rows)):
+        r0, nr = b * th.RB_ROWS, min(th.RB_ROWS, m.n_rows - b * th.RB_ROWS)
+        s_ptr = ptr[r0:r0 + nr + 1]
+        if s_ptr[0] == s_ptr[nr]:
+            continue
+        e = th.uniform_lanes(int(s_ptr[0]), int(s_ptr[nr])).ravel()
+        want = np.searchsorted(s_ptr[:nr], e, side="right") - 1
+        got = th.rb_row_of(s_ptr, nr, e, mutate)
+        bad = got != want
+        wrong += int(bad.sum())
+        past += int((bad & (e >= s_ptr[nr])).sum())
+        rows += [(nr, int(g)) for g in np.unique(got[bad])]
+    return wrong, past, rows
+
+
+@pytest.mark.parametrize("last_nr,lower", STREAMS, ids=STREAM_IDS)
+def test_row_search_model_gives_the_row(last_nr, lower):
+    """The seven guarded steps equal np.searchsorted(s_ptr[:nr], e, "right") - 1
+    for every entry id a block's stream hands out, the ids past the block's end
+    in its last partial step included (sym_block searches for those too)."""
+    m = th.rowblock_stream_matrix(last_nr, lower)[0]
+    assert _row_search(m)[0] == 0
+
+
+def test_row_search_mutations_fail_here():
+    """Each one-line mutation gives a wrong row on these matrices:
+      <= to <         the first entry of every row that follows an entry
+      six steps       without step 64 the rows from 64 on ("last", "middle",
+                      "singles"); without step 1 the odd rows
+      r + step <= nr  s_ptr[nr] is the block's end, above every entry, and in a
+                      full block no step reaches r + step = 128: the mutation
+                      can only move the lanes past the end of the SHORT last
+                      block (1, 2 and 127 rows), to row nr, one past the block.
+                      sym_block searches for those lanes and then ignores them,
+                      so the guard protects no result today; the model keeps
+                      the three last blocks able to see it."""
+    totals = {}
+    for nr, lower in STREAMS:
+        m = th.rowblock_stream_matrix(nr, lower)[0]
+        for mutate in ("less", "guard", "six_front", "six_back"):
+            wrong, past, rows = _row_search(m, mutate)
+            assert wrong > 0, (mutate, nr, lower)
+            totals[mutate] = totals.get(mutate, 0) + wrong
+            if mutate == "guard":
+                assert wrong == past and all(got == n for n, got in rows)
+                assert {n for n, _ in rows} == {nr}  # the short last block alone
+            elif mutate == "six_front":
+                assert past < wrong
+    assert min(totals.values()) > 100
+
+
+# ---------------------------------------------------- wave_run_add, modelled
+def _row_counts(m):
+    """x = 1, every value 1: a row's sum is the number of its entries inside [0, n)."""
+    ptr, col, _ = th.csr_of(m)
+    ok = (col >= 0) & (col < m.n_cols)
+    return ptr, col, ok.astype(np.float64), np.bincount(m.row[ok], minlength=m.n_rows).astype(np.float64)
+
+
+@pytest.mark.parametrize("last_nr", th.RB_LAST_ROWS)
+def test_wave_scan_model_on_the_valid_families(last_nr):
+    """Without a dropped entry both key rules give every row its sum: on the
+    lower stream matrices (rows ending on lanes 62, 63 and 64, a row across
+    whole steps, blocks that end inside a wave) and on the cap family."""
+    for m in (th.rowblock_stream_matrix(last_nr, True)[0], th.rowblock_sym_cap_matrix()[0]):
+        ptr, col, prod, want = _row_counts(m)
+        for fixed in (False, True):
+            assert np.array_equal(th.sym_row_sums(m.n_rows, ptr, col, prod, fixed), want)
+
+
+def test_wave_scan_double_counts_around_a_dropped_lane():
+    """The defect on record without a GPU: with key -1 on a dropped entry
+    inside a row the scan's step off = 2 adds the lane below the gap into the
+    lane above it and both are the last of a run.  The probe row (10 entries,
+    a dropped one, 9 more, all 1.0, lanes 0..19 of one wave) gets 29 instead
+    of 19; a dropped FIRST or LAST entry of a row breaks no run.  With the
+    row's key and a product of 0.0 on the dropped lane every row gets its sum."""
+    with_d, valid, info = th.rowblock_dropped_matrix()
+    ptr, col, prod, want = _row_counts(with_d)
+    assert np.array_equal(want, np.bincount(valid.row, minlength=valid.n_rows))
+    assert np.array_equal(th.sym_row_sums(with_d.n_rows, ptr, col, prod, fixed=True), want)
+    old = th.sym_row_sums(with_d.n_rows, ptr, col, prod, fixed=False)
+    pr = info["probe_row"]
+    assert want[pr] == 19.0 and old[pr] == 29.0
+    bad = np.flatnonzero(old != want)
+    assert pr in bad and (old[bad] > want[bad]).all()
+    # the rows that come out wrong are exactly rows with a dropped entry strictly inside them
+    out = (with_d.col < 0) | (with_d.col >= with_d.n_cols)
+    inner = {int(with_d.row[e]) for e in np.flatnonzero(out)
+             if ptr[with_d.row[e]] < e < ptr[with_d.row[e] + 1] - 1 and not out[ptr[with_d.row[e]]:ptr[with_d.row[e] + 1]].all()}
+    assert set(bad.tolist()) <= inner and len(bad) >= 4
+    # the minimal wave of the issue: ten products of row 5, a dropped lane, nine more
+    key = np.full((1, th.K_WAVE), -1)
+    p = np.zeros((1, th.K_WAVE))
+    key[0, :20], p[0, :20] = 5, 1.0
+    key[0, 10], p[0, 10] = -1, 0.0
+    acc = np.zeros(8)
+    th.wave_run_add(acc, key, p)
+    assert acc[5] == 29.0
+    key[0, 10] = 5
+    acc[:] = 0.0
+    th.wave_run_add(acc, key, p)
+    assert acc[5] == 19.0
+
+
+def test_rowblock_dropped_matrix_delivers_its_entries():
+    with_d, valid, info = th.rowblock_dropped_matrix()
+    n = with_d.n_rows
+    out = (with_d.col < 0) | (with_d.col >= n)
+    assert sorted(np.unique(with_d.col[out]).tolist()) == [-1, n, n + 1] and info["dropped"] == out.sum() == with_d.nnz - valid.nnz
+    ptr = th.csr_of(with_d)[0]
+    first = out[ptr[:-1][np.diff(ptr) > 0]]
+    last = out[ptr[1:][np.diff(ptr) > 0] - 1]
+    assert first.sum() >= 4 and last.sum() >= 4  # dropped first and last entries of rows
+    span = info["windows"][:, 1] - info["windows"][:, 0] + 1
+    blocks = with_d.row[out] // th.RB_ROWS
+    assert {info["only"], info["window_block"], *info["wide"]} <= set(blocks.tolist())
+    assert (span[list(info["wide"])] > th.T_MULTI_CAP).all() and 0 < span[info["window_block"]] < 512
+    # the host statements refuse the matrix: they cannot supply the reference
+    y = np.zeros(n)
+    with pytest.raises(sa.SpmvError):
+        sa.cpu_csr_sym(n, ptr, with_d.col, with_d.val, np.ones(n), y)
+    with pytest.raises(sa.SpmvError):
+        sa.cpu_csr_t(n, n, ptr, with_d.col, with_d.val, np.ones(n), y)
+    # the cases: the valid matrix's references, and CSR arrays that hold its values at the valid entries
+    cinfo, csr, t, s = th.dropped_case()
+    for (kind, integer), (p, c, v) in csr.items():
+        case = t if kind == "t" else s
+        assert np.array_equal(v[~out], (case["mi"] if integer else case["mr"]).val) and (v[out] != 0.0).all()
+        assert p is ptr or np.array_equal(p, ptr)
+    assert th.dropped_case()[2] is t

@@ -40,6 +40,19 @@ sources):
   coo_window_matrix,    x windows of exactly kStagedXwinCap = 2048 columns, of
   cmrs_window_matrix    2049 and of one, in one launch
 
+The row-block core (csrc/rowblock.h) and its users, the transposed scatter
+kernels and the fused symmetric kernels, have theirs at the end of the file,
+again with constants, window rules, the width rule and LDS sizes restated, and
+with numpy models of rb_row_of's search and wave_run_add's scan:
+
+  rowblock_stream_matrix   128-row blocks of 1 .. 5,121 entries around every
+                           loop bound of rb_stream (steps of 1,024, a tail in
+                           steps of 256), in seven row layouts; last blocks of
+                           1, 2 and 127 rows; a lower-triangular twin
+  rowblock_cap_matrix,     column spans of 1,024 .. 8,193 and union windows of
+  rowblock_sym_cap_matrix  512 .. 4,097: every cap of every width and one more
+  rowblock_dropped_matrix  valid entries plus columns -1, n and n + 1
+
 None needs a GPU.  The matrices are made once per argument set and never
 changed.
 """
@@ -867,3 +880,636 @@ def cmrs_window_matrix(n_cols: int = 5000):
 def window_case(fmt: str):
     m, spans = (coo_window_matrix() if fmt == "coo" else cmrs_window_matrix()[:2])
     return spans, *_case(m, 380 + len(fmt))
+
+
+# ===================================================== the row-block core
+# csrc/rowblock.h and its users csr_t_window_kernel, csr_t_multi_kernel<KV>
+# (csrc/transpose.hip), csr_sym_window_kernel and csr_sym_multi_kernel<KV>
+# (csrc/symmetric.hip).  Constants, the window rules, the width rule and the
+# LDS sizes restated (tests/test_thresholds.py holds them against the sources),
+# then three families:
+#
+#   rowblock_stream_matrix   blocks of 128 rows whose entry counts sit on both
+#                            sides of every loop bound of rb_stream's two forms
+#                            (steps of 1,024 entries, a tail in steps of 256),
+#                            the entries laid out so that rb_row_of's search,
+#                            wave_run_add's scan and the DPP rounds meet their
+#                            edges; last blocks of 1, 2 and 127 rows
+#   rowblock_cap_matrix,     blocks whose column span (transposed) or union
+#   rowblock_sym_cap_matrix  window (symmetric) is exactly every cap and one
+#                            more, every column of the span hit
+#   rowblock_dropped_matrix  a valid matrix plus entries in columns -1, n and
+#                            n + 1, which the scatter and fused runs drop
+RB_ROWS = 128                # rowblock.h kRbRows
+RB_PTR = RB_ROWS + 2         # rowblock.h kRbPtr
+RB_U = 4                     # rowblock.h kRbU
+RB_STEP = RB_U * K_BLOCK     # entries of one unrolled step of rb_stream: 1,024
+RB_SEARCH_STEPS = 7          # rb_row_of: step = kRbRows / 2, ..., 1
+T_CAP = 2048                 # transpose.hip kTCap
+T_MULTI_CAP = 8192           # transpose.hip SPMV_T_MULTI_CAP
+S_CAP = 2048                 # symmetric.hip kSCap
+S_MULTI_CAP = 4096           # symmetric.hip SPMV_S_MULTI_CAP
+T_WIDTHS = (1, 2, 4, 8)      # rowblock.h kTWidths
+RB_KS = (1, 2, 3, 4, 5, 8, 9)  # vectors per call: live < KV at every width, a second pass of width 1
+RB_KMAX = max(RB_KS)
+# exact scalings: column j of a real X is SCALES[j] * x, its reference and bound scale with it
+RB_SCALES = (1.0, -2.0, 0.5, 4.0, -0.25, 8.0, -1.0, 0.125, -16.0)
+# both sides of every bound of `e + 3 * 256 < end` (per thread) and `e0 + 1024 <= end` (uniform), of the
+# 256-entry tail steps, of two and of five unrolled steps; E mod 4 takes 1, 2 and 3
+RB_ENTRY_COUNTS = (1, 255, 256, 257, 1023, 1024, 1025, 1026, 1279, 1280, 2047, 2048, 2049, 5121)
+RB_LAYOUTS = ("first", "last", "middle", "singles", "wave", "long", "runs")
+RB_LAST_ROWS = (1, 2, 127)   # rows of the last block: rb_row_of's guard r + step < nr, the tid < nr loads of x
+RB_LONG_ROW = 1500           # the "long" layout's row: longer than one unrolled step
+
+
+def rb_blocks(n_rows: int) -> int:
+    return (n_rows + RB_ROWS - 1) // RB_ROWS
+
+
+def pass_widths(k: int) -> list:
+    """launch_scatter_multi / launch_fused_multi: [(live vectors, kernel width)]
+    of the ceil(k / 8) passes: live > 4 -> 8, > 2 -> 4, else live."""
+    out = []
+    for j0 in range(0, k, 8):
+        live = min(k - j0, 8)
+        out.append((live, 8 if live > 4 else 4 if live > 2 else live))
+    return out
+
+
+def t_multi_lds(kv: int, span: int) -> int:
+    """transpose.hip t_multi_lds: dynamic LDS bytes of csr_t_multi_kernel<kv>."""
+    return (RB_PTR + RB_ROWS * kv + span * kv) * 8
+
+
+def sym_multi_lds(kv: int, span: int) -> int:
+    """symmetric.hip sym_multi_lds: dynamic LDS bytes of csr_sym_multi_kernel<kv>."""
+    return (RB_PTR + 2 * max(span, RB_ROWS) * kv) * 8
+
+
+def _block_ranges(n_rows, n_cols, ptr, col):
+    blocks = rb_blocks(n_rows)
+    win = np.empty((blocks, 2), np.int64)
+    for b in range(blocks):
+        r0, r1 = b * RB_ROWS, min((b + 1) * RB_ROWS, n_rows)
+        c = np.asarray(col[ptr[r0]:ptr[r1]], np.int64)
+        c = c[(c >= 0) & (c < n_cols)]
+        win[b] = (c.min(), c.max()) if c.size else (0, -1)
+    return win
+
+
+def t_windows(n_rows: int, n_cols: int, ptr, col) -> np.ndarray:
+    """csr_t_range_kernel restated -> (blocks, 2) {lo, hi}: the range of the
+    block's columns inside [0, n_cols); {0, -1} for a block without one."""
+    return _block_ranges(n_rows, n_cols, ptr, col)
+
+
+def sym_windows(n: int, ptr, col) -> np.ndarray:
+    """csr_sym_range_kernel restated: the same range joined with the block's
+    own rows; {0, -1} for a block without an entry inside [0, n)."""
+    win = _block_ranges(n, n, ptr, col)
+    for b in range(win.shape[0]):
+        if win[b, 1] >= win[b, 0]:
+            win[b] = (min(win[b, 0], b * RB_ROWS), max(win[b, 1], min((b + 1) * RB_ROWS, n) - 1))
+    return win
+
+
+def window_tally(win: np.ndarray, cap: int):
+    """plan.hip windows_tally -> (blocks that fit, the sum of their spans, the widest of them)."""
+    span = win[:, 1] - win[:, 0] + 1
+    fit = (span > 0) & (span <= cap)
+    return int(fit.sum()), int(span[fit].sum()), int(span[fit].max()) if fit.any() else 0
+
+
+def expected_transpose_info(win: np.ndarray) -> dict:
+    """What prepare_scatter must report for these windows."""
+    one = window_tally(win, T_CAP)
+    return dict(blocks=win.shape[0], lds_blocks=one[0], flush_entries=one[1],
+                multi_lds_blocks=[window_tally(win, T_MULTI_CAP // w)[0] for w in T_WIDTHS],
+                multi_widest=[window_tally(win, T_MULTI_CAP // w)[2] for w in T_WIDTHS])
+
+
+def expected_symmetric_info(n: int, win: np.ndarray) -> dict:
+    """What prepare_fused must report: a union past the cap flushes the sums of the block's rows."""
+    span = win[:, 1] - win[:, 0] + 1
+    rows = np.minimum((np.arange(win.shape[0]) + 1) * RB_ROWS, n) - np.arange(win.shape[0]) * RB_ROWS
+
+    def at(cap):
+        fit = window_tally(win, cap)
+        return fit[0], fit[1] + int(rows[span > cap].sum()), fit[2]
+
+    one, multi = at(S_CAP), [at(S_MULTI_CAP // w) for w in T_WIDTHS]
+    return dict(blocks=win.shape[0], window_blocks=one[0], flush_entries=one[1],
+                multi_window_blocks=[m[0] for m in multi], multi_flush_entries=[m[1] for m in multi],
+                multi_widest=[m[2] for m in multi])
+
+
+def csr_of(m: sa.Coo):
+    """(row_ptr, col, val) of a row-sorted Coo in numpy: no host builder, so
+    columns outside [0, n_cols) pass through."""
+    assert (np.diff(m.row) >= 0).all()
+    ptr = np.concatenate(([0], np.cumsum(np.bincount(m.row, minlength=m.n_rows)))).astype(np.int64)
+    return ptr, m.col, m.val
+
+
+# ------------------------------------------------------- the models
+def rb_row_of(s_ptr: np.ndarray, nr: int, e: np.ndarray, mutate: str | None = None) -> np.ndarray:
+    """rowblock.h rb_row_of in numpy for entries e (any shape): seven guarded
+    steps over the block's nr + 1 offsets.  mutate, one line each:
+      "less"       s_ptr[r + step] < e instead of <=
+      "guard"      r + step <= nr instead of < nr
+      "six_front"  the search starts at step 32
+      "six_back"   the search stops before step 1"""
+    assert mutate in (None, "less", "guard", "six_front", "six_back") and s_ptr.size == nr + 1
+    steps = [RB_ROWS >> (i + 1) for i in range(RB_SEARCH_STEPS)]
+    steps = steps[1:] if mutate == "six_front" else steps[:-1] if mutate == "six_back" else steps
+    e = np.asarray(e, np.int64)
+    r = np.zeros(e.shape, np.int64)
+    for step in steps:
+        inside = (r + step <= nr) if mutate == "guard" else (r + step < nr)
+        at = s_ptr[np.minimum(r + step, nr)]
+        r = r + step * (inside & ((at < e) if mutate == "less" else (at <= e)))
+    return r
+
+
+def uniform_lanes(s0: int, end: int) -> np.ndarray:
+    """The entry ids rb_stream<true> hands to its body, wave by wave -> (waves,
+    64): the block's entries from s_ptr[0] in order; the last tail step is
+    filled with ids past `end` (the lanes that are not live)."""
+    count = (end - s0 + K_BLOCK - 1) // K_BLOCK * K_BLOCK if (end - s0) % RB_STEP else end - s0
+    return (s0 + np.arange(count, dtype=np.int64)).reshape(-1, K_WAVE)
+
+
+def wave_run_add(acc: np.ndarray, key: np.ndarray, p: np.ndarray) -> None:
+    """symmetric.hip wave_run_add for (waves, 64) keys and products: the
+    segmented scan by shuffles from `off` lanes below, then the last lane of
+    every run adds its sum to acc[key]."""
+    lane = np.arange(K_WAVE)
+    p = p.astype(np.float64).copy()
+    off = 1
+    while off < K_WAVE:
+        t, k = p.copy(), key.copy()
+        t[:, off:], k[:, off:] = p[:, :-off], key[:, :-off]
+        p = np.where((lane >= off) & (k == key), p + t, p)
+        off *= 2
+    nxt = key.copy()
+    nxt[:, :-1] = key[:, 1:]
+    last = (key >= 0) & ((lane == K_WAVE - 1) | (nxt != key))
+    np.add.at(acc, key[last], p[last])
+
+
+def sym_row_sums(n: int, ptr, col, prod, fixed: bool) -> np.ndarray:
+    """The row sums of sym_block as its accumulator receives them through
+    wave_run_add (the mirrored products are not modelled): prod[e] is the
+    product of entry e, taken as 0.0 where the entry is dropped.  fixed: a
+    dropped entry keeps its row's key; else it gets key -1, the form that
+    breaks a run of equal keys in two."""
+    acc = np.zeros(n)
+    win = sym_windows(n, ptr, col)
+    col = np.asarray(col, np.int64)
+    for b in range(win.shape[0]):
+        if win[b, 1] < win[b, 0]:
+            continue
+        r0, nr = b * RB_ROWS, min(RB_ROWS, n - b * RB_ROWS)
+        s_ptr = np.asarray(ptr[r0:r0 + nr + 1], np.int64)
+        e = uniform_lanes(int(s_ptr[0]), int(s_ptr[nr]))
+        live = e < s_ptr[nr]
+        ec = np.minimum(e, max(int(s_ptr[nr]) - 1, 0))
+        kept = live & (col[ec] >= 0) & (col[ec] < n)
+        key = np.where(live if fixed else kept, r0 + rb_row_of(s_ptr, nr, e), -1)
+        wave_run_add(acc, key, np.where(kept, np.asarray(prod)[ec], 0.0))
+    return acc
+
+
+# ------------------------------------------------ 1. the stream family
+def _rb_row_lens(layout: str, E: int) -> np.ndarray:
+    """Row lengths of a full block of E entries."""
+    lens = np.zeros(RB_ROWS, np.int64)
+    if layout == "first":
+        lens[0] = E
+    elif layout == "last":
+        lens[RB_ROWS - 1] = E
+    elif layout == "middle":  # row 77 = 64 + 8 + 4 + 1 among empty rows
+        lens[77] = E
+    elif layout == "singles":  # one entry per row, what is left in the last row
+        k = min(E, RB_ROWS - 1)
+        lens[:k] = 1
+        lens[RB_ROWS - 1] += E - k
+    elif layout == "wave":  # rows of 63, 64 and 65: their last entries on lanes 62, 62, 63, 63, 0, 63 of a wave
+        r, left = 0, E
+        while left > 0:
+            lens[r] = min((K_WAVE - 1, K_WAVE, K_WAVE + 1, K_WAVE, K_WAVE + 1, K_WAVE - 1)[r % 6], left)
+            left -= lens[r]
+            r += 1
+    elif layout == "long":  # one row across a whole unrolled step, rows of up to 100 behind it
+        lens[5] = min(E, RB_LONG_ROW)
+        r, left = 6, E - lens[5]
+        while left > 0:
+            lens[r] = min(100, left)
+            left -= lens[r]
+            r += 1
+    else:  # "runs": 40 empty rows in front, 40 behind
+        assert layout == "runs"
+        mid = RB_ROWS - 80
+        lens[40:40 + mid] = E // mid
+        lens[40:40 + E % mid] += 1
+    assert lens.sum() == E
+    return lens
+
+
+def rb_layout_of(j: int, second: bool) -> str:
+    """The layout of the block of RB_ENTRY_COUNTS[j] in the first / second pass over the counts."""
+    return RB_LAYOUTS[(j + (3 if second else 0)) % len(RB_LAYOUTS)]
+
+
+RB_LAST_ENTRIES = 300  # the short last block: one tail step of 256 and a partial one
+
+
+@functools.lru_cache(maxsize=None)
+def rowblock_stream_matrix(last_nr: int, lower: bool = False):
+    """-> (matrix, info).  Two blocks of 128 rows per E of RB_ENTRY_COUNTS, in
+    two different layouts (rb_layout_of); a filler block of 37 entries in front
+    of every fourth, so that blocks begin at odd offsets that are no multiple
+    of 32; a block without entries behind every fifth; a last block of last_nr
+    rows and 300 entries, its first and last row used.  lower=False: 300
+    columns, every block in a range of at most 300; lower=True: square, lower
+    triangular, row r's columns in [r - 200, r].  Every window stays under 512
+    columns, the narrowest cap.  info: under = [(block, E, layout)], empty =
+    the blocks without entries, starts = the first offset of every block under
+    test."""
+    rng = np.random.default_rng(900 + last_nr + (7 if lower else 0))
+    lens, under, empty, b = [], [], [], 0
+    for i in range(2 * len(RB_ENTRY_COUNTS)):
+        j, second = i % len(RB_ENTRY_COUNTS), i >= len(RB_ENTRY_COUNTS)
+        if i % 4 == 1:
+            f = np.zeros(RB_ROWS, np.int64)
+            np.add.at(f, rng.integers(0, RB_ROWS, 37), 1)
+            lens.append(f)
+            b += 1
+        E, layout = RB_ENTRY_COUNTS[j], rb_layout_of(j, second)
+        lens.append(_rb_row_lens(layout, E))
+        under.append((b, E, layout))
+        b += 1
+        if i % 5 == 2:
+            lens.append(np.zeros(RB_ROWS, np.int64))
+            empty.append(b)
+            b += 1
+    tail = np.zeros(last_nr, np.int64)
+    tail[0] = 37 if last_nr > 1 else RB_LAST_ENTRIES
+    if last_nr > 2:
+        tail[last_nr // 2] = 100
+    tail[last_nr - 1] += RB_LAST_ENTRIES - tail.sum()
+    lens = np.concatenate(lens + [tail])
+    n_rows, nnz = lens.size, int(lens.sum())
+    assert n_rows == b * RB_ROWS + last_nr and rb_blocks(n_rows) == b + 1
+    row = _sorted_rows(lens)
+    if lower:
+        n_cols = n_rows
+        col = row - (rng.integers(0, 201, nnz) % (row.astype(np.int64) + 1))
+    else:
+        n_cols = 300
+        base, width = rng.integers(0, 100, b + 1), rng.integers(40, 200, b + 1)
+        blk = row // RB_ROWS
+        col = base[blk] + rng.integers(0, 1 << 30, nnz) % width[blk]
+    m = _freeze(sa.Coo(n_rows, n_cols, row, col.astype(np.int32), rng.uniform(-1.0, 1.0, nnz), False,
+                       f"row-block stream family, last block of {last_nr} rows{', lower triangle' if lower else ''}"))
+    ptr = csr_of(m)[0]
+    starts = [int(ptr[blk * RB_ROWS]) for blk, _, _ in under]
+    for (blk, E, layout), s in zip(under, starts):
+        assert ptr[(blk + 1) * RB_ROWS] - s == E
+        assert np.array_equal(np.diff(ptr[blk * RB_ROWS:(blk + 1) * RB_ROWS + 1]), _rb_row_lens(layout, E))
+    assert all(ptr[blk * RB_ROWS] == ptr[(blk + 1) * RB_ROWS] for blk in empty) and len(empty) >= 3
+    assert ptr[n_rows] - ptr[b * RB_ROWS] == RB_LAST_ENTRIES and lens[b * RB_ROWS] > 0 and lens[-1] > 0
+    assert sum(s % 2 == 1 and s % 32 != 0 for s in starts) >= 8 and starts[0] == 0
+    assert {E for _, E, _ in under} == set(RB_ENTRY_COUNTS) and {E % 4 for E in RB_ENTRY_COUNTS} == {0, 1, 2, 3}
+    for layout in RB_LAYOUTS:  # every layout in a block of at most one tail step and in one of whole unrolled steps
+        es = [E for _, E, la in under if la == layout]
+        assert min(es) <= K_BLOCK + 1 and max(es) > RB_STEP, (layout, es)
+    assert any(la == "long" and E >= RB_LONG_ROW for _, E, la in under)
+    win = sym_windows(n_rows, ptr, m.col) if lower else t_windows(n_rows, n_cols, ptr, m.col)
+    span = win[:, 1] - win[:, 0] + 1
+    assert span.max() < min(S_MULTI_CAP, T_MULTI_CAP) // max(T_WIDTHS) and (span[empty] == 0).all()
+    if lower:
+        assert (m.col <= m.row).all() and (m.col == m.row).any() and (m.col < m.row).any()
+    assert 30_000 < nnz < 60_000
+    return m, dict(under=tuple(under), empty=tuple(empty), starts=tuple(starts), last_nr=last_nr, windows=win)
+
+
+# ------------------------------------------- references shared by the tests
+def _int_block(seed: int, rows: int, bits: int) -> np.ndarray:
+    return _signed_block(np.random.default_rng(seed), rows, bits)
+
+
+def _signed_block(rng, rows, bits):
+    return exact._signed_ints(rng, (rows, RB_KMAX), bits)
+
+
+def _frozen(*arrays):
+    for a in arrays:
+        a.setflags(write=False)
+    return arrays
+
+
+def transposed_case(m: sa.Coo, seed: int) -> dict:
+    """Y = A^T X on m, both rules of tests/exact.py: the integer copy with an
+    integer X[n_rows, 9] and its int64 reference; the wide-range copy with one
+    x, its extended-precision reference and fp64 bound, column j of its X being
+    RB_SCALES[j] x (exact scalings: reference and bound scale with them)."""
+    e = exact.integerize(m, seed=seed)
+    Xi = _int_block(seed + 1, m.n_rows, e.b)
+    ref = exact.int_spmv(m.n_cols, m.col, m.row, e.m.val.astype(np.int64), Xi)
+    assert (np.abs(ref) < (1 << 53)).all()
+    mr, _, xt = exact.realize(m, seed=seed + 2)
+    X = np.stack([s * xt for s in RB_SCALES], axis=1)
+    Xf = Xi.astype(np.float64)
+    _frozen(Xf, ref, X)
+    return dict(mi=e.m, Xi=Xf, ref_i=ref, mr=mr, X=X, ref=exact.exact_reference(mr, xt, transpose=True),
+                bound=exact.fp64_bound(mr, xt, transpose=True), a=e.a, b=e.b)
+
+
+def symmetric_case(m: sa.Coo, seed: int) -> dict:
+    """Y = (S + S^T - diag S) X on the half m: as transposed_case, the integer
+    sizes taken from the expansion's longest row (test_symmetric.integer_half)
+    and the reference and bound of the real copy from sa.expand_symmetric."""
+    ex = exact.integerize(sa.expand_symmetric(m), seed)
+    half = sa.Coo(m.n_rows, m.n_cols, m.row, m.col, np.array(ex.m.val[: m.nnz]), m.symmetric, m.label + " (integer)")
+    ei = sa.expand_symmetric(half)
+    Xi = _int_block(seed + 1, m.n_rows, ex.b)
+    ref = exact.int_spmv(m.n_rows, ei.row, ei.col, ei.val.astype(np.int64), Xi)
+    assert (np.abs(ei.val) < (1 << ex.a)).all() and (np.abs(ref) < (1 << 53)).all()
+    rng = np.random.default_rng(seed + 2)
+    mr = sa.Coo(m.n_rows, m.n_cols, m.row, m.col, exact.wide_range(rng, m.nnz), m.symmetric, m.label + " (wide range)")
+    x = exact.wide_range(rng, m.n_cols)
+    er = sa.expand_symmetric(mr)
+    X = np.stack([s * x for s in RB_SCALES], axis=1)
+    Xf = Xi.astype(np.float64)
+    _frozen(half.val, Xf, ref, mr.val, X)
+    return dict(mi=half, Xi=Xf, ref_i=ref, mr=mr, X=X, ref=exact.exact_reference(er, x), bound=exact.fp64_bound(er, x),
+                a=ex.a, b=ex.b)
+
+
+@functools.lru_cache(maxsize=None)
+def stream_case(last_nr: int, lower: bool):
+    """-> (info, transposed_case, symmetric_case or None) of rowblock_stream_matrix; made once."""
+    m, info = rowblock_stream_matrix(last_nr, lower)
+    seed = 500 + 10 * last_nr + (5 if lower else 0)
+    return info, transposed_case(m, seed), symmetric_case(m, seed + 3) if lower else None
+
+
+# ---------------------------------------------------- 2. the cap family
+T_CAP_SPANS = tuple(s for c in (1024, 2048, 4096, 8192) for s in (c, c + 1))
+S_CAP_SPANS = tuple(s for c in (512, 1024, 2048, 4096) for s in (c, c + 1))
+
+
+def _spread(total: int, rows: int = RB_ROWS) -> np.ndarray:
+    lens = np.full(rows, total // rows, np.int64)
+    lens[: total % rows] += 1
+    return lens
+
+
+@functools.lru_cache(maxsize=None)
+def rowblock_cap_matrix():
+    """-> (matrix, info) for the transposed runs.  One block of 128 rows per
+    span of T_CAP_SPANS (both sides of 8,192 / KV for KV = 8, 4, 2, 1 and of
+    kTCap): `span` entries over the 128 rows (8,193: 64 a row, eight unrolled
+    steps), their columns a permutation of [lo, lo + span), so every
+    accumulator word is hit; lo = 61 per block further on, so neighbouring
+    windows overlap and several workgroups add to the same outputs.  The wide
+    and the narrow spans alternate; a block without entries and a last block of
+    5 rows over 9 columns close the matrix.  info: under = [(block, span)],
+    expect = what the plan must report (expected_transpose_info)."""
+    rng = np.random.default_rng(911)
+    order = (8193, 1024, 4097, 2048, 8192, 1025, 4096, 2049)
+    assert sorted(order) == sorted(T_CAP_SPANS)
+    lens, cols, under = [], [], []
+    for b, span in enumerate(order):
+        lens.append(_spread(span))
+        cols.append(61 * b + rng.permutation(span))
+        under.append((b, span))
+    lens += [np.zeros(RB_ROWS, np.int64), np.array([3, 0, 4, 0, 5])]
+    cols.append(5000 + rng.integers(0, 9, 12))
+    cols[-1][:2] = (5000, 5008)
+    lens, col = np.concatenate(lens), np.concatenate(cols)
+    n_rows, n_cols = lens.size, 61 * len(order) + max(order) + 17
+    m = _freeze(sa.Coo(n_rows, n_cols, _sorted_rows(lens), col.astype(np.int32), rng.uniform(-1.0, 1.0, col.size), False,
+                       "row blocks spanning every transposed cap and one more column"))
+    ptr = csr_of(m)[0]
+    win = t_windows(n_rows, n_cols, ptr, m.col)
+    span = win[:, 1] - win[:, 0] + 1
+    assert [int(span[b]) for b, _ in under] == list(order) and span[len(order)] == 0 and span[-1] == 9
+    for b, s in under:
+        c = m.col[ptr[b * RB_ROWS]:ptr[(b + 1) * RB_ROWS]]
+        assert np.array_equal(np.sort(c), win[b, 0] + np.arange(s))  # every column of the span, once
+    assert all(win[b, 1] >= win[b + 1, 0] for b in range(len(order) - 1))  # neighbours overlap
+    expect = expected_transpose_info(win)
+    small = 1 + 0  # the 9-column last block fits every cap
+    assert expect["lds_blocks"] == 3 + small and expect["flush_entries"] == 1024 + 1025 + 2048 + 9
+    assert expect["multi_lds_blocks"] == [7 + small, 5 + small, 3 + small, 1 + small]
+    assert expect["multi_widest"] == [8192, 4096, 2048, 1024]
+    assert [t_multi_lds(w, s) for w, s in zip(T_WIDTHS, expect["multi_widest"])] == [67_600, 68_624, 70_672, 74_768]
+    assert t_multi_lds(1, 8192) > 65_536  # more than the default dynamic LDS of a launch
+    assert 30_000 < m.nnz < 40_000
+    return m, dict(under=tuple(under), expect=expect, windows=win)
+
+
+S_CAP_LOWER_AT = 40  # the first block of the lower-half forms: r0 = 5,120 >= 4,097 - 128
+S_CAP_UPPER_AT = 1   # the first block of the upper-half forms
+S_CAP_BLOCKS = 48    # full blocks; a diagonal-only block of S_CAP_LAST_ROWS rows follows
+S_CAP_LAST_ROWS = 77
+S_CAP_EMPTY = (20, 21)
+
+
+@functools.lru_cache(maxsize=None)
+def rowblock_sym_cap_matrix():
+    """-> (half, info) for the symmetric runs; n = 48 * 128 + 77 = 6,221.  The
+    union window of a block is its column range joined with its rows:
+      lower forms  blocks 40..47, one per span of S_CAP_SPANS: every row its
+                   diagonal entry, and the span - 128 columns [r0 + 128 - span,
+                   r0) spread over the rows: the window ends on the block's
+                   last row
+      upper forms  blocks 1..8: the diagonal, and the columns [r0 + 128, r0 +
+                   span) spread over the rows: the window starts exactly at r0
+      the others   the diagonal only (span 128), blocks 20 and 21 nothing
+      the last     77 rows, the diagonal only: the span equals nr
+    Every word of every window is hit: the rows' words by their sums, the
+    others as a mirrored column.  info: under = [(block, span, form)], expect =
+    what the plan must report (expected_symmetric_info)."""
+    rng = np.random.default_rng(913)
+    n = S_CAP_BLOCKS * RB_ROWS + S_CAP_LAST_ROWS
+    form = {S_CAP_LOWER_AT + i: (s, "lower") for i, s in enumerate(S_CAP_SPANS)}
+    form.update({S_CAP_UPPER_AT + i: (s, "upper") for i, s in enumerate(S_CAP_SPANS)})
+    rows, cols, under = [], [], []
+    for b in range(rb_blocks(n)):
+        if b in S_CAP_EMPTY:
+            continue
+        r0, nr = b * RB_ROWS, min(RB_ROWS, n - b * RB_ROWS)
+        own = r0 + np.arange(nr)
+        rows.append(own)
+        cols.append(own)
+        if b in form:
+            span, kind = form[b]
+            far = (r0 + RB_ROWS - span + np.arange(span - RB_ROWS)) if kind == "lower" else (r0 + RB_ROWS + np.arange(span - RB_ROWS))
+            rows.append(r0 + np.repeat(np.arange(RB_ROWS), _spread(span - RB_ROWS)))
+            cols.append(rng.permutation(far))
+            under.append((b, span, kind))
+    row, col = np.concatenate(rows), np.concatenate(cols)
+    order = np.argsort(row, kind="stable")
+    m = _freeze(sa.Coo(n, n, row[order].astype(np.int32), col[order].astype(np.int32), rng.uniform(-1.0, 1.0, row.size),
+                       True, "union windows spanning every symmetric cap and one more column"))
+    ptr = csr_of(m)[0]
+    win = sym_windows(n, ptr, m.col)
+    span = win[:, 1] - win[:, 0] + 1
+    for b, s, kind in under:
+        r0 = b * RB_ROWS
+        assert span[b] == s and (win[b, 1] == r0 + RB_ROWS - 1 if kind == "lower" else win[b, 0] == r0), (b, s, kind)
+        c = np.unique(m.col[ptr[r0]:ptr[r0 + RB_ROWS]])
+        assert np.array_equal(c, win[b, 0] + np.arange(s))  # every column of the window
+        mine = slice(ptr[r0], ptr[r0 + RB_ROWS])
+        assert ((m.col[mine] <= m.row[mine]) if kind == "lower" else (m.col[mine] >= m.row[mine])).all()
+    assert (span[list(S_CAP_EMPTY)] == 0).all() and span[-1] == S_CAP_LAST_ROWS
+    rest = np.setdiff1d(np.arange(S_CAP_BLOCKS), [b for b, _, _ in under] + list(S_CAP_EMPTY))
+    assert (span[rest] == RB_ROWS).all()
+    expect = expected_symmetric_info(n, win)
+    live = rb_blocks(n) - len(S_CAP_EMPTY)
+    assert expect["window_blocks"] == live - 2 * 3  # 2,049, 4,096 and 4,097 in both forms are past kSCap
+    assert expect["multi_window_blocks"] == [live - 2 * 1, live - 2 * 3, live - 2 * 5, live - 2 * 7]
+    assert expect["multi_widest"] == [4096, 2048, 1024, 512]
+    assert sym_multi_lds(1, 4096) == 66_576 > 65_536 and [sym_multi_lds(w, S_MULTI_CAP // w) for w in T_WIDTHS] == [66_576] * 4
+    wide = sum(s > S_CAP for _, s, _ in under)
+    assert expect["flush_entries"] == int(span[span <= S_CAP].sum()) + RB_ROWS * wide
+    return m, dict(under=tuple(under), expect=expect, windows=win)
+
+
+@functools.lru_cache(maxsize=None)
+def cap_case():
+    m, info = rowblock_cap_matrix()
+    return info, transposed_case(m, 601)
+
+
+@functools.lru_cache(maxsize=None)
+def sym_cap_case():
+    m, info = rowblock_sym_cap_matrix()
+    return info, symmetric_case(m, 611)
+
+
+# ------------------------------------------------- 3. the dropped family
+DROP_PROBE_ROW = 5      # of the probe block: 10 entries, a dropped one, 9 more, lanes 0..19 of the block's first wave
+DROP_WIDE_COLS = 50     # the wide blocks also hold columns [0, 50): unions past every cap
+DROP_WIDE_AT = 66       # first of the two wide blocks: r0 = 8,448 > kTMultiCap
+
+
+@functools.lru_cache(maxsize=None)
+def rowblock_dropped_matrix():
+    """-> (matrix with the dropped entries, the same matrix without them,
+    info); both as row-sorted Coo, to be turned into CSR by csr_of (the host
+    builders refuse such columns).  The valid matrix is the lower-triangular
+    stream matrix with a last block of 127 rows, grown to n = 68 * 128 + 3:
+      the probe block   (the first block behind the stream matrix) rows 0..4
+                        empty, row 5 of 19 entries, rows of 64 behind it
+      a block of        dropped entries only (nothing else in its 128 rows)
+      two wide blocks   at rows 8,448 on: 1,025 entries near the diagonal and
+                        in columns [0, 50), so their unions and column ranges
+                        are wider than every cap of both families
+    Added entries, columns -1, n and n + 1 in turn, never another value:
+      - in the probe block, behind the 10th entry of row 5: the middle of a
+        row, inside one wave
+      - as the first and as the last entry of rows of a window block of the
+        stream matrix, of the probe block and of both wide blocks, and in the
+        middle of a long row of each
+      - the block of nothing else.
+    info: probe_row (global), dropped = their count, windows (symmetric union
+    windows, unchanged by the added entries), wide = the wide blocks."""
+    base, binfo = rowblock_stream_matrix(127, True)
+    rng = np.random.default_rng(917)
+    n = (DROP_WIDE_AT + 2) * RB_ROWS + 3
+    first = rb_blocks(base.n_rows)
+    probe, only = first, first + 1
+    assert only < DROP_WIDE_AT - 1
+    rows, cols = [base.row.astype(np.int64)], [base.col.astype(np.int64)]
+    lens = np.zeros(RB_ROWS, np.int64)
+    lens[DROP_PROBE_ROW] = 19
+    lens[DROP_PROBE_ROW + 1:DROP_PROBE_ROW + 9] = K_WAVE
+    r = probe * RB_ROWS + np.repeat(np.arange(RB_ROWS), lens)
+    rows.append(r)
+    cols.append(r - rng.integers(0, 150, r.size))
+    for b in (DROP_WIDE_AT, DROP_WIDE_AT + 1):
+        lens = _rb_row_lens("wave" if b == DROP_WIDE_AT else "long", 1025)
+        r = b * RB_ROWS + np.repeat(np.arange(RB_ROWS), lens)
+        c = np.where(rng.integers(0, 3, r.size) == 0, rng.integers(0, DROP_WIDE_COLS, r.size), r - rng.integers(0, 150, r.size))
+        c[:2] = (0, r[1])
+        rows.append(r)
+        cols.append(c)
+    row, col = np.concatenate(rows), np.concatenate(cols)
+    order = np.argsort(row, kind="stable")
+    row, col = row[order], col[order]
+    val = rng.uniform(-1.0, 1.0, row.size)
+    valid = sa.Coo(n, n, row.astype(np.int32), col.astype(np.int32), val, True, "the dropped family without its dropped entries")
+    ptr = csr_of(valid)[0]
+    bad_cols = (-1, n, n + 1)
+    # (entry position the dropped entry goes in front of, its row)
+    places = [(int(ptr[probe * RB_ROWS + DROP_PROBE_ROW]) + 10, probe * RB_ROWS + DROP_PROBE_ROW)]
+    window_block = next(b for b, E, la in binfo["under"] if la == "wave" and E >= 2048)
+    for b in (window_block, probe, DROP_WIDE_AT, DROP_WIDE_AT + 1):
+        rws = b * RB_ROWS + np.flatnonzero(np.diff(ptr[b * RB_ROWS:(b + 1) * RB_ROWS + 1]) >= 19)
+        for r in (int(rws[0]), int(rws[len(rws) // 2]), int(rws[-1])):
+            if r == probe * RB_ROWS + DROP_PROBE_ROW:
+                continue
+            places += [(int(ptr[r]), r), (int(ptr[r + 1]), r), (int(ptr[r]) + int(ptr[r + 1] - ptr[r]) // 2, r)]
+    pos = np.array([p for p, _ in places], np.int64)
+    add_row = np.array([r for _, r in places], np.int64)
+    add_col = np.array([bad_cols[i % 3] for i in range(len(places))], np.int64)
+    add_val = rng.uniform(1.0, 2.0, len(places))
+    row_d, col_d, val_d = (np.insert(a, pos, v) for a, v in ((row, add_row), (col, add_col), (val, add_val)))
+    lens = np.zeros(RB_ROWS, np.int64)  # the block of dropped entries only: 300 over a few rows
+    lens[[0, 3, 64, 127]] = (1, 70, 129, 100)
+    r = only * RB_ROWS + np.repeat(np.arange(RB_ROWS), lens)
+    at = int(np.searchsorted(row_d, only * RB_ROWS))
+    row_d = np.insert(row_d, at, r)
+    col_d = np.insert(col_d, at, np.array(bad_cols)[np.arange(r.size) % 3])
+    val_d = np.insert(val_d, at, rng.uniform(1.0, 2.0, r.size))
+    assert (np.diff(row_d) >= 0).all()
+    with_d = sa.Coo(n, n, row_d.astype(np.int32), col_d.astype(np.int32), val_d, True, "valid entries and columns -1, n, n + 1")
+    _freeze(valid)
+    _freeze(with_d)
+    out = (with_d.col < 0) | (with_d.col >= n)
+    assert set(np.unique(with_d.col[out]).tolist()) == set(bad_cols) and out.sum() == len(places) + 300
+    for a, b_ in ((with_d.row[~out], valid.row), (with_d.col[~out], valid.col), (with_d.val[~out], valid.val)):
+        assert np.array_equal(a, b_)  # without them: the valid matrix, entry for entry
+    ptr_d = csr_of(with_d)[0]
+    pr = probe * RB_ROWS + DROP_PROBE_ROW
+    assert ptr_d[pr] == ptr_d[probe * RB_ROWS] and ptr_d[pr + 1] - ptr_d[pr] == 20 and out[ptr_d[pr] + 10]
+    assert not out[ptr_d[pr]:ptr_d[pr] + 10].any() and not out[ptr_d[pr] + 11:ptr_d[pr] + 20].any()
+    win = sym_windows(n, ptr_d, with_d.col)
+    assert np.array_equal(win, sym_windows(n, ptr, valid.col)) and np.array_equal(
+        t_windows(n, n, ptr_d, with_d.col), t_windows(n, n, ptr, valid.col))
+    span = win[:, 1] - win[:, 0] + 1
+    assert span[only] == 0 and ptr_d[(only + 1) * RB_ROWS] - ptr_d[only * RB_ROWS] == 300
+    wide = (DROP_WIDE_AT, DROP_WIDE_AT + 1)
+    tspan = np.diff(t_windows(n, n, ptr_d, with_d.col), axis=1)[:, 0] + 1
+    assert (span[list(wide)] > T_MULTI_CAP).all() and (tspan[list(wide)] > T_MULTI_CAP).all()
+    assert span[window_block] < S_MULTI_CAP // 8 and span[probe] < S_MULTI_CAP // 8
+    for b in (window_block, probe) + wide:  # each holds a first, a last and a middle dropped entry of a row
+        blk = slice(ptr_d[b * RB_ROWS], ptr_d[(b + 1) * RB_ROWS])
+        assert out[blk].sum() >= 3
+    return with_d, valid, dict(probe_row=pr, dropped=int(out.sum()), windows=win, wide=wide, only=only,
+                               window_block=window_block)
+
+
+@functools.lru_cache(maxsize=None)
+def dropped_case():
+    """-> (info, (ptr, col, val) per copy with the dropped entries, the cases of
+    the valid matrix).  The integer and the real copy of the matrix WITH the
+    dropped entries take the valid copy's values at the valid entries and 3.0
+    (integer) or the constructor's values (real) at the dropped ones."""
+    with_d, valid, info = rowblock_dropped_matrix()
+    t, s = transposed_case(valid, 631), symmetric_case(valid, 641)
+    out = (with_d.col < 0) | (with_d.col >= with_d.n_cols)
+    ptr = csr_of(with_d)[0]
+
+    def arrays(vals, fill):
+        v = np.where(out, fill, 0.0)
+        v[~out] = vals
+        return _frozen(ptr, with_d.col, v)
+
+    csr = {("t", True): arrays(t["mi"].val, 3.0), ("t", False): arrays(t["mr"].val, with_d.val),
+           ("s", True): arrays(s["mi"].val, 3.0), ("s", False): arrays(s["mr"].val, with_d.val)}
+    return info, csr, t, s
