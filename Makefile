@@ -41,7 +41,7 @@ LIB_HIP  := $(LIBDIR)/libspmv_hip.so
 LIB_HOST := $(LIBDIR)/libspmv_host.so
 ORACLE   := oracle/liboracle.so
 
-.PHONY: all default lib oracle probes lab test-san test-san-transpose test-san-transpose-multi test-san-multi-plan test-san-symmetric test-san-symmetric-multi test-san-precond test-san-cheb test-san-bicgstab test-cpu test-gpu clean $(TARGETS)
+.PHONY: all default lib oracle probes lab test-san test-san-transpose test-san-transpose-multi test-san-multi-plan test-san-symmetric test-san-symmetric-multi test-san-precond test-san-cheb test-san-bicgstab test-san-bsr test-cpu test-gpu clean $(TARGETS)
 
 default: all
 all: lib $(TARGETS) probes
@@ -223,6 +223,17 @@ build/san/bicgstab_harness: tests/san/bicgstab_harness.c $(HOST_SRC) include/spm
 
 test-san-bicgstab: build/san/bicgstab_harness
 	$(SANENV) ASAN_OPTIONS=detect_leaks=1:exitcode=99 build/san/bicgstab_harness
+
+# the host side of block CSR (spmv_bsr_plan, spmv_bsr_fill, spmv_cpu_bsr) under
+# ASan + UBSan: a stand-alone program over the fixtures, every block size,
+# sizes that are no multiple of it, exactly-sized buffers and the refused
+# inputs (tests/san/bsr_harness.c)
+build/san/bsr_harness: tests/san/bsr_harness.c $(HOST_SRC) include/spmv_host.h include/spmv_rc.h
+	@mkdir -p build/san
+	$(CC) -std=c11 -Wall -Wextra -Werror -fopenmp -Iinclude $(SANFLAGS) $< $(HOST_SRC) -o $@ -lm
+
+test-san-bsr: build/san/bsr_harness
+	$(SANENV) ASAN_OPTIONS=detect_leaks=1:exitcode=99 build/san/bsr_harness tests/golden/*.mtx
 
 test-gpu: all oracle
 	python -m pytest tests/ -x -q -m gpu

@@ -102,7 +102,14 @@ typedef struct spmv_dims {
  *              copy); -1 the rule (2^19 columns when n_cols > 2^21 and they
  *              hold half the entries), 0 none (e.g. columns already
  *              relabelled by degree, spmv_column_relabel), > 0 that many  */
-enum spmv_fmt { SPMV_FMT_COO = 0, SPMV_FMT_CSR = 1, SPMV_FMT_ELL = 2, SPMV_FMT_SELL = 3, SPMV_FMT_CMRS = 4 };
+enum spmv_fmt {
+    SPMV_FMT_COO = 0,
+    SPMV_FMT_CSR = 1,
+    SPMV_FMT_ELL = 2,
+    SPMV_FMT_SELL = 3,
+    SPMV_FMT_CMRS = 4,
+    SPMV_FMT_BSR = 5 /* block CSR, not one of the reference's five: spmv_plan_bsr */
+};
 
 typedef struct spmv_plan_opts {
     int32_t lanes;
@@ -169,6 +176,46 @@ int spmv_plan_sell(spmv_dims d, int32_t C, int32_t sigma, int32_t ki, int64_t n_
  * kernels/Cmrs.cl:1).  Layout of spmv_cmrs_run below.                     */
 int spmv_plan_cmrs(spmv_dims d, int32_t h, int64_t n_strips, const int64_t *strip_ptr, const uint8_t *row_in_strip,
                    const int32_t *col, const double *val, const spmv_plan_opts *o, spmv_plan **out);
+/* Block CSR (BSR) with b x b blocks, b in {2, 3, 4}: one int32 column per
+ * block, 8 + 4/b^2 bytes per stored value instead of CSR's 12, for matrices
+ * with b unknowns per node (3-dof FEM).  The arrays are those of
+ * spmv_bsr_fill (spmv_host.h, which states the layout and THE FILL-IN RULE: a
+ * slot without an entry multiplies 0.0 by an x value of its block column):
+ * brow_ptr[n_brows + 1] int64, bcol[n_blocks] int32 ascending inside a block
+ * row, bval[n_blocks * b * b] row-major inside a block.  d.n_rows and d.n_cols
+ * are the scalar sizes, d.nnz the stored values n_blocks * b * b ("the stored
+ * entries that are multiplied"); n_brows = ceil(n_rows / b), the last block
+ * row and block column may be partial.
+ *   - Only opts.lanes is honoured: the lanes per block row, a power of two
+ *     2..64; 0 = about one lane per 2 blocks of the mean block row, 8 at
+ *     the least (spmv_bsr_auto_lanes).  The other options are ignored.
+ *   - The plan builds nothing (owned_bytes = 0).  spmv_plan_run's contract
+ *     holds word for word: a partial last block column is guarded, no 16-byte
+ *     load of x or store of y, no atomics, the same bits on every run and
+ *     under every spmv_set_option switch.  Info: format 5, kernel
+ *     "bsr_kernel", desc names b, the lanes and the block count.
+ *   - Refused with SPMV_OTHER_ERROR, a message and no plan: b not in
+ *     {2, 3, 4}, n_brows != ceil(n_rows / b), d.nnz not a multiple of b*b,
+ *     n_cols > INT32_MAX - 8, lanes not 0 or a power of two in 2..64, a NULL
+ *     array with blocks present.
+ *   - No multi-vector, transposed or symmetric run: spmv_plan_run_multi
+ *     refuses, the three *_supported calls answer 0 and the three prepare
+ *     calls refuse as for every non-CSR plan.
+ * Which to call (the byte model, profiles/bsr/README.md): BSR stores fewer
+ * bytes than CSR when fill (stored values / entries) < 12 / (8 + 4/b^2), i.e.
+ * 1.33 / 1.42 / 1.45 at b = 2 / 3 / 4; on the cant-like matrix at b = 3 (fill
+ * 1.079) it is 0.755 of CSR's bytes, on a truly blocked matrix 0.70.  On an
+ * MI355X (cold, b = 3, tools/bsr_bench.py, profiles/bsr/README.md) those
+ * bytes turn into time only in part.  One cant-like matrix: SLOWER than the
+ * default CSR plan, 12.0 against 10.4 us (1.16x, the same in a second run).
+ * The 32-copy cant-like batch: a tie, 0.2104 against 0.2190 ms in one run
+ * (0.96x), 0.2301 against 0.2159 on another box (1.07x).  A fill-1.0 matrix
+ * of 49,152 rows: FASTER, 4.7 against 6.9 us (0.68x, one run).  Call
+ * spmv_plan_bsr for a truly blocked matrix or where the memory matters,
+ * spmv_plan_csr for one matrix with fill-in.                              */
+int spmv_bsr_auto_lanes(int64_t n_brows, int64_t n_blocks);
+int spmv_plan_bsr(spmv_dims d, int32_t b, int64_t n_brows, const int64_t *brow_ptr, const int32_t *bcol,
+                  const double *bval, const spmv_plan_opts *o, spmv_plan **out);
 /* y = A x on `stream` (NULL = the default stream; the plan's d.stream is
  * used for building only).  x[n_cols], y[n_rows], device pointers.
  *   - y[0 .. n_rows) is FULLY overwritten (rows without entries get 0.0);

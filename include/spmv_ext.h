@@ -556,6 +556,15 @@ int spmv_bjacobi_destroy(spmv_bjacobi *m);
  * takes.  out must not alias x.                                          */
 int spmv_gather(int64_t n, const int32_t *order, const double *x, double *out, int device, void *stream);
 
+/* ---------------------------------------------------------------- BSR ---
+ * The one-call form of a BSR plan's run (spmv_plan_bsr, spmv.h: the arrays,
+ * d.nnz = the stored values, the refusals and the run contract are that
+ * plan's).  lanes = the lanes per block row, a power of two 2..64, 0 =
+ * spmv_bsr_auto_lanes.  y is bit-identical to the plan's run with the same
+ * lanes.                                                                  */
+int spmv_bsr_run(spmv_dims d, int32_t b, int64_t n_brows, const int64_t *brow_ptr, const int32_t *bcol,
+                 const double *bval, const double *x, double *y, int lanes);
+
 /* ---------------------------------------------------------- switches ---
  * Placement and load-policy switches for A/B runs; each changes speed,
  * never a result bit (tests/test_gpu_parity.py checks that).  The library

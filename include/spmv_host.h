@@ -307,6 +307,48 @@ int spmv_partition_rows_calibrated(int64_t n_rows, const int64_t *row_ptr, int p
                                    double row_weight, int old_parts, const int64_t *old_bounds,
                                    const double *old_ms, int64_t *bounds);
 
+/* ------------------------------------------------------ block CSR (BSR) ---
+ * One int32 column per b x b block instead of one per entry, for matrices
+ * with b unknowns per node (3-dof FEM).  The layout is scipy's
+ * bsr_matrix.data[blk, r, c] and rocSPARSE's row-major one:
+ *   brow_ptr[n_brows + 1]  int64, n_brows = ceil(n_rows / b)
+ *   bcol[n_blocks]         int32, strictly ascending inside a block row
+ *   bval[n_blocks * b * b] double, bval[(blk*b + r)*b + c] = entry
+ *                          (I*b + r, bcol[blk]*b + c) of block row I
+ * The last block row and the last block column may be partial.  Slots outside
+ * the matrix and slots without an entry hold +0.0.
+ *
+ * THE FILL-IN RULE, a real difference from CSR: a slot without an entry
+ * multiplies 0.0 by an x value of its block column.  For finite x no result
+ * changes.  A non-finite x[c] reaches every scalar row of every block row that
+ * has a block in c's block column (0.0 * inf = NaN), and a row whose exact
+ * result is -0.0 may come out +0.0.  Slots outside the matrix are never
+ * multiplied: no x at or past n_cols is read.
+ *
+ * spmv_bsr_plan counts the blocks of a CSR matrix (columns in any order
+ * inside a row, duplicates allowed); spmv_bsr_fill writes the three arrays,
+ * duplicates of one (i, j) added into their slot in CSR order.  1 <= b <=
+ * SPMV_BSR_MAX_B.  SPMV_OTHER_ERROR with nothing written: b out of range,
+ * negative sizes, row_ptr not nondecreasing from a non-negative start, a
+ * column outside [0, n_cols), n_cols > INT32_MAX - 8, or a NULL array that
+ * would be read or written.                                               */
+#define SPMV_BSR_MAX_B 8
+int spmv_bsr_plan(int64_t n_rows, int64_t n_cols, const int64_t *row_ptr, const int32_t *col, int32_t b,
+                  int64_t *n_brows, int64_t *n_blocks);
+int spmv_bsr_fill(int64_t n_rows, int64_t n_cols, const int64_t *row_ptr, const int32_t *col, const double *val,
+                  int32_t b, int64_t *brow_ptr, int32_t *bcol, double *bval);
+/* y = A x from the BSR arrays: the plain serial loop, block after block in
+ * storage order, the CPU statement of a BSR plan's run (spmv_plan_bsr,
+ * spmv.h), never a device fallback.  Writes y[0 .. n_rows) only (rows of empty
+ * block rows get 0.0) and reads x[0 .. n_cols) only: the partial last block
+ * row and block column are cut, not hidden behind their stored 0.0.
+ * SPMV_OTHER_ERROR, before y is touched: b out of range, negative sizes,
+ * n_brows != ceil(n_rows / b), offsets not nondecreasing, a block column
+ * outside [0, ceil(n_cols / b)), n_cols > INT32_MAX - 8, or a NULL array that
+ * would be read or written.                                               */
+int spmv_cpu_bsr(int64_t n_rows, int64_t n_cols, int32_t b, int64_t n_brows, const int64_t *brow_ptr,
+                 const int32_t *bcol, const double *bval, const double *x, double *y);
+
 /* ---------------------------------------------------------- CPU loops ---
  * OpenMP restatements of the reference's compute_using_cpu loops, with
  * zero-initialised output (the reference accumulated into malloc'd

@@ -174,6 +174,14 @@ int launch_slot_multi(const spmv_dims &d, bool sell, int32_t ki, int32_t C, int6
                       const int32_t *perm, int32_t K, int64_t ld, const int32_t *col, const double *val, int32_t k,
                       const double *X, int64_t ldx, double *Y, int64_t ldy);
 
+// block CSR (bsr.hip).  bsr_refusal: why the arrays of a BSR plan / run are
+// refused (NULL: they are accepted).  launch_bsr: bsr_kernel with L lanes per
+// block row on d.stream (d.nnz = the stored values, n_blocks * b * b).
+const char *bsr_refusal(const spmv_dims &d, int32_t b, int64_t n_brows, const int64_t *brow_ptr, const int32_t *bcol,
+                        const double *bval);
+int launch_bsr(const spmv_dims &d, int32_t b, int64_t n_brows, const int64_t *brow_ptr, const int32_t *bcol,
+               const double *bval, const double *x, double *y, int L);
+
 // ------------------------------------------------------- device helpers
 // Bijective blockIdx remap: blocks b and b+8 are dealt to the same XCD
 // (MI355X_MICROARCH.md §Workgroup dispatch), so give each such group a

@@ -77,6 +77,8 @@ struct spmv_plan {
     // geometry
     int32_t K = 0, C = 0, sigma = 0, ki = 0, h = 0, lanes = 0, variant = 0, xwin_rows = 0;
     int64_t ld = 0, n_slices = 0, n_strips = 0;
+    int32_t bsr_b = 0;    // BSR: the block size (ptr = brow_ptr, col = bcol, val = bval)
+    int64_t n_brows = 0;  // BSR: block rows
     // owned by the plan (device)
     void *win = nullptr;
     int32_t xcap = 0;

@@ -1,5 +1,5 @@
 // plan.hip — the per-format SpMV plans of the C-ABI (include/spmv.h):
-// spmv_plan_{coo,csr,ell,sell,cmrs} look at a matrix already in HBM ONCE,
+// spmv_plan_{coo,csr,ell,sell,cmrs,bsr} look at a matrix already in HBM ONCE,
 // choose the kernel path the measurements picked for it (x windows in LDS,
 // the small-matrix SELL kernel's head copy, the single-pass COO tail, the
 // entry-balanced CSR/CMRS tiles with their tile and big-tile plans, the
@@ -47,6 +47,7 @@ enum PlanPath {
     P_CMRS,
     P_CMRS_XWIN,
     P_CMRS_TILED,
+    P_BSR,
 };
 
 // CSR x-window plans build the 16-bit window-relative column copy by default
@@ -754,6 +755,41 @@ int spmv_plan_cmrs(spmv_dims d, int32_t h, int64_t n_strips, const int64_t *stri
     return finish(p, SPMV_SUCCESS, out);
 }
 
+// ------------------------------------------------------------------ BSR
+// Nothing is built: the kernel reads the caller's three arrays as they are
+// (owned_bytes = 0).  d.nnz = the stored values, n_blocks * b * b.
+int spmv_plan_bsr(spmv_dims d, int32_t b, int64_t n_brows, const int64_t *brow_ptr, const int32_t *bcol,
+                  const double *bval, const spmv_plan_opts *o, spmv_plan **out)
+{
+    if (!out)
+        return fail_msg(SPMV_OTHER_ERROR, "spmv_plan_bsr: out is NULL");
+    *out = nullptr;
+    if (const char *why = bsr_refusal(d, b, n_brows, brow_ptr, bcol, bval)) {
+        static thread_local char msg[128];
+        snprintf(msg, sizeof msg, "spmv_plan_bsr: %s", why);
+        return fail_msg(SPMV_OTHER_ERROR, msg);
+    }
+    const int64_t n_blocks = d.nnz / (b * b);
+    const int lanes = o && o->lanes > 0 ? o->lanes : spmv_bsr_auto_lanes(n_brows, n_blocks);
+    if (lanes < 2 || lanes > 64 || (lanes & (lanes - 1)))
+        return fail_msg(SPMV_OTHER_ERROR, "spmv_plan_bsr: opts.lanes must be 0 or a power of two in [2,64]");
+    spmv_plan *p = new_plan(SPMV_FMT_BSR, d, o);
+    if (!p)
+        return fail_msg(SPMV_OTHER_ERROR, "spmv_plan_bsr: out of host memory");
+    SPMV_GUARD(d);
+    p->path = P_BSR;
+    p->bsr_b = b;
+    p->n_brows = n_brows;
+    p->ptr = brow_ptr;
+    p->col = bcol;
+    p->val = bval;
+    p->lanes = lanes;
+    snprintf(p->kernel, sizeof p->kernel, "bsr_kernel");
+    snprintf(p->desc, sizeof p->desc, "BSR: %dx%d blocks, %d lanes per block row, %lld blocks streamed flat through LDS",
+             b, b, lanes, (long long)n_blocks);
+    return finish(p, SPMV_SUCCESS, out);
+}
+
 // ------------------------------------------------------------------ run
 int spmv_plan_run(const spmv_plan *p, const double *x, double *y, void *stream)
 {
@@ -820,6 +856,8 @@ int spmv_plan_run(const spmv_plan *p, const double *x, double *y, void *stream)
         }
         return spmv_cmrs_run_tiled_hot(d, p->h, p->n_strips, p->ptr, p->rin, col, p->val, x, y, H, p->hot, p->ws,
                                        p->ws_bytes);
+    case P_BSR:
+        return launch_bsr(d, p->bsr_b, p->n_brows, p->ptr, p->col, p->val, x, y, p->lanes);
     }
     return fail_msg(SPMV_OTHER_ERROR, "spmv_plan_run: corrupt plan");
 }
@@ -843,6 +881,8 @@ static const char *multi_refusal(const spmv_plan *p)
         return "spmv_plan_run_multi: COO plans have no multi-vector kernel";
     case SPMV_FMT_CMRS:
         return "spmv_plan_run_multi: CMRS plans have no multi-vector kernel";
+    case SPMV_FMT_BSR:
+        return "spmv_plan_run_multi: BSR plans have no multi-vector kernel";
     }
     return "spmv_plan_run_multi: corrupt plan";
 }

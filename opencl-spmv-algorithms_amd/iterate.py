@@ -419,9 +419,22 @@ def build_operator(m: sa.Coo, rank: int = 0, world: int = 1, fmt: str = "csr", d
     approaches the largest eigenvalue from below and AN UNDERESTIMATED lmax
     MAKES THE PRECONDITIONER INDEFINITE (CG may then break down or stall):
     that is what cheb_boost guards against; raise it, or pass cheb_bounds,
-    for a matrix on which ten steps are too few."""
+    for a matrix on which ten steps are too few.
+    fmt="bsr" (block=2, 3 or 4 and the other sa.to_device keywords through
+    fmt_kw): block CSR, for power_iteration, cg and bicgstab (no multi-vector
+    run: cg_multi and bicgstab_multi refuse).  On more than one rank align must
+    be a multiple of the block size."""
     def refuse_cheb(why):
         return sa.SpmvError(sa.OTHER_ERROR, "build_operator", f"chebyshev={chebyshev!r}: {why}")
+
+    if fmt in sa.BLOCK_FORMATS and world > 1:
+        # each rank blocks its own shard from its first row: bounds that cut a
+        # block row of the whole matrix would break its blocks apart
+        block = fmt_kw.get("block", 3)
+        if isinstance(block, (int, np.integer)) and not isinstance(block, bool) and block > 0 and align % block:
+            raise sa.SpmvError(sa.OTHER_ERROR, "build_operator",
+                               f'fmt="{fmt}" with block={block} on {world} ranks: align={align} must be a multiple of '
+                               "the block size (a shard bound would cut a block row)")
 
     if chebyshev is None:
         if cheb_bounds is not None:
@@ -491,6 +504,11 @@ def build_operator(m: sa.Coo, rank: int = 0, world: int = 1, fmt: str = "csr", d
     local, remote = split_local_remote(loc, layout, rank)
     return DistOperator(layout, rank, m.n_rows, HipKernels(sa.to_device(local, fmt, device, **fmt_kw)), device,
                         HipKernels(sa.to_device(remote, fmt, device, **fmt_kw)), overlap, precond(local))
+
+
+def _fmt_of(kernels) -> str:
+    """The format name of an operator's device matrix, for messages."""
+    return repr(getattr(getattr(kernels, "dm", None), "fmt", "?"))
 
 
 def _zeros(op, n):
@@ -757,7 +775,8 @@ def _cg_multi(op: DistOperator, B_loc, comm: Comm | None = None, tol: float = 1e
         raise sa.SpmvError(sa.OTHER_ERROR, "cg_multi", "split / overlap operators are not supported")
     if not getattr(k, "multi_supported", False):
         raise sa.SpmvError(sa.OTHER_ERROR, "cg_multi",
-                           "the operator's matrix has no multi-vector run (CSR, ELL and SELL plans have one)")
+                           f"the operator's {_fmt_of(k)} matrix has no multi-vector run (CSR, ELL and SELL plans "
+                           "have one)")
     nv = _check_block(op, B_loc)
     torch = sa._torch()
     rows = op.rows
@@ -1061,7 +1080,8 @@ def bicgstab_multi(op: DistOperator, B_loc, comm: Comm | None = None, tol: float
             raise sa.SpmvError(sa.OTHER_ERROR, "bicgstab_multi", "split / overlap operators are not supported")
         if not getattr(op.kernels, "multi_supported", False):
             raise sa.SpmvError(sa.OTHER_ERROR, "bicgstab_multi",
-                               "the operator's matrix has no multi-vector run (CSR, ELL and SELL plans have one)")
+                               f"the operator's {_fmt_of(op.kernels)} matrix has no multi-vector run (CSR, ELL "
+                               "and SELL plans have one)")
         _check_block(op, B_loc, "bicgstab_multi")
         return _bicgstab(op, comm or Comm(), M, B_loc, True, tol, maxit, check_every)
 

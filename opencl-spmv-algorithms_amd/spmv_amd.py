@@ -32,6 +32,8 @@ FORMATS = ("coo", "csr", "ell", "sell", "cmrs")  # the reference's five
 # SELL-C-σ with 16-bit column offsets; column-grouped CSR (gather-bound rows)
 EXTRA_FORMATS = ("csr16", "hyb", "csrf32", "sell16", "csrg")
 ALL_FORMATS = FORMATS + EXTRA_FORMATS
+# block formats: their own tuple, so the per-format sweeps over ALL_FORMATS stay what they were
+BLOCK_FORMATS = ("bsr",)
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec (MI355X_MICROARCH.md)
 
 # The reference's ReturnCode values (reference inc/enums.h:4-11).
@@ -178,6 +180,9 @@ HIP_SYMBOLS = {
     "spmv_plan_ell": (ctypes.c_int, [Dims, _c_i32, _c_i64, _c_i32, _vp, _vp, _PO, _PP]),
     "spmv_plan_sell": (ctypes.c_int, [Dims, _c_i32, _c_i32, _c_i32, _c_i64, _vp, _vp, _vp, _vp, _PO, _PP]),
     "spmv_plan_cmrs": (ctypes.c_int, [Dims, _c_i32, _c_i64, _vp, _vp, _vp, _vp, _PO, _PP]),
+    "spmv_bsr_auto_lanes": (ctypes.c_int, [_c_i64, _c_i64]),
+    "spmv_plan_bsr": (ctypes.c_int, [Dims, _c_i32, _c_i64, _vp, _vp, _vp, _PO, _PP]),
+    "spmv_bsr_run": (ctypes.c_int, [Dims, _c_i32, _c_i64, _vp, _vp, _vp, _vp, _vp, ctypes.c_int]),
     "spmv_plan_run": (ctypes.c_int, [_vp, _vp, _vp, _vp]),
     "spmv_plan_run_multi": (ctypes.c_int, [_vp, _c_i32, _vp, _c_i64, _vp, _c_i64, _vp]),
     "spmv_plan_multi_supported": (ctypes.c_int, [_vp]),
@@ -417,6 +422,9 @@ HOST_SYMBOLS = {
     "spmv_csrg_block_rows": (_c_i32, []),
     "spmv_csrg_plan": (ctypes.c_int, [_c_i64, _vp, _vp, _c_i32, ctypes.POINTER(_c_i64)]),
     "spmv_csrg_fill": (ctypes.c_int, [_c_i64, _vp, _vp, _vp, _c_i32, _vp, _vp, _vp, _vp, _vp]),
+    "spmv_bsr_plan": (ctypes.c_int, [_c_i64, _c_i64, _vp, _vp, _c_i32, ctypes.POINTER(_c_i64), ctypes.POINTER(_c_i64)]),
+    "spmv_bsr_fill": (ctypes.c_int, [_c_i64, _c_i64, _vp, _vp, _vp, _c_i32, _vp, _vp, _vp]),
+    "spmv_cpu_bsr": (ctypes.c_int, [_c_i64, _c_i64, _c_i32, _c_i64, _vp, _vp, _vp, _vp, _vp]),
     "spmv_cpu_coo": (ctypes.c_int, [_c_i64, _c_i64, _vp, _vp, _vp, _vp, _vp, ctypes.c_int]),
     "spmv_cpu_csr": (ctypes.c_int, [_c_i64, _vp, _vp, _vp, _vp, _vp, ctypes.c_int]),
     "spmv_cpu_csr_multi": (ctypes.c_int, [_c_i64, _vp, _vp, _vp, _c_i32, _vp, _c_i64, _vp, _c_i64]),
@@ -1000,6 +1008,60 @@ def csrg_build(n_rows: int, ptr, col, val, groups: int = 4):
                                    _ptr(val_g), _ptr(blk_off), _ptr(pair_row)), "csrg_fill")
     return dict(groups=groups, n_pairs=n, nb=nb, pair_ptr=pair_ptr, col_g=col_g, val_g=val_g, blk_off=blk_off,
                 pair_row=pair_row)
+
+
+BSR_MAX_B = 8  # SPMV_BSR_MAX_B (spmv_host.h): the host builder's block sizes; the device runs 2, 3 and 4
+
+
+def bsr_build(n_rows: int, n_cols: int, ptr, col, val, b: int):
+    """Block CSR with b x b blocks from a CSR (spmv_bsr_plan / spmv_bsr_fill,
+    spmv_host.h, which states the layout and the fill-in rule): brow_ptr
+    (n_brows + 1, int64), bcol (n_blocks, int32, ascending inside a block row),
+    bval (n_blocks * b * b, float64, scipy's data[blk, r, c]); fill = stored
+    values / entries (0.0 for an empty matrix)."""
+    lib = host_lib()
+    nbr, nbl = _c_i64(0), _c_i64(0)
+    _check_host(lib.spmv_bsr_plan(n_rows, n_cols, _ptr(ptr), _ptr(col), b, ctypes.byref(nbr), ctypes.byref(nbl)),
+                "bsr_plan")
+    brow_ptr = np.empty(nbr.value + 1, np.int64)
+    bcol = np.empty(nbl.value, np.int32)
+    bval = np.empty(nbl.value * b * b, np.float64)
+    _check_host(lib.spmv_bsr_fill(n_rows, n_cols, _ptr(ptr), _ptr(col), _ptr(val), b, _ptr(brow_ptr), _ptr(bcol),
+                                  _ptr(bval)), "bsr_fill")
+    nnz = int(ptr[n_rows]) - int(ptr[0]) if n_rows > 0 else 0
+    return dict(b=b, n_brows=nbr.value, n_blocks=nbl.value, brow_ptr=brow_ptr, bcol=bcol, bval=bval,
+                fill=nbl.value * b * b / nnz if nnz else 0.0)
+
+
+def bsr_stored_bytes(s: dict) -> int:
+    """Bytes of the three BSR arrays of bsr_build's dict."""
+    return 8 * s["n_blocks"] * s["b"] ** 2 + 4 * s["n_blocks"] + 8 * (s["n_brows"] + 1)
+
+
+def bsr_check_fill(n_rows: int, nnz: int, s: dict, bsr_max_fill: float | None = None) -> None:
+    """to_device's acceptance rule for bsr_build's dict `s`: None raises
+    SpmvError when the BSR arrays are not smaller than CSR's
+    12 nnz + 8 (n_rows + 1) bytes (a derived break-even, not a measured one); a
+    float raises when fill exceeds it (float("inf"): never)."""
+    b, stored, csr_bytes = s["b"], bsr_stored_bytes(s), 12 * nnz + 8 * (n_rows + 1)
+    if bsr_max_fill is None and stored >= csr_bytes:
+        raise SpmvError(OTHER_ERROR, "bsr_build", f"{b}x{b} blocks store {stored} bytes (fill {s['fill']:.3f}), "
+                        f"not fewer than CSR's {csr_bytes}")
+    if bsr_max_fill is not None and s["fill"] > float(bsr_max_fill):
+        raise SpmvError(OTHER_ERROR, "bsr_build", f"{b}x{b} blocks: fill {s['fill']:.3f} > {float(bsr_max_fill)}")
+
+
+def cpu_bsr(n_rows: int, n_cols: int, b: int, brow_ptr, bcol, bval, x: np.ndarray, y: np.ndarray) -> None:
+    """y = A x from the BSR arrays on the CPU (spmv_cpu_bsr: the plain loop,
+    the host statement of a BSR plan's run).  x float64 (>= n_cols), y
+    float64 (>= n_rows), both C-contiguous; y[:n_rows] is overwritten."""
+    for a, n, what in ((x, n_cols, "x"), (y, n_rows, "y")):
+        if not isinstance(a, np.ndarray) or a.dtype != np.float64 or a.ndim != 1 or not a.flags.c_contiguous:
+            raise SpmvError(OTHER_ERROR, "cpu_bsr", f"{what} must be a contiguous 1-D float64 array")
+        if a.shape[0] < n:
+            raise SpmvError(OTHER_ERROR, "cpu_bsr", f"{what} is too short")
+    _check_host(host_lib().spmv_cpu_bsr(n_rows, n_cols, b, int(brow_ptr.shape[0]) - 1, _ptr(brow_ptr), _ptr(bcol),
+                                        _ptr(bval), _ptr(x), _ptr(y)), "cpu_bsr")
 
 
 def partition_rows(n_rows: int, ptr: np.ndarray, parts: int, align: int = 1024,
@@ -1769,13 +1831,33 @@ def _plan_cmrs(dm, *, variant=None, xwin=None, hot=None):
     dm.stored_bytes = 13 * dm.nnz + 8 * (p["n_strips"] + 1)
 
 
+def _plan_bsr(dm, b, n_blocks, fill, *, lanes=0):
+    """The C plan of a BSR matrix (spmv_plan_bsr): d.nnz is the stored values
+    n_blocks * b * b, while dm.nnz stays the matrix's entries (bytes_alg)."""
+    a = dm.arrays
+    d = dm.dims()
+    d.nnz = n_blocks * b * b
+    n_brows = (dm.n_rows + b - 1) // b
+    plan = _vp()
+    _check(hip_lib().spmv_plan_bsr(d, b, n_brows, _ptr(a["brow_ptr"]), _ptr(a["bcol"]), _ptr(a["bval"]),
+                                   ctypes.byref(plan_opts(lanes=int(lanes))), ctypes.byref(plan)), "spmv_plan_bsr")
+    dm.plan = plan
+    info = PlanInfo()
+    _check(hip_lib().spmv_plan_get_info(plan, ctypes.byref(info)), "spmv_plan_get_info")
+    for k in _PLAN_INFO_KEYS:
+        dm.params[k] = int(getattr(info, k))
+    dm.params.update(kernel=info.kernel.decode(), plan=info.desc.decode(), format=int(info.format), b=b,
+                     n_brows=n_brows, n_blocks=n_blocks, fill=fill)
+    dm.stored_bytes = 8 * n_blocks * b * b + 4 * n_blocks + 8 * (n_brows + 1)
+
+
 def to_device(m: Coo, fmt: str, device="cuda:0", *, lanes: int = 0, variant: int = 0, ki: int = 0, C: int = 64,
               sigma: int = 1024, h: int = 8, ell_max_padding: float | None = 64.0,
               xwin: bool | None = None, xwin_rows: int = 0, split: int | None = None,
               cmrs_variant: int | None = None, hot: int | None = None,
               csr16_max_escape: float | None = 0.5, groups: int = 0, head: bool = True,
               sell_head: bool | None = None, coo_tail: bool | None = None, bigplan: bool = True,
-              hyb_k: int = 0) -> DeviceMatrix:
+              hyb_k: int = 0, block: int = 3, bsr_max_fill: float | None = None) -> DeviceMatrix:
     """Build `fmt` on the host (libspmv_host.so), upload it and, for the
     reference's five formats and SELL16, create its C plan (spmv.h): the
     library picks the kernel path — x windows in LDS (CSR, ELL, SELL, CMRS
@@ -1788,7 +1870,13 @@ def to_device(m: Coo, fmt: str, device="cuda:0", *, lanes: int = 0, variant: int
     copy where the small-matrix kernel runs), coo_tail (None = the single
     pass where the tail plan accepts the matrix, True = it or raise, False =
     the carry pass), bigplan (tiled CSR's big-tile plan), hyb_k (HYB's ELL
-    width: 0 = spmv_hyb_plan's rule, K > 0 forced)."""
+    width: 0 = spmv_hyb_plan's rule, K > 0 forced).
+    fmt "bsr" (BLOCK_FORMATS): block CSR with block x block blocks (2, 3 or
+    4) through spmv_plan_bsr; lanes = the lanes per block row (0 = the rule).
+    bsr_max_fill: None = raise SpmvError, as ELL and CSR16 do, when the BSR
+    arrays are not smaller than CSR's 12 nnz + 8 (n_rows + 1) bytes (a derived
+    break-even, not a measured one); a float = refuse a fill (stored values /
+    entries) above it; float("inf") = no check."""
     torch = _torch()
     device = torch.device(device)
     dm = DeviceMatrix(fmt, m.n_rows, m.n_cols, m.nnz, device)
@@ -1933,6 +2021,15 @@ def to_device(m: Coo, fmt: str, device="cuda:0", *, lanes: int = 0, variant: int
                          row_in_strip=_dev_tensor(c["row_in_strip"], device),
                          col=_dev_tensor(col, device), val=_dev_tensor(val, device))
         _plan_cmrs(dm, variant=cmrs_variant, xwin=xwin, hot=hot)
+    elif fmt == "bsr":
+        if isinstance(block, bool) or not isinstance(block, (int, np.integer)) or block not in (2, 3, 4):
+            raise SpmvError(OTHER_ERROR, "to_device", f"bsr: block must be 2, 3 or 4, not {block!r}")
+        b = int(block)
+        s = bsr_build(m.n_rows, m.n_cols, ptr, col, val, b)
+        bsr_check_fill(m.n_rows, m.nnz, s, bsr_max_fill)
+        dm.arrays = dict(brow_ptr=_dev_tensor(s["brow_ptr"], device), bcol=_dev_tensor(s["bcol"], device),
+                         bval=_dev_tensor(s["bval"], device))
+        _plan_bsr(dm, b, s["n_blocks"], s["fill"], lanes=lanes)
     else:
         raise SpmvError(OTHER_ERROR, "to_device", f"unknown format {fmt}")
     return dm
