@@ -41,7 +41,7 @@ LIB_HIP  := $(LIBDIR)/libspmv_hip.so
 LIB_HOST := $(LIBDIR)/libspmv_host.so
 ORACLE   := oracle/liboracle.so
 
-.PHONY: all default lib oracle probes lab test-san test-san-transpose test-san-transpose-multi test-san-multi-plan test-san-symmetric test-san-symmetric-multi test-san-precond test-san-cheb test-san-bicgstab test-san-bsr test-cpu test-gpu clean $(TARGETS)
+.PHONY: all default lib oracle probes lab test-san test-san-transpose test-san-transpose-multi test-san-multi-plan test-san-symmetric test-san-symmetric-multi test-san-precond test-san-cheb test-san-bicgstab test-san-bsr test-san-block test-cpu test-gpu clean $(TARGETS)
 
 default: all
 all: lib $(TARGETS) probes
@@ -234,6 +234,17 @@ build/san/bsr_harness: tests/san/bsr_harness.c $(HOST_SRC) include/spmv_host.h i
 
 test-san-bsr: build/san/bsr_harness
 	$(SANENV) ASAN_OPTIONS=detect_leaks=1:exitcode=99 build/san/bsr_harness tests/golden/*.mtx
+
+# the host statement of LOBPCG's block combine (spmv_cpu_block_combine_multi)
+# under ASan + UBSan: a stand-alone program with exactly-sized buffers, every
+# operand count, ld == width and ld > width, n = 0 and the refused inputs
+# (tests/san/block_harness.c)
+build/san/block_harness: tests/san/block_harness.c $(HOST_SRC) include/spmv_host.h include/spmv_rc.h
+	@mkdir -p build/san
+	$(CC) -std=c11 -Wall -Wextra -Werror -fopenmp -Iinclude $(SANFLAGS) $< $(HOST_SRC) -o $@ -lm
+
+test-san-block: build/san/block_harness
+	$(SANENV) ASAN_OPTIONS=detect_leaks=1:exitcode=99 build/san/block_harness
 
 test-gpu: all oracle
 	python -m pytest tests/ -x -q -m gpu

@@ -480,6 +480,47 @@ int spmv_bicgstab_dir_multi(int64_t n, int32_t k, const double *rho_new, const d
                             const double *tt, const double *ts, const double *V, int64_t ldv,
                             const double *R, int64_t ldr, double *P, int64_t ldp, int device,
                             void *stream);
+/* The two block kernels of the LOBPCG eigensolver (iterate.lobpcg), by the
+ * conventions of the block vector kernels above: row-major blocks V[i*ld + j],
+ * j < k <= ld, 8-byte alignment only (16-byte loads only where the base and ld
+ * of a block allow them); nothing outside [i*ld, i*ld + k), i < n, is read or
+ * written; asynchronous on `stream`, no allocation, no synchronisation
+ * (capturable); no atomics.  SPMV_OTHER_ERROR, before anything is written, for
+ * n < 0, a width out of range, a leading dimension below the width, a NULL
+ * argument that would be read or written or a workspace that is too small.
+ *
+ * spmv_gram_multi: out[a*kb + b] = sum_i A[i][a] B[i][b], a < ka, b < kb,
+ * 1 <= ka, kb <= 24 (three blocks of 8), in one pass: a thread owns a row and
+ * a 4 x 4 tile of the pairs, so a block is read once per 4 columns of the
+ * other.  out is a device array of ka*kb doubles; n == 0 writes ka*kb zeros;
+ * ws holds spmv_gram_multi_ws_bytes(n, ka, kb) bytes.  Every sum goes through
+ * spmv_dot_multi's fixed tree (the same workgroups, rows, accumulator pair and
+ * final kernel): out[a*kb + b] is bit for bit what spmv_dot_multi(n, 1, A + a,
+ * lda, B + b, ldb, ...) gives, whatever ka, kb, the position of the columns,
+ * lda / ldb, the alignment or the load width; with A == B, out[a*kb + b] and
+ * out[b*kb + a] are bit-equal.  A may be B, and the two may overlap (both are
+ * only read).  At most FOUR stage-1 launches (whole tiles and the columns left
+ * of A times those of B) and one final launch.
+ *
+ * spmv_block_combine_multi: Y[i][c] = sum_r S[i][r] C[r*kc + c], c < kc, with
+ * S = [A0 A1 A2] side by side (ka0 + ka1 + ka2 columns), 1 <= kc <= 8,
+ * 0 <= ka <= 8 each (0: the operand is absent and its pointer ignored) and at
+ * least one operand present.  C is a HOST array of (ka0 + ka1 + ka2) * kc
+ * doubles: it is read before the call returns and travels in the kernel
+ * arguments (at most 1,536 bytes), nothing is uploaded and no scalar lives on
+ * the device (the convention of spmv_bjacobi_cheb_step_multi's a and b).
+ * Every element is the fma chain s = 0.0; s = fma(S[i][r], C[r*kc + c], s) for
+ * r = 0, 1, ... in that order: the device form of spmv_cpu_block_combine_multi
+ * (spmv_host.h), which fixes every bit whatever the widths, the leading
+ * dimensions, the alignment or the load width.  Y must not overlap an operand;
+ * the operands may overlap each other.  One launch; n == 0 writes nothing. */
+size_t spmv_gram_multi_ws_bytes(int64_t n, int32_t ka, int32_t kb);
+int spmv_gram_multi(int64_t n, int32_t ka, const double *A, int64_t lda, int32_t kb, const double *B,
+                    int64_t ldb, double *out, void *ws, size_t ws_bytes, int device, void *stream);
+int spmv_block_combine_multi(int64_t n, int32_t kc, const double *C, int32_t ka0, const double *A0,
+                             int64_t lda0, int32_t ka1, const double *A1, int64_t lda1, int32_t ka2,
+                             const double *A2, int64_t lda2, double *Y, int64_t ldy, int device,
+                             void *stream);
 /* Block-Jacobi preconditioner M = blockdiag(D_0, D_1, ...), bs x bs blocks of
  * the diagonal, 1 <= bs <= 16, for the CG solvers of iterate.py (cg, cg_multi).
  * spmv_bjacobi_build (spmv_host.h) defines the blocks (col_base,

@@ -476,6 +476,22 @@ int spmv_cpu_bicgstab_update_multi(int64_t n, int32_t k, const double *a_num, co
 int spmv_cpu_bicgstab_dir_multi(int64_t n, int32_t k, const double *rho_new, const double *rv,
                                 const double *tt, const double *ts, const double *V, int64_t ldv,
                                 const double *R, int64_t ldr, double *P, int64_t ldp);
+/* The block combine of the LOBPCG eigensolver (iterate.lobpcg) on row-major
+ * blocks (V[i*ld + j], i < n, j < k <= ld): with S = [A0 A1 A2] side by side
+ * (ka0 + ka1 + ka2 columns; ka = 0: the operand is absent and its pointer
+ * ignored) and C a row-major (ka0 + ka1 + ka2) x kc matrix,
+ *   Y[i][c] = s after  s = 0.0;  s = fma(S[i][r], C[r*kc + c], s), r = 0, 1, ...
+ * This fixes the bits of every element: the CPU statement of
+ * spmv_block_combine_multi (spmv_ext.h).  A zero in C does not skip a term, so
+ * an Inf or NaN in S[i][r] reaches every Y[i][c].  A row of S is read before
+ * that row of Y is written; Y must not overlap an operand otherwise.  Nothing is
+ * read or written outside the columns of a row or at or past row n.
+ * SPMV_OTHER_ERROR, before anything is written, for a negative n, kc outside
+ * 1..8, a ka outside 0..8 or all three 0, a leading dimension below its width,
+ * or a NULL array that would be read or written.                             */
+int spmv_cpu_block_combine_multi(int64_t n, int32_t kc, const double *C, int32_t ka0, const double *A0,
+                                 int64_t lda0, int32_t ka1, const double *A1, int64_t lda1, int32_t ka2,
+                                 const double *A2, int64_t lda2, double *Y, int64_t ldy);
 /* Y = A^T X for k >= 1 vectors stored row-major, the layout of
  * spmv_plan_run_t_multi (spmv.h): X[r*ldx + j], r < n_rows; Y[c*ldy + j],
  * c < n_cols; j < k; ldx >= k, ldy >= k.  Serial: zeroes Y[c*ldy + j], j < k,

@@ -1,5 +1,5 @@
 """iterate.py — iterated SpMV over row shards: power iteration, CG,
-multi-right-hand-side CG and BiCGSTAB.
+multi-right-hand-side CG, BiCGSTAB and the LOBPCG eigensolver.
 
 SURVEY.md §8f row 3: "Iterated SpMV (power iteration / CG) reusing the y
 all-gather as the next x".  The reference stops after one SpMV (reference
@@ -57,6 +57,13 @@ BiCGSTAB on the same layout, products and device-resident scalars, one
 recurrence per column, with three fused block kernels of its own
 (spmv_dot2_multi, spmv_bicgstab_update_dot_multi, spmv_bicgstab_dir_multi) so
 that an iteration is 10 launches; block Jacobi is its preconditioner.
+
+Eigenpairs (lobpcg): the k <= 8 smallest or largest eigenpairs of a symmetric
+operator by LOBPCG in its orthonormal-basis form, on the multi-vector products,
+the block-Jacobi apply and two block kernels of its own (spmv_gram_multi,
+spmv_block_combine_multi; csrc/block.hip).  Its small Gram matrices visit the
+host every iteration (Cholesky, a 3k x 3k eigenproblem); everything of the
+matrix's length stays on the device.
 
 The device work goes through a `kernels` object (HipKernels by default).
 Tests substitute a numpy double to exercise the multi-rank orchestration on
@@ -315,6 +322,32 @@ class HipKernels:
                                                    sa._ptr(ts), sa._ptr(V), self._ld(V), sa._ptr(R), self._ld(R),
                                                    sa._ptr(P), self._ld(P), self.dev.index or 0, self._s()),
                   "spmv_bicgstab_dir_multi")
+
+    # the block kernels of LOBPCG (csrc/block.hip)
+    def gram(self, n, A, B, out, ws) -> None:
+        """out[a * kb + b] = sum over the first n rows of A[:, a] B[:, b], for
+        blocks of ka and kb <= 24 columns (A may be B); ws: gram_ws(n, ka, kb)."""
+        sa._check(self.lib.spmv_gram_multi(n, A.shape[1], sa._ptr(A), self._ld(A), B.shape[1], sa._ptr(B),
+                                           self._ld(B), sa._ptr(out), sa._ptr(ws), ws.numel(), self.dev.index or 0,
+                                           self._s()), "spmv_gram_multi")
+
+    def gram_ws(self, n, ka, kb):
+        torch = sa._torch()
+        nbytes = self.lib.spmv_gram_multi_ws_bytes(n, ka, kb)
+        return torch.empty(nbytes, dtype=torch.uint8, device=self.dev)
+
+    def block_combine(self, n, C, blocks, Y) -> None:
+        """Y[:n, :kc] = [blocks[0] blocks[1] blocks[2]] C: 1 to 3 blocks of up to
+        8 columns, C a HOST (sum of their widths, kc <= 8) matrix that travels in
+        the kernel arguments.  Y must not overlap a block."""
+        C, kc = sa.combine_matrix(C, blocks, "block_combine")
+        args = []
+        for q in range(3):
+            t = blocks[q] if q < len(blocks) else None
+            args += [0, None, 0] if t is None else [t.shape[1], sa._ptr(t), self._ld(t)]
+        ldy = Y.stride(0) if Y.shape[0] > 1 else kc
+        sa._check(self.lib.spmv_block_combine_multi(n, kc, sa._ptr(C), *args, sa._ptr(Y), ldy, self.dev.index or 0,
+                                                    self._s()), "spmv_block_combine_multi")
 
     # the preconditioner M (sa.BlockJacobi over this rank's n rows):
     # Z = M^-1 R, out[:k] = column sums of R Z, out[k:2k] of R R
@@ -1207,3 +1240,325 @@ def _bicgstab(op: DistOperator, comm: Comm, M, B, multi: bool, tol: float, maxit
     live = bb > 0.0
     rel[live] = np.sqrt(np.maximum(res[live], 0.0) / bb[live])
     return X, it, rel
+
+
+# ------------------------------------------------------------------- LOBPCG
+def lobpcg(op: DistOperator, k: int | None = None, X0=None, largest: bool = False, tol: float = 1e-8,
+           atol: float = 0.0, maxit: int = 500, precond=None, comm: Comm | None = None, seed: int = 0):
+    """The k <= 8 smallest (largest=True: largest) eigenpairs of the symmetric
+    operator `op` by LOBPCG, on the operator's kernel stream (_lobpcg has the
+    method).  k defaults to X0's width, or to 1 without an X0.  Returns
+    (lam, X, iterations, res): lam a numpy (k,) array, ascending (descending for
+    `largest`); X this rank's (rows, k) block with X^T X = I; res[j] the TRUE
+    residual ||A x_j - lam_j x_j||_2, computed afresh from one extra product
+    after the loop (the rule of bicgstab's rel), lam_j the Rayleigh quotient of
+    x_j from that same product.  Column j has converged when
+    res_j <= tol |lam_j| + atol; the loop ends when every column has, or at
+    maxit.
+
+    Every operator cg_multi runs on: unsplit operators whose matrix has a
+    multi-vector run, symmetric="fused" | "expand", several ranks.  precond as
+    for cg (_precond_of): the operator's block-Jacobi preconditioner by default,
+    False for none; a Chebyshev one is refused.  X0: a float64 (rows, k) tensor
+    on the operator's device with independent columns; default
+    numpy.random.default_rng(seed).standard_normal((n, k)) indexed by GLOBAL
+    row, so the start does not depend on the number of ranks.  Refused before
+    any device work: k outside 1..8, 3k > n, a non-square operator, a format
+    without a multi-vector run, an X0 of the wrong shape or dtype."""
+    with _kernel_stream(op):
+        M = _precond_of(op, precond)
+        if isinstance(M, Chebyshev):
+            raise sa.SpmvError(sa.OTHER_ERROR, "lobpcg",
+                               "a Chebyshev preconditioner is not supported: use block Jacobi or none")
+        k = _lobpcg_check(op, k, X0)
+        return _lobpcg(op, k, X0, bool(largest), float(tol), float(atol), int(maxit), M, comm or Comm(), seed)
+
+
+def _lobpcg_check(op, k, X0) -> int:
+    """The refusals of lobpcg, all before any device work; returns k."""
+    torch = sa._torch()
+
+    def refuse(why):
+        return sa.SpmvError(sa.OTHER_ERROR, "lobpcg", why)
+
+    kn = op.kernels
+    if op.remote is not None:
+        raise refuse("split / overlap operators are not supported")
+    if not getattr(kn, "multi_supported", False):
+        raise refuse(f"the operator's {_fmt_of(kn)} matrix has no multi-vector run (CSR, ELL and SELL plans have one)")
+    # a shard of a square matrix: this rank's rows, and columns either in the
+    # gathered layout or (the stored half of symmetric=...) the matrix's own
+    mat = getattr(kn, "dm", None)
+    shape = (mat.n_rows, mat.n_cols) if mat is not None else getattr(getattr(kn, "A", None), "shape", None)
+    if shape is not None and (shape[0] != op.rows or shape[1] not in (op.n, op.world * op.pad)):
+        raise refuse(f"the operator is not square ({op.n} rows, a {shape[0]} x {shape[1]} shard on {op.world} ranks)")
+    if X0 is not None:
+        if not isinstance(X0, torch.Tensor) or X0.dtype != torch.float64:
+            raise refuse("X0 must be a float64 tensor")
+        if X0.dim() != 2 or X0.shape[0] != op.rows or (k is not None and X0.shape[1] != k):
+            raise refuse(f"X0 must be ({op.rows}, k), not {tuple(X0.shape)}")
+        here = torch.device(op.device if op.device is not None else "cpu")
+        if X0.device.type != here.type or (X0.device.index or 0) != (here.index or 0):
+            raise refuse(f"X0 must be on {here}")
+        k = int(X0.shape[1])
+    k = 1 if k is None else k
+    if not isinstance(k, (int, np.integer)) or isinstance(k, bool) or not 1 <= k <= 8:
+        raise refuse(f"k must be in 1..8, not {k!r}")
+    if 3 * k > op.n:
+        raise refuse(f"k = {k} needs a basis of 3k = {3 * k} vectors, the matrix has {op.n} rows")
+    return int(k)
+
+
+def _chol_inverse(G: np.ndarray):
+    """R^-1 for the Gram matrix G = R^T R of a block V (V R^-1 is orthonormal),
+    or None when G is not numerically positive definite.  G is scaled to a unit
+    diagonal first, so a column of V that is tiny against the others (a
+    converged residual) does not by itself make the factorisation fail."""
+    with np.errstate(invalid="ignore", divide="ignore"):
+        d = np.sqrt(np.diag(G))
+        if not (np.isfinite(d).all() and (d > 0.0).all()):
+            return None
+        Gs = G / np.outer(d, d)
+    Gs = 0.5 * (Gs + Gs.T)
+    if not np.isfinite(Gs).all():
+        return None
+    try:
+        L = np.linalg.cholesky(Gs)
+    except np.linalg.LinAlgError:
+        return None
+    Rinv = np.linalg.inv(L).T / d[:, None]
+    return Rinv if np.isfinite(Rinv).all() else None
+
+
+def _ortho_matrix(B: np.ndarray, G: np.ndarray):
+    """The matrix C of one projection + Cholesky-QR pass of a block V against
+    an orthonormal basis Q: with B = Q^T V (q x k, q may be 0) and G = V^T V,
+    (V - Q B) has the Gram matrix G - B^T B = R^T R, and [Q V] C with
+    C = [-B R^-1; R^-1] is orthonormal and orthogonal to Q.  None when the
+    factorisation fails."""
+    Rinv = _chol_inverse(G - B.T @ B)
+    return None if Rinv is None else np.vstack([-B @ Rinv, Rinv])
+
+
+def _lobpcg(op: DistOperator, k: int, X0, largest: bool, tol: float, atol: float, maxit: int, M, comm: Comm, seed):
+    """LOBPCG (locally optimal block preconditioned CG) in the orthonormal-basis
+    form of Hetmaniuk and Lehoucq, standard problem, no locking.  The basis
+    S = [X W P] is ONE row-major (rows, 3k) block and AS = [AX AW AP] another,
+    so that a Gram matrix over any part of the basis is one kernel.
+
+    Per iteration:
+        R = AX - X diag(lam)                       block_combine of [AX X]
+        W = M^-1 R (precond_apply), or R itself
+        W: projected against X and orthonormalised, twice:
+           gram ([X W]^T W), host Cholesky of W^T W - B^T B, block_combine
+        AW = A W                                   the ONE spmm
+        P: projected against X and W and orthonormalised in the same way,
+           AP following by the same combinations of [AX AW AP]
+        T = S^T A S                                one gram, 3k x 3k
+        numpy.linalg.eigh(T) on the host: C
+        X+ = S C, AX+ = AS C, P+ = [W P] C_WP, AP+ likewise: block_combine
+           into the spare pair of blocks, which is then swapped in
+    The first iteration, and one whose P fails its Cholesky factorisation (a
+    restart), run on [X W].  A factorisation of W's Gram matrix that fails ends
+    the loop: the residual has then reached rounding.  A rank-deficient X0
+    raises SpmvError.
+
+    THE SMALL MATRICES GO TO THE HOST: every group of Gram matrices computed
+    together is all-reduced once (Comm) and read by the host, which
+    synchronises with the stream, five times per iteration.  That is inherent
+    in the method (the Cholesky factors and the 3k x 3k eigenproblem are host
+    work); everything of length `rows` stays on the device, and C travels back
+    in kernel arguments.
+
+    The stop test runs on the recurrence's residual (AX is carried along, not
+    recomputed).  When it passes, lam and the true residual are computed from one
+    extra product (lam_j = x_j^T A x_j / x_j^T x_j: the carried Ritz values and
+    AX gather about one rounding of ||A|| per iteration); if those do not pass,
+    the fresh A X and lam replace the carried ones and the loop goes on.  The
+    returned lam and res are always the fresh ones.
+
+    With a forward or symmetric="expand" operator every kernel is deterministic
+    (fixed reduction trees, fma chains in a fixed order) and so is the host
+    step: two calls with the same arguments return the same bits.
+    symmetric="fused" is not reproducible (its product is not)."""
+    torch = sa._torch()
+    kn = op.kernels
+    rows, n = op.rows, op.n
+
+    def zeros(*shape):
+        return torch.zeros(shape, dtype=torch.float64, device=op.device)
+
+    def cols(T, j):  # block j of a basis block: X, W, P = 0, 1, 2
+        return T[:, j * k:(j + 1) * k]
+
+    # two (S, AS) pairs: the combinations of an iteration's end write the spare
+    # one.  S has `pad` rows: alone, its W columns are the product's input.
+    pairs = [(zeros(op.pad, 3 * k), zeros(max(rows, 1), 3 * k)) for _ in range(2)]
+    t1, t2, t3 = (zeros(max(rows, 1), k) for _ in range(3))
+    if comm.world > 1:
+        send, full = zeros(op.pad, k), zeros(op.world * op.pad, k)
+        apply_shared = _Apply(op, comm, full, send, multi=True)
+    else:
+        applies = {id(S): _Apply(op, comm, cols(S, 1), cols(S, 1), multi=True) for S, _ in pairs}
+
+    def product(S, AS):  # AW = A W
+        if comm.world > 1:
+            send[:rows].copy_(cols(S, 1)[:rows])
+            apply_shared(cols(AS, 1))
+        else:
+            applies[id(S)](cols(AS, 1))
+
+    gout = zeros(9 * k * k + k)
+    ws = kn.gram_ws(rows, 3 * k, 3 * k)
+    ws_dot, ws_dot2 = kn.dot_multi_ws(rows, k), kn.dot_multi_ws(rows, 2 * k)
+
+    def grams(*blocks, norms=None):
+        """One group: the Gram matrices of the (A, B) pairs, and the column
+        sums of squares of `norms`, in one all-reduce and one host read."""
+        off = 0
+        shapes = []
+        for A, B in blocks:
+            ka, kb = A.shape[1], B.shape[1]
+            kn.gram(rows, A, B, gout[off:off + ka * kb], ws)
+            shapes.append((ka, kb))
+            off += ka * kb
+        if norms is not None:
+            kn.dot_multi(rows, norms, norms, gout[off:off + k], ws_dot)
+            off += k
+        comm.allreduce(gout[:off])
+        host = gout[:off].cpu().numpy()
+        out, off = [], 0
+        for ka, kb in shapes:
+            out.append(host[off:off + ka * kb].reshape(ka, kb).copy())
+            off += ka * kb
+        if norms is not None:
+            out.append(host[off:off + k].copy())
+        return out
+
+    def residual_matrix(lam):  # R = [AX X] [I; -diag(lam)]
+        return np.vstack([np.eye(k), -np.diag(lam)])
+
+    (S, AS), (S2, AS2) = pairs
+    X, W = cols(S, 0), cols(S, 1)
+    # start: X0 -> t1, orthonormalised twice into W's place (the product's
+    # input), AW = A W, then Rayleigh-Ritz on that block alone into X, AX
+    if X0 is None:
+        start = np.random.default_rng(seed).standard_normal((n, k))[op.lo:op.lo + rows]
+        t1[:rows].copy_(torch.from_numpy(np.ascontiguousarray(start)))
+    else:
+        t1[:rows].copy_(X0)
+    none = np.zeros((0, k))
+    for src, dst in ((t1, t2), (t2, W)):
+        (G,) = grams((src, src))
+        C = _ortho_matrix(none, G)
+        if C is None:
+            raise sa.SpmvError(sa.OTHER_ERROR, "lobpcg", "X0 is rank-deficient (its Gram matrix has no Cholesky "
+                                                         "factorisation)")
+        kn.block_combine(rows, C, [src], dst)
+    product(S, AS)
+    (T,) = grams((W, cols(AS, 1)))
+    lam, V = np.linalg.eigh(0.5 * (T + T.T))
+    order = np.argsort(-lam if largest else lam, kind="stable")
+    lam, V = lam[order], np.ascontiguousarray(V[:, order])
+    kn.block_combine(rows, V, [W], X)
+    kn.block_combine(rows, V, [cols(AS, 1)], cols(AS, 0))
+
+    def converged(res, lam):
+        return bool((res <= tol * np.abs(lam) + atol).all())
+
+    def true_residual(S, AS):
+        """(lam, res) afresh from one more product: X goes through W's place,
+        whose old content no later step reads; lam_j is the Rayleigh quotient
+        x_j^T (A x_j) / x_j^T x_j of the fresh product (the carried Ritz value
+        has the drift of the carried AX in it) and res_j = ||A x_j - lam_j x_j||."""
+        X, W, AW = cols(S, 0), cols(S, 1), cols(AS, 1)
+        W[:rows].copy_(X[:rows])
+        product(S, AS)
+        kn.dot2_multi(rows, X, AW, X, gout[:2 * k], ws_dot2)
+        comm.allreduce(gout[:2 * k])
+        q = gout[:2 * k].cpu().numpy()
+        fresh = q[:k] / q[k:]
+        kn.block_combine(rows, residual_matrix(fresh), [AW, X], t1)
+        kn.dot_multi(rows, t1, t1, gout[:k], ws_dot)
+        comm.allreduce(gout[:k])
+        return fresh, np.sqrt(np.maximum(gout[:k].cpu().numpy(), 0.0))
+
+    has_p = False
+    it = 0
+    refreshed = -1
+    res_true = None
+    while True:
+        X, W, P = (cols(S, j) for j in range(3))
+        AX, AW, AP = (cols(AS, j) for j in range(3))
+        XW = S[:, :2 * k]
+        # the residual, into W's place (or, under a preconditioner, beside it)
+        if M is None:
+            kn.block_combine(rows, residual_matrix(lam), [AX, X], W)
+            G1, = grams((XW, W))
+            rr = np.diag(G1[k:]).copy()
+        else:
+            kn.block_combine(rows, residual_matrix(lam), [AX, X], t1)
+            kn.precond_apply(M, rows, t1, W)
+            G1, rr = grams((XW, W), norms=t1)
+        res = np.sqrt(np.maximum(rr, 0.0))
+        if converged(res, lam) or it >= maxit:
+            # the recurrence's word is checked against the true residual; where
+            # the carried AX has drifted too far, the fresh A X (now in AW's
+            # place) replaces it and the loop goes on, once per iteration
+            lam_true, res_true = true_residual(S, AS)
+            if converged(res_true, lam_true) or it >= maxit or refreshed == it:
+                break
+            AX[:rows].copy_(AW[:rows])
+            lam, refreshed = lam_true, it
+            continue
+        res_true = None
+        # W: two passes of projection against X + Cholesky QR (W -> t2 -> W)
+        C = _ortho_matrix(G1[:k], G1[k:])
+        if C is None:
+            break
+        kn.block_combine(rows, C, [X, W], t2)
+        Gx, Gw = grams((X, t2), (t2, t2))
+        C = _ortho_matrix(Gx, Gw)
+        if C is None:
+            break
+        kn.block_combine(rows, C, [X, t2], W)
+        product(S, AS)
+        # P (and AP by the same matrix): against X and W (P -> t2 -> P)
+        m = 2 * k
+        if has_p:
+            G3, = grams((S, P))
+            C = _ortho_matrix(G3[:2 * k], G3[2 * k:])
+            if C is not None:
+                kn.block_combine(rows, C, [X, W, P], t2)
+                kn.block_combine(rows, C, [AX, AW, AP], t3)
+                Gq, Gp = grams((XW, t2), (t2, t2))
+                C = _ortho_matrix(Gq, Gp)
+                if C is not None:
+                    kn.block_combine(rows, C, [X, W, t2], P)
+                    kn.block_combine(rows, C, [AX, AW, t3], AP)
+                    m = 3 * k
+        # Rayleigh-Ritz on the orthonormal basis
+        T, = grams((S[:, :m], AS[:, :m]))
+        w, V = np.linalg.eigh(0.5 * (T + T.T))
+        pick = np.arange(m - 1, m - 1 - k, -1) if largest else np.arange(k)
+        lam = w[pick]
+        C = np.ascontiguousarray(V[:, pick])
+        basis = [X, W, P][:m // k]
+        images = [AX, AW, AP][:m // k]
+        kn.block_combine(rows, C, basis, cols(S2, 0))
+        kn.block_combine(rows, C, images, cols(AS2, 0))
+        kn.block_combine(rows, C[k:], basis[1:], cols(S2, 2))
+        kn.block_combine(rows, C[k:], images[1:], cols(AS2, 2))
+        (S, AS), (S2, AS2) = (S2, AS2), (S, AS)
+        has_p = True
+        it += 1
+    if res_true is None:  # W's factorisation failed
+        lam_true, res_true = true_residual(S, AS)
+    X = cols(S, 0)
+    order = np.argsort(-lam_true if largest else lam_true, kind="stable")
+    if not np.array_equal(order, np.arange(k)):
+        # two Rayleigh quotients a rounding apart changed places: the columns
+        # follow (a chain over one 1.0 and zeros copies exactly)
+        kn.block_combine(rows, np.eye(k)[:, order], [X], cols(S2, 0))
+        X, lam_true, res_true = cols(S2, 0), lam_true[order], res_true[order]
+    return lam_true.copy(), X[:rows].clone(), it, res_true

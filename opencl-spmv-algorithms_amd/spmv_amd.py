@@ -320,6 +320,12 @@ HIP_SYMBOLS = {
                                                       _vp, ctypes.c_size_t, ctypes.c_int, _vp]),
     "spmv_bicgstab_dir_multi": (ctypes.c_int, [_c_i64, ctypes.c_int32, _vp, _vp, _vp, _vp, _vp, _c_i64, _vp, _c_i64,
                                                _vp, _c_i64, ctypes.c_int, _vp]),
+    "spmv_gram_multi_ws_bytes": (ctypes.c_size_t, [_c_i64, ctypes.c_int32, ctypes.c_int32]),
+    "spmv_gram_multi": (ctypes.c_int, [_c_i64, ctypes.c_int32, _vp, _c_i64, ctypes.c_int32, _vp, _c_i64, _vp, _vp,
+                                       ctypes.c_size_t, ctypes.c_int, _vp]),
+    "spmv_block_combine_multi": (ctypes.c_int, [_c_i64, ctypes.c_int32, _vp, ctypes.c_int32, _vp, _c_i64,
+                                                ctypes.c_int32, _vp, _c_i64, ctypes.c_int32, _vp, _c_i64, _vp, _c_i64,
+                                                ctypes.c_int, _vp]),
     "spmv_bjacobi_create": (ctypes.c_int, [Dims, _vp, _vp, _vp, _c_i32, _c_i64, _c_i32, _PP]),
     "spmv_bjacobi_get_info": (ctypes.c_int, [_vp, ctypes.POINTER(BjacobiInfo)]),
     "spmv_bjacobi_inverse": (ctypes.c_int, [_vp, _PP]),
@@ -388,6 +394,8 @@ HOST_SYMBOLS = {
                                                       _c_i64, _vp, _c_i64, _vp, _c_i64]),
     "spmv_cpu_bicgstab_dir_multi": (ctypes.c_int, [_c_i64, _c_i32, _vp, _vp, _vp, _vp, _vp, _c_i64, _vp, _c_i64, _vp,
                                                    _c_i64]),
+    "spmv_cpu_block_combine_multi": (ctypes.c_int, [_c_i64, _c_i32, _vp, _c_i32, _vp, _c_i64, _c_i32, _vp, _c_i64,
+                                                    _c_i32, _vp, _c_i64, _vp, _c_i64]),
     "spmv_csr_sort_rows": (ctypes.c_int, [_c_i64, _vp, _vp, _vp]),
     "spmv_csr_row_stats": (ctypes.c_int, [_c_i64, _vp, ctypes.POINTER(_c_i64), ctypes.POINTER(_c_i64), ctypes.POINTER(ctypes.c_double)]),
     "spmv_csr_pick_variant": (ctypes.c_int, [_c_i64, _vp]),
@@ -792,6 +800,51 @@ def cpu_bicgstab_dir_multi(n: int, rho_new, rv, tt, ts, V, R, P, k: int | None =
     _check_host(host_lib().spmv_cpu_bicgstab_dir_multi(n, k, _ptr(rho_new), _ptr(rv), _ptr(tt), _ptr(ts), _ptr(V),
                                                        ld(V), _ptr(R), ld(R), _ptr(P), ld(P)),
                 "spmv_cpu_bicgstab_dir_multi")
+
+
+def combine_matrix(C, blocks, who: str):
+    """The checks that spmv_block_combine_multi's callers share: 1 to 3 blocks
+    of 1..8 columns each, C a (sum of their widths, kc) matrix with kc in 1..8.
+    Returns (C as a contiguous float64 array, kc)."""
+    if not 1 <= len(blocks) <= 3:
+        raise SpmvError(OTHER_ERROR, who, "1 to 3 operand blocks")
+    widths = [int(t.shape[1]) for t in blocks]
+    if any(not 1 <= w <= 8 for w in widths):
+        raise SpmvError(OTHER_ERROR, who, f"every operand has 1..8 columns, not {widths}")
+    C = np.ascontiguousarray(C, np.float64)
+    if C.ndim != 2 or C.shape[0] != sum(widths) or not 1 <= C.shape[1] <= 8:
+        raise SpmvError(OTHER_ERROR, who, f"C must be ({sum(widths)}, kc in 1..8), not {C.shape}")
+    return C, int(C.shape[1])
+
+
+def cpu_block_combine_multi(n: int, C, blocks, Y: np.ndarray) -> None:
+    """Host statement of the block combine (spmv_cpu_block_combine_multi):
+    Y[:n, :kc] = [blocks[0] blocks[1] blocks[2]] C, every element the fma chain
+    s = 0; s = fma(S[i][r], C[r][c], s) in the order of r.  blocks: 1 to 3 2-D
+    float64 arrays (>= n rows, unit inner stride, 1..8 columns each); C: (sum of
+    their widths, kc <= 8); Y (>= n rows, >= kc columns) must not overlap them.
+    Only Y[:n, :kc] is written."""
+    what = "cpu_block_combine_multi"
+    for t in (*blocks, Y):
+        if not isinstance(t, np.ndarray) or t.dtype != np.float64 or t.ndim != 2:
+            raise SpmvError(OTHER_ERROR, what, "the blocks must be 2-D float64 arrays")
+        if t.shape[1] > 1 and t.strides[1] != 8 or t.strides[0] % 8:
+            raise SpmvError(OTHER_ERROR, what, "the blocks need unit inner stride")
+        if t.shape[0] < n:
+            raise SpmvError(OTHER_ERROR, what, "a block has too few rows")
+    C, kc = combine_matrix(C, blocks, what)
+    if Y.shape[1] < kc:
+        raise SpmvError(OTHER_ERROR, what, "Y has fewer than kc columns")
+
+    def ld(t, w):  # one row: its stride is never used
+        return t.strides[0] // 8 if t.shape[0] > 1 else w
+
+    args = []
+    for q in range(3):
+        t = blocks[q] if q < len(blocks) else None
+        args += [0, None, 0] if t is None else [t.shape[1], _ptr(t), ld(t, t.shape[1])]
+    _check_host(host_lib().spmv_cpu_block_combine_multi(n, kc, _ptr(C), *args, _ptr(Y), ld(Y, kc)),
+                "spmv_cpu_block_combine_multi")
 
 
 def csr_sort_rows(n_rows: int, ptr, col, val) -> None:
