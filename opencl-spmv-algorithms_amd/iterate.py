@@ -275,7 +275,7 @@ class HipKernels:
     # (>= n, k) blocks with inner stride 1, out / num / den hold k scalars
     @staticmethod
     def _ld(t) -> int:
-        return t.stride(0) if t.shape[0] > 1 else t.shape[1]
+        return sa._ld(t, t.shape[1])
 
     def dot_multi(self, n, A, B, out, ws) -> None:
         sa._check(self.lib.spmv_dot_multi(n, A.shape[1], sa._ptr(A), self._ld(A), sa._ptr(B), self._ld(B),
@@ -345,7 +345,7 @@ class HipKernels:
         for q in range(3):
             t = blocks[q] if q < len(blocks) else None
             args += [0, None, 0] if t is None else [t.shape[1], sa._ptr(t), self._ld(t)]
-        ldy = Y.stride(0) if Y.shape[0] > 1 else kc
+        ldy = sa._ld(Y, kc)
         sa._check(self.lib.spmv_block_combine_multi(n, kc, sa._ptr(C), *args, sa._ptr(Y), ldy, self.dev.index or 0,
                                                     self._s()), "spmv_block_combine_multi")
 
@@ -774,6 +774,15 @@ def _check_block(op, B_loc, who: str = "cg_multi") -> int:
     return int(B_loc.shape[1])
 
 
+def _rel(rr_host, bb):
+    """|r_j| / |b_j| per column from the squared norms rr_host and bb (0.0
+    for a zero column b_j)."""
+    out = np.zeros(bb.shape[0])
+    live = bb > 0.0
+    out[live] = np.sqrt(np.maximum(rr_host[live], 0.0) / bb[live])
+    return out
+
+
 def _cg_multi(op: DistOperator, B_loc, comm: Comm | None = None, tol: float = 1e-10, maxit: int = 1000,
               check_every: int = 10, M=None):
     """k independent CG recurrences (x0 = 0, A symmetric positive definite),
@@ -833,12 +842,6 @@ def _cg_multi(op: DistOperator, B_loc, comm: Comm | None = None, tol: float = 1e
     comm.allreduce(rr)
     bb = rr.cpu().numpy().copy()
 
-    def rel(rr_host):
-        out = np.zeros(nv)
-        live = bb > 0.0
-        out[live] = np.sqrt(np.maximum(rr_host[live], 0.0) / bb[live])
-        return out
-
     if not (bb > 0.0).any():
         return X, 0, np.zeros(nv)
     it = 0
@@ -856,7 +859,7 @@ def _cg_multi(op: DistOperator, B_loc, comm: Comm | None = None, tol: float = 1e
         if it % check_every == 0 or it == maxit:
             if (rr.cpu().numpy() <= tol * tol * bb).all():
                 break
-    return X, it, rel(rr.cpu().numpy())
+    return X, it, _rel(rr.cpu().numpy(), bb)
 
 
 # ------------------------------------------- Chebyshev over block Jacobi
@@ -1056,12 +1059,6 @@ def _pcg(op: DistOperator, comm: Comm, M, B, full, send, multi: bool, tol: float
     comm.allreduce(s)
     bb = rr.cpu().numpy().copy()
 
-    def rel(rr_host):
-        out = np.zeros(nv)
-        live = bb > 0.0
-        out[live] = np.sqrt(np.maximum(rr_host[live], 0.0) / bb[live])
-        return out
-
     if not (bb > 0.0).any():
         return X, 0, np.zeros(nv)
     P.copy_(Z[:rows])
@@ -1080,7 +1077,7 @@ def _pcg(op: DistOperator, comm: Comm, M, B, full, send, multi: bool, tol: float
         if it % check_every == 0 or it == maxit:
             if (rr.cpu().numpy() <= tol * tol * bb).all():
                 break
-    return X, it, rel(rr.cpu().numpy())
+    return X, it, _rel(rr.cpu().numpy(), bb)
 
 
 # ----------------------------------------------------------------- BiCGSTAB
@@ -1235,11 +1232,7 @@ def _bicgstab(op: DistOperator, comm: Comm, M, B, multi: bool, tol: float, maxit
     k.axpy_ratio_multi(rows, one, one, -1.0, V, T)
     k.dot_multi(rows, T, T, rv, ws)
     comm.allreduce(rv)
-    res = rv.cpu().numpy()
-    rel = np.zeros(nv)
-    live = bb > 0.0
-    rel[live] = np.sqrt(np.maximum(res[live], 0.0) / bb[live])
-    return X, it, rel
+    return X, it, _rel(rv.cpu().numpy(), bb)
 
 
 # ------------------------------------------------------------------- LOBPCG

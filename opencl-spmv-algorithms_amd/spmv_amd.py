@@ -122,6 +122,7 @@ class TransposeMultiInfo(ctypes.Structure):
 
 
 TRANSPOSE_MODES = {None: 0, "scatter": 1, "copy": 2}  # enum spmv_transpose_mode
+_TRANSPOSE_MODE_NAMES = {v: k for k, v in TRANSPOSE_MODES.items()}
 
 
 class SymmetricInfo(ctypes.Structure):
@@ -133,6 +134,7 @@ class SymmetricInfo(ctypes.Structure):
 
 
 SYMMETRIC_MODES = {None: 0, "fused": 1, "expand": 2}  # enum spmv_symmetric_mode
+_SYMMETRIC_MODE_NAMES = {v: k for k, v in SYMMETRIC_MODES.items()}
 
 
 class SymmetricMultiInfo(ctypes.Structure):
@@ -159,6 +161,7 @@ class MultiInfo(ctypes.Structure):
 
 
 MULTI_MODES = {None: 0, "balanced": 1}  # enum spmv_multi_mode
+_MULTI_MODE_NAMES = {v: k for k, v in MULTI_MODES.items()}
 
 
 class BjacobiInfo(ctypes.Structure):
@@ -619,14 +622,45 @@ def csr_transpose(n_rows: int, n_cols: int, ptr, col, val):
     return t_ptr, t_col, t_val
 
 
+# The host statements hand raw addresses and strides of numpy arrays to C:
+# these two checks are all that stands between a caller's array and a loop
+# that trusts them.  Each array is checked completely before the next one.
+_F64 = np.dtype(np.float64)  # made once: comparing a dtype with the type np.float64 makes one every time
+
+
+def _host_vectors(what: str, *pairs) -> None:
+    """pairs of (array, least length): contiguous 1-D float64 vectors."""
+    for a, n in pairs:
+        if not isinstance(a, np.ndarray) or a.dtype != _F64 or a.ndim != 1 or not a.flags.c_contiguous:
+            raise SpmvError(OTHER_ERROR, what, "x and y must be contiguous 1-D float64 arrays")
+        if a.size < n:
+            raise SpmvError(OTHER_ERROR, what, "x or y too short")
+
+
+def _host_blocks(what: str, pairs, k=None, names=("X and Y", "X and Y", "X or Y")):
+    """pairs of (array, least rows): 2-D float64 blocks with unit inner stride
+    and a row stride of whole doubles, k columns (default: the first block's
+    width) in each; k = 0 for blocks without a common width.  names: what the
+    messages call all of them (their kind, their strides) and any one.
+    Returns (k, ld), ld(a, w=k) the leading dimension C is given."""
+    for a, n in pairs:
+        if not isinstance(a, np.ndarray) or a.dtype != _F64 or a.ndim != 2:
+            raise SpmvError(OTHER_ERROR, what, f"{names[0]} must be 2-D float64 arrays")
+        if a.shape[1] > 1 and a.strides[1] != 8 or a.strides[0] % 8:
+            raise SpmvError(OTHER_ERROR, what, f"{names[1]} need unit inner stride")
+        if a.shape[0] < n:
+            raise SpmvError(OTHER_ERROR, what, f"{names[2]} has too few rows")
+    k = pairs[0][0].shape[1] if k is None else int(k)
+    for a, _ in pairs:
+        if k > a.shape[1]:
+            raise SpmvError(OTHER_ERROR, what, f"{names[2]} has fewer than k columns")
+    return k, lambda a, w=k: a.strides[0] // 8 if a.shape[0] > 1 else w  # one row: its stride is never used
+
+
 def cpu_csr_t(n_rows: int, n_cols: int, ptr, col, val, x: np.ndarray, y: np.ndarray) -> None:
     """Host y = A^T x (spmv_cpu_csr_t): x has n_rows entries; y[:n_cols] is
     overwritten, nothing past it."""
-    for a, n in ((x, n_rows), (y, n_cols)):
-        if not isinstance(a, np.ndarray) or a.dtype != np.float64 or a.ndim != 1 or not a.flags.c_contiguous:
-            raise SpmvError(OTHER_ERROR, "cpu_csr_t", "x and y must be contiguous 1-D float64 arrays")
-        if a.size < n:
-            raise SpmvError(OTHER_ERROR, "cpu_csr_t", "x or y too short")
+    _host_vectors("cpu_csr_t", (x, n_rows), (y, n_cols))
     _check_host(host_lib().spmv_cpu_csr_t(n_rows, n_cols, _ptr(ptr), _ptr(col), _ptr(val), _ptr(x), _ptr(y)),
                 "spmv_cpu_csr_t")
 
@@ -653,11 +687,7 @@ def expand_symmetric(m: Coo) -> Coo:
 def cpu_csr_sym(n: int, ptr, col, val, x: np.ndarray, y: np.ndarray) -> None:
     """Host y = (S + S^T - diag S) x on the half storage (spmv_cpu_csr_sym):
     x has n entries; y[:n] is overwritten, nothing past it."""
-    for a in (x, y):
-        if not isinstance(a, np.ndarray) or a.dtype != np.float64 or a.ndim != 1 or not a.flags.c_contiguous:
-            raise SpmvError(OTHER_ERROR, "cpu_csr_sym", "x and y must be contiguous 1-D float64 arrays")
-        if a.size < n:
-            raise SpmvError(OTHER_ERROR, "cpu_csr_sym", "x or y too short")
+    _host_vectors("cpu_csr_sym", (x, n), (y, n))
     _check_host(host_lib().spmv_cpu_csr_sym(n, _ptr(ptr), _ptr(col), _ptr(val), _ptr(x), _ptr(y)), "spmv_cpu_csr_sym")
 
 
@@ -666,18 +696,8 @@ def cpu_csr_sym_multi(n: int, ptr, col, val, X: np.ndarray, Y: np.ndarray, k: in
     (spmv_cpu_csr_sym_multi): X and Y (>= n rows) are 2-D float64 arrays with
     unit inner stride whose row strides are ldx and ldy; k defaults to X's
     width.  Only Y[:n, :k] is written."""
-    for a in (X, Y):
-        if not isinstance(a, np.ndarray) or a.dtype != np.float64 or a.ndim != 2:
-            raise SpmvError(OTHER_ERROR, "cpu_csr_sym_multi", "X and Y must be 2-D float64 arrays")
-        if a.shape[1] > 1 and a.strides[1] != 8 or a.strides[0] % 8:
-            raise SpmvError(OTHER_ERROR, "cpu_csr_sym_multi", "X and Y need unit inner stride")
-        if a.shape[0] < n:
-            raise SpmvError(OTHER_ERROR, "cpu_csr_sym_multi", "X or Y has too few rows")
-    k = X.shape[1] if k is None else int(k)
-    if k > X.shape[1] or k > Y.shape[1]:
-        raise SpmvError(OTHER_ERROR, "cpu_csr_sym_multi", "X or Y has fewer than k columns")
-    ldx, ldy = (a.strides[0] // 8 if a.shape[0] > 1 else k for a in (X, Y))  # one row: its stride is never used
-    rc = host_lib().spmv_cpu_csr_sym_multi(n, _ptr(ptr), _ptr(col), _ptr(val), k, _ptr(X), ldx, _ptr(Y), ldy)
+    k, ld = _host_blocks("cpu_csr_sym_multi", ((X, n), (Y, n)), k)
+    rc = host_lib().spmv_cpu_csr_sym_multi(n, _ptr(ptr), _ptr(col), _ptr(val), k, _ptr(X), ld(X), _ptr(Y), ld(Y))
     _check_host(rc, "spmv_cpu_csr_sym_multi")
 
 
@@ -701,21 +721,11 @@ def cpu_bjacobi_apply_multi(n: int, bs: int, inv: np.ndarray, R: np.ndarray, Z: 
     """Host Z = M^-1 R (spmv_cpu_bjacobi_apply_multi) with inv from
     bjacobi_build_host: R and Z (>= n rows) are 2-D float64 arrays with unit
     inner stride; k defaults to R's width.  Only Z[:n, :k] is written."""
-    for a in (R, Z):
-        if not isinstance(a, np.ndarray) or a.dtype != np.float64 or a.ndim != 2:
-            raise SpmvError(OTHER_ERROR, "cpu_bjacobi_apply_multi", "R and Z must be 2-D float64 arrays")
-        if a.shape[1] > 1 and a.strides[1] != 8 or a.strides[0] % 8:
-            raise SpmvError(OTHER_ERROR, "cpu_bjacobi_apply_multi", "R and Z need unit inner stride")
-        if a.shape[0] < n:
-            raise SpmvError(OTHER_ERROR, "cpu_bjacobi_apply_multi", "R or Z has too few rows")
-    k = R.shape[1] if k is None else int(k)
-    if k > R.shape[1] or k > Z.shape[1]:
-        raise SpmvError(OTHER_ERROR, "cpu_bjacobi_apply_multi", "R or Z has fewer than k columns")
+    k, ld = _host_blocks("cpu_bjacobi_apply_multi", ((R, n), (Z, n)), k, ("R and Z", "R and Z", "R or Z"))
     inv = np.ascontiguousarray(inv, np.float64)
     if 1 <= bs <= 16 and inv.size < (max(n, 0) + bs - 1) // bs * bs * bs:
         raise SpmvError(OTHER_ERROR, "cpu_bjacobi_apply_multi", "inv is too short")
-    ldr, ldz = (a.strides[0] // 8 if a.shape[0] > 1 else k for a in (R, Z))  # one row: its stride is never used
-    _check_host(host_lib().spmv_cpu_bjacobi_apply_multi(n, bs, _ptr(inv), k, _ptr(R), ldr, _ptr(Z), ldz),
+    _check_host(host_lib().spmv_cpu_bjacobi_apply_multi(n, bs, _ptr(inv), k, _ptr(R), ld(R), _ptr(Z), ld(Z)),
                 "spmv_cpu_bjacobi_apply_multi")
 
 
@@ -732,51 +742,31 @@ def cpu_bjacobi_cheb_step_multi(n: int, bs: int, inv: np.ndarray, a: float, b: f
         Zin = None
     elif Zin is None:
         raise SpmvError(OTHER_ERROR, what, "a general step (AZ given) needs Zin")
-    given = [t for t in (R, AZ, D, Zin, Zout) if t is not None]
-    for t in given:
-        if not isinstance(t, np.ndarray) or t.dtype != np.float64 or t.ndim != 2:
-            raise SpmvError(OTHER_ERROR, what, "R, AZ, D, Zin and Zout must be 2-D float64 arrays")
-        if t.shape[1] > 1 and t.strides[1] != 8 or t.strides[0] % 8:
-            raise SpmvError(OTHER_ERROR, what, "the arrays need unit inner stride")
-        if t.shape[0] < n:
-            raise SpmvError(OTHER_ERROR, what, "an array has too few rows")
-    k = R.shape[1] if k is None else int(k)
-    if any(k > t.shape[1] for t in given):
-        raise SpmvError(OTHER_ERROR, what, "an array has fewer than k columns")
+    k, ld = _host_blocks(what, [(t, n) for t in (R, AZ, D, Zin, Zout) if t is not None], k,
+                         ("R, AZ, D, Zin and Zout", "the arrays", "an array"))
     inv = np.ascontiguousarray(inv, np.float64)
     if 1 <= bs <= 16 and inv.size < (max(n, 0) + bs - 1) // bs * bs * bs:
         raise SpmvError(OTHER_ERROR, what, "inv is too short")
-
-    def ld(t):  # one row: its stride is never used
-        return 0 if t is None else t.strides[0] // 8 if t.shape[0] > 1 else k
-
-    def p(t):
-        return None if t is None else _ptr(t)
-
-    _check_host(host_lib().spmv_cpu_bjacobi_cheb_step_multi(n, bs, _ptr(inv), k, float(a), float(b), p(R), ld(R), p(AZ),
-                                                            ld(AZ), p(D), ld(D), p(Zin), ld(Zin), p(Zout), ld(Zout)),
+    args = []
+    for t in (R, AZ, D, Zin, Zout):
+        args += [None, 0] if t is None else [_ptr(t), ld(t)]
+    _check_host(host_lib().spmv_cpu_bjacobi_cheb_step_multi(n, bs, _ptr(inv), k, float(a), float(b), *args),
                 "spmv_cpu_bjacobi_cheb_step_multi")
+
+
+_BLOCK_NAMES = ("the blocks", "the blocks", "a block")
 
 
 def _bicgstab_blocks(what: str, n: int, k, blocks, scalars):
     """The checks of the two BiCGSTAB host statements: 2-D float64 blocks with
     unit inner stride and >= n rows, k (default: the first block's width)
     columns in each, float64 arrays of >= k scalars.  Returns (k, ld(block))."""
-    for t in blocks:
-        if not isinstance(t, np.ndarray) or t.dtype != np.float64 or t.ndim != 2:
-            raise SpmvError(OTHER_ERROR, what, "the blocks must be 2-D float64 arrays")
-        if t.shape[1] > 1 and t.strides[1] != 8 or t.strides[0] % 8:
-            raise SpmvError(OTHER_ERROR, what, "the blocks need unit inner stride")
-        if t.shape[0] < n:
-            raise SpmvError(OTHER_ERROR, what, "a block has too few rows")
-    k = blocks[0].shape[1] if k is None else int(k)
-    if any(k > t.shape[1] for t in blocks):
-        raise SpmvError(OTHER_ERROR, what, "a block has fewer than k columns")
+    k, ld = _host_blocks(what, [(t, n) for t in blocks], k, _BLOCK_NAMES)
     for c in scalars:
         if not isinstance(c, np.ndarray) or c.dtype != np.float64 or c.ndim != 1 or c.size < k or \
                 (c.size > 1 and c.strides[0] != 8):
             raise SpmvError(OTHER_ERROR, what, "the scalars must be contiguous float64 arrays of k entries")
-    return k, lambda t: t.strides[0] // 8 if t.shape[0] > 1 else k  # one row: its stride is never used
+    return k, ld
 
 
 def cpu_bicgstab_update_multi(n: int, a_num, a_den, w_num, w_den, Ph, Sh, T, X, R, k: int | None = None) -> None:
@@ -825,20 +815,10 @@ def cpu_block_combine_multi(n: int, C, blocks, Y: np.ndarray) -> None:
     their widths, kc <= 8); Y (>= n rows, >= kc columns) must not overlap them.
     Only Y[:n, :kc] is written."""
     what = "cpu_block_combine_multi"
-    for t in (*blocks, Y):
-        if not isinstance(t, np.ndarray) or t.dtype != np.float64 or t.ndim != 2:
-            raise SpmvError(OTHER_ERROR, what, "the blocks must be 2-D float64 arrays")
-        if t.shape[1] > 1 and t.strides[1] != 8 or t.strides[0] % 8:
-            raise SpmvError(OTHER_ERROR, what, "the blocks need unit inner stride")
-        if t.shape[0] < n:
-            raise SpmvError(OTHER_ERROR, what, "a block has too few rows")
+    _, ld = _host_blocks(what, [(t, n) for t in (*blocks, Y)], 0, _BLOCK_NAMES)  # every block has its own width
     C, kc = combine_matrix(C, blocks, what)
     if Y.shape[1] < kc:
         raise SpmvError(OTHER_ERROR, what, "Y has fewer than kc columns")
-
-    def ld(t, w):  # one row: its stride is never used
-        return t.strides[0] // 8 if t.shape[0] > 1 else w
-
     args = []
     for q in range(3):
         t = blocks[q] if q < len(blocks) else None
@@ -1185,17 +1165,11 @@ def bytes_alg_multi(n_rows: int, n_cols: int, nnz: int, k: int) -> int:
 
 
 def cpu_csr_multi(n_rows: int, ptr, col, val, X: np.ndarray, Y: np.ndarray, k: int | None = None) -> None:
-    """Host Y = A X (spmv_cpu_csr_multi): X and Y are 2-D float64 arrays with
-    unit inner stride whose row strides are ldx and ldy; k defaults to X's
-    width.  Only Y[:, :k] is written."""
-    for a in (X, Y):
-        if not isinstance(a, np.ndarray) or a.dtype != np.float64 or a.ndim != 2:
-            raise SpmvError(OTHER_ERROR, "cpu_csr_multi", "X and Y must be 2-D float64 arrays")
-        if a.shape[1] > 1 and a.strides[1] != 8 or a.strides[0] % 8:
-            raise SpmvError(OTHER_ERROR, "cpu_csr_multi", "X and Y need unit inner stride")
-    k = X.shape[1] if k is None else int(k)
-    rc = host_lib().spmv_cpu_csr_multi(n_rows, _ptr(ptr), _ptr(col), _ptr(val), k, _ptr(X), X.strides[0] // 8,
-                                       _ptr(Y), Y.strides[0] // 8)
+    """Host Y = A X (spmv_cpu_csr_multi): X and Y (>= n_rows rows) are 2-D
+    float64 arrays with unit inner stride whose row strides are ldx and ldy; k
+    defaults to X's width.  Only Y[:n_rows, :k] is written."""
+    k, ld = _host_blocks("cpu_csr_multi", ((X, 0), (Y, n_rows)), k)  # no n_cols here: X's rows go unchecked
+    rc = host_lib().spmv_cpu_csr_multi(n_rows, _ptr(ptr), _ptr(col), _ptr(val), k, _ptr(X), ld(X), _ptr(Y), ld(Y))
     _check_host(rc, "spmv_cpu_csr_multi")
 
 
@@ -1204,19 +1178,9 @@ def cpu_csr_t_multi(n_rows: int, n_cols: int, ptr, col, val, X: np.ndarray, Y: n
     (>= n_cols rows) are 2-D float64 arrays with unit inner stride whose row
     strides are ldx and ldy; k defaults to X's width.  Only Y[:n_cols, :k] is
     written."""
-    for a, n in ((X, n_rows), (Y, n_cols)):
-        if not isinstance(a, np.ndarray) or a.dtype != np.float64 or a.ndim != 2:
-            raise SpmvError(OTHER_ERROR, "cpu_csr_t_multi", "X and Y must be 2-D float64 arrays")
-        if a.shape[1] > 1 and a.strides[1] != 8 or a.strides[0] % 8:
-            raise SpmvError(OTHER_ERROR, "cpu_csr_t_multi", "X and Y need unit inner stride")
-        if a.shape[0] < n:
-            raise SpmvError(OTHER_ERROR, "cpu_csr_t_multi", "X or Y has too few rows")
-    k = X.shape[1] if k is None else int(k)
-    if k > X.shape[1] or k > Y.shape[1]:
-        raise SpmvError(OTHER_ERROR, "cpu_csr_t_multi", "X or Y has fewer than k columns")
-    ldx, ldy = (a.strides[0] // 8 if a.shape[0] > 1 else k for a in (X, Y))  # one row: its stride is never used
-    rc = host_lib().spmv_cpu_csr_t_multi(n_rows, n_cols, _ptr(ptr), _ptr(col), _ptr(val), k, _ptr(X), ldx,
-                                         _ptr(Y), ldy)
+    k, ld = _host_blocks("cpu_csr_t_multi", ((X, n_rows), (Y, n_cols)), k)
+    rc = host_lib().spmv_cpu_csr_t_multi(n_rows, n_cols, _ptr(ptr), _ptr(col), _ptr(val), k, _ptr(X), ld(X),
+                                         _ptr(Y), ld(Y))
     _check_host(rc, "spmv_cpu_csr_t_multi")
 
 
@@ -1240,6 +1204,79 @@ def _torch():
 def _dev_tensor(arr: np.ndarray, device):
     torch = _torch()
     return torch.from_numpy(np.ascontiguousarray(arr)).to(device)
+
+
+# Raw data_ptr()s and strides go to the C-ABI: a tensor of another dtype, a
+# strided view or a tensor on another device would give a wrong y or a GPU
+# fault, not an exception.  The two checks below are the only thing between a
+# caller's tensors and a kernel; they are in front of every launch, so they
+# look torch, the dtype and the device up once, not per tensor.
+def _ld(t, k: int) -> int:
+    """Leading dimension of a row-major (rows, k) block (one row: its stride is never used)."""
+    return t.stride(0) if t.shape[0] > 1 else k
+
+
+def _on_device(t, here) -> bool:
+    """t is on the torch.device `here`, an index-less device being its device
+    0 (the one dims() names); equal devices are the quick way out."""
+    d = t.device
+    return d == here or (d.type == here.type and (d.index or 0) == (here.index or 0))
+
+
+def _check_vectors(what: str, x, x_len: int, y, y_len: int, device, *, types="x and y must be float64 tensors",
+                   refuse=None) -> None:
+    """x and y are contiguous float64 tensors of >= x_len and >= y_len entries
+    on `device`, or SpmvError(OTHER_ERROR, what, ..).  types: the wording of
+    the first refusal (run's differs).  refuse: a refusal of the caller's own
+    that stands between the type checks and the sizes."""
+    torch = _torch()
+    tensor, f64 = torch.Tensor, torch.float64
+    for t in (x, y):
+        if not isinstance(t, tensor) or t.dtype != f64:
+            raise SpmvError(OTHER_ERROR, what, types)
+    if refuse:
+        raise SpmvError(OTHER_ERROR, what, refuse)
+    if x.numel() < x_len or y.numel() < y_len:
+        raise SpmvError(OTHER_ERROR, what, "x or y too short")
+    if not (x.is_contiguous() and y.is_contiguous()):
+        raise SpmvError(OTHER_ERROR, what, "x and y must be contiguous")
+    here = torch.device(device)
+    if not (_on_device(x, here) and _on_device(y, here)):
+        raise SpmvError(OTHER_ERROR, what, f"x and y must be on {here.type}:{here.index or 0}")
+
+
+def _check_blocks(what: str, X, x_rows: int, Y, y_rows: int, device, *, refuse=None):
+    """X and Y are row-major float64 blocks on `device` of >= x_rows and
+    >= y_rows rows and the same k >= 1 columns: rows of k contiguous values, row
+    stride >= k, so column slices of wider tensors pass.  Returns (k, ldx,
+    ldy), or SpmvError(OTHER_ERROR, what, ..); refuse as in _check_vectors."""
+    torch = _torch()
+    tensor, f64 = torch.Tensor, torch.float64
+    for t in (X, Y):
+        if not isinstance(t, tensor) or t.dtype != f64:
+            raise SpmvError(OTHER_ERROR, what, "X and Y must be float64 tensors")
+        if t.dim() != 2:
+            raise SpmvError(OTHER_ERROR, what, "X and Y must be 2-D (rows, k)")
+    if refuse:
+        raise SpmvError(OTHER_ERROR, what, refuse)
+    (xr, k), (yr, yk) = X.shape, Y.shape
+    if k < 1 or yk != k:
+        raise SpmvError(OTHER_ERROR, what, "X and Y must have the same number k >= 1 of columns")
+    if xr < x_rows or yr < y_rows:
+        raise SpmvError(OTHER_ERROR, what, "X or Y has too few rows")
+    for rows, (row_stride, inner) in ((xr, X.stride()), (yr, Y.stride())):
+        if (k > 1 and inner != 1) or (rows > 1 and row_stride < k):
+            raise SpmvError(OTHER_ERROR, what, "X and Y need inner stride 1 and a row stride >= k")
+    here = torch.device(device)
+    if not (_on_device(X, here) and _on_device(Y, here)):
+        raise SpmvError(OTHER_ERROR, what, f"X and Y must be on {here.type}:{here.index or 0}")
+    return k, _ld(X, k), _ld(Y, k)
+
+
+def _stream_handle(stream, device) -> int:
+    """The HIP stream of `stream` (None: torch's current stream on `device`)."""
+    st = stream if stream is not None else _torch().cuda.current_stream(device)
+    return st.cuda_stream
 
 
 @dataclass
@@ -1287,27 +1324,14 @@ class DeviceMatrix:
 
     def run(self, x, y, stream=None) -> None:
         """y = A x on `stream` (default: torch's current stream)."""
+        _check_vectors("run", x, self.n_cols, y, self.n_rows, self.device, types="x and y must be float64")
         lib = hip_lib()
-        torch = _torch()
+        if self.plan is not None:
+            _check(lib.spmv_plan_run(self.plan, _ptr(x), _ptr(y), _stream_handle(stream, self.device)),
+                   f"spmv_plan_run ({self.fmt})")
+            return
         a = self.arrays
         p = self.params
-        if x.dtype != torch.float64 or y.dtype != torch.float64:
-            raise SpmvError(OTHER_ERROR, "run", "x and y must be float64")
-        if x.numel() < self.n_cols or y.numel() < self.n_rows:
-            raise SpmvError(OTHER_ERROR, "run", "x or y too short")
-        # raw data_ptr()s go to the C-ABI: a strided view or a tensor on
-        # another device would give a wrong y or a GPU fault
-        if not (x.is_contiguous() and y.is_contiguous()):
-            raise SpmvError(OTHER_ERROR, "run", "x and y must be contiguous")
-        here = torch.device(self.device)
-        idx = here.index or 0  # the device dims() passes to the C-ABI
-        for t in (x, y):
-            if t.device.type != here.type or (t.device.index or 0) != idx:
-                raise SpmvError(OTHER_ERROR, "run", f"x and y must be on {here.type}:{idx}")
-        if self.plan is not None:
-            st = stream if stream is not None else torch.cuda.current_stream(here)
-            _check(lib.spmv_plan_run(self.plan, _ptr(x), _ptr(y), st.cuda_stream), f"spmv_plan_run ({self.fmt})")
-            return
         d = self.dims(stream)
         if self.fmt == "csrf32" and p.get("variant") == 4:
             rc = lib.spmv_csr_f32v_run_tiled_hot(d, _ptr(a["row_ptr"]), _ptr(a["col"]), _ptr(a["val"]), _ptr(x),
@@ -1348,6 +1372,23 @@ class DeviceMatrix:
             raise SpmvError(OTHER_ERROR, "run", f"format {self.fmt} has no plan and no entry point")
         _check(rc, f"spmv_{self.fmt}_run")
 
+    def _plan_info(self, what: str, struct, mode_names: dict) -> dict:
+        """The struct that spmv_plan_get_<what> fills, as a dict: mode by its
+        name, kernel as a str, arrays as lists, every other field an int
+        (reserved ones left out)."""
+        if self.plan is None:
+            raise SpmvError(OTHER_ERROR, what, f"format {self.fmt} has no plan")
+        info = struct()
+        _check(getattr(hip_lib(), f"spmv_plan_get_{what}")(self.plan, ctypes.byref(info)), f"spmv_plan_get_{what}")
+        out = {}
+        for name, _ in struct._fields_:
+            v = getattr(info, name)
+            if name == "mode":
+                out[name] = mode_names[v]
+            elif name != "reserved":
+                out[name] = v.decode() if isinstance(v, bytes) else int(v) if isinstance(v, int) else [int(e) for e in v]
+        return out
+
     @property
     def multi_supported(self) -> bool:
         """run_multi can run this matrix (spmv_plan_multi_supported)."""
@@ -1358,33 +1399,11 @@ class DeviceMatrix:
         X is (>= n_cols, k), Y is (>= n_rows, k), float64 on the matrix's
         device with inner stride 1; their row strides (>= k) are ldx and ldy,
         so column slices of wider tensors work.  Only Y[:n_rows, :k] is written."""
-        torch = _torch()
-        for t in (X, Y):
-            if not isinstance(t, torch.Tensor) or t.dtype != torch.float64:
-                raise SpmvError(OTHER_ERROR, "run_multi", "X and Y must be float64 tensors")
-            if t.dim() != 2:
-                raise SpmvError(OTHER_ERROR, "run_multi", "X and Y must be 2-D (rows, k)")
-        k = X.shape[1]
-        if k < 1 or Y.shape[1] != k:
-            raise SpmvError(OTHER_ERROR, "run_multi", "X and Y must have the same number k >= 1 of columns")
-        if X.shape[0] < self.n_cols or Y.shape[0] < self.n_rows:
-            raise SpmvError(OTHER_ERROR, "run_multi", "X or Y has too few rows")
-        # raw data_ptr()s and strides go to the C-ABI: rows of k contiguous
-        # values, row stride >= k (a one-row tensor's row stride is never used)
-        for t in (X, Y):
-            if (k > 1 and t.stride(1) != 1) or (t.shape[0] > 1 and t.stride(0) < k):
-                raise SpmvError(OTHER_ERROR, "run_multi", "X and Y need inner stride 1 and a row stride >= k")
-        here = torch.device(self.device)
-        idx = here.index or 0
-        for t in (X, Y):
-            if t.device.type != here.type or (t.device.index or 0) != idx:
-                raise SpmvError(OTHER_ERROR, "run_multi", f"X and Y must be on {here.type}:{idx}")
+        k, ldx, ldy = _check_blocks("run_multi", X, self.n_cols, Y, self.n_rows, self.device)
         if self.plan is None:
             raise SpmvError(OTHER_ERROR, "run_multi", f"format {self.fmt} has no plan: no multi-vector run")
-        ldx = X.stride(0) if X.shape[0] > 1 else k
-        ldy = Y.stride(0) if Y.shape[0] > 1 else k
-        st = stream if stream is not None else torch.cuda.current_stream(here)
-        _check(hip_lib().spmv_plan_run_multi(self.plan, k, _ptr(X), ldx, _ptr(Y), ldy, st.cuda_stream),
+        st = _stream_handle(stream, self.device)
+        _check(hip_lib().spmv_plan_run_multi(self.plan, k, _ptr(X), ldx, _ptr(Y), ldy, st),
                f"spmv_plan_run_multi ({self.fmt})")
 
     def prepare_multi(self, mode="balanced", long_len=None, seg_len=None) -> None:
@@ -1404,14 +1423,7 @@ class DeviceMatrix:
     @property
     def multi_info(self) -> dict:
         """spmv_multi_info as a dict; mode is None or "balanced"."""
-        if self.plan is None:
-            raise SpmvError(OTHER_ERROR, "multi_info", f"format {self.fmt} has no plan")
-        info = MultiInfo()
-        _check(hip_lib().spmv_plan_get_multi_info(self.plan, ctypes.byref(info)), "spmv_plan_get_multi_info")
-        out = {k: int(getattr(info, k)) for k, _ in MultiInfo._fields_ if k not in ("mode", "reserved", "kernel")}
-        out["mode"] = {v: k for k, v in MULTI_MODES.items()}[info.mode]
-        out["kernel"] = info.kernel.decode()
-        return out
+        return self._plan_info("multi_info", MultiInfo, _MULTI_MODE_NAMES)
 
     @property
     def transpose_supported(self) -> bool:
@@ -1433,35 +1445,15 @@ class DeviceMatrix:
     @property
     def transpose_info(self) -> dict:
         """spmv_transpose_info as a dict; mode is None, "scatter" or "copy"."""
-        if self.plan is None:
-            raise SpmvError(OTHER_ERROR, "transpose_info", f"format {self.fmt} has no plan")
-        info = TransposeInfo()
-        _check(hip_lib().spmv_plan_get_transpose_info(self.plan, ctypes.byref(info)), "spmv_plan_get_transpose_info")
-        out = {k: int(getattr(info, k)) for k in ("cap", "blocks", "lds_blocks", "flush_entries", "owned_bytes")}
-        out["mode"] = {v: k for k, v in TRANSPOSE_MODES.items()}[info.mode]
-        out["kernel"] = info.kernel.decode()
-        return out
+        return self._plan_info("transpose_info", TransposeInfo, _TRANSPOSE_MODE_NAMES)
 
     def run_t(self, x, y, stream=None) -> None:
         """y = A^T x on `stream` (spmv_plan_run_t): x has >= n_rows entries,
         y[:n_cols] is overwritten.  Needs prepare_transpose first."""
-        torch = _torch()
-        for t in (x, y):
-            if not isinstance(t, torch.Tensor) or t.dtype != torch.float64:
-                raise SpmvError(OTHER_ERROR, "run_t", "x and y must be float64 tensors")
-        if x.numel() < self.n_rows or y.numel() < self.n_cols:
-            raise SpmvError(OTHER_ERROR, "run_t", "x or y too short")
-        if not (x.is_contiguous() and y.is_contiguous()):
-            raise SpmvError(OTHER_ERROR, "run_t", "x and y must be contiguous")
-        here = torch.device(self.device)
-        idx = here.index or 0
-        for t in (x, y):
-            if t.device.type != here.type or (t.device.index or 0) != idx:
-                raise SpmvError(OTHER_ERROR, "run_t", f"x and y must be on {here.type}:{idx}")
+        _check_vectors("run_t", x, self.n_rows, y, self.n_cols, self.device)
         if self.plan is None:
             raise SpmvError(OTHER_ERROR, "run_t", f"format {self.fmt} has no plan: no transposed run")
-        st = stream if stream is not None else torch.cuda.current_stream(here)
-        _check(hip_lib().spmv_plan_run_t(self.plan, _ptr(x), _ptr(y), st.cuda_stream),
+        _check(hip_lib().spmv_plan_run_t(self.plan, _ptr(x), _ptr(y), _stream_handle(stream, self.device)),
                f"spmv_plan_run_t ({self.fmt})")
 
     @property
@@ -1486,15 +1478,7 @@ class DeviceMatrix:
     @property
     def symmetric_info(self) -> dict:
         """spmv_symmetric_info as a dict; mode is None, "fused" or "expand"."""
-        if self.plan is None:
-            raise SpmvError(OTHER_ERROR, "symmetric_info", f"format {self.fmt} has no plan")
-        info = SymmetricInfo()
-        _check(hip_lib().spmv_plan_get_symmetric_info(self.plan, ctypes.byref(info)), "spmv_plan_get_symmetric_info")
-        out = {k: int(getattr(info, k)) for k in ("cap", "blocks", "window_blocks", "flush_entries", "nnz_expanded",
-                                                  "owned_bytes")}
-        out["mode"] = {v: k for k, v in SYMMETRIC_MODES.items()}[info.mode]
-        out["kernel"] = info.kernel.decode()
-        return out
+        return self._plan_info("symmetric_info", SymmetricInfo, _SYMMETRIC_MODE_NAMES)
 
     def symmetric_arrays(self):
         """Expand mode: host copies (row_ptr[n+1], col, val) of the CSR of A
@@ -1512,29 +1496,18 @@ class DeviceMatrix:
                 _check(lib.spmv_download(_ptr(host), dptr, host.nbytes, None), "spmv_download")
         return out
 
+    def _not_square(self):
+        """The symmetric runs' own refusal (for _check_*'s refuse), or None."""
+        return None if self.n_rows == self.n_cols else "the matrix is not square"
+
     def run_sym(self, x, y, stream=None) -> None:
         """y = (S + S^T - diag S) x on `stream` (spmv_plan_run_sym), S the
         stored half this matrix holds: x has >= n entries, y[:n] is
         overwritten.  Needs prepare_symmetric first."""
-        torch = _torch()
-        for t in (x, y):
-            if not isinstance(t, torch.Tensor) or t.dtype != torch.float64:
-                raise SpmvError(OTHER_ERROR, "run_sym", "x and y must be float64 tensors")
-        if self.n_rows != self.n_cols:
-            raise SpmvError(OTHER_ERROR, "run_sym", "the matrix is not square")
-        if x.numel() < self.n_cols or y.numel() < self.n_rows:
-            raise SpmvError(OTHER_ERROR, "run_sym", "x or y too short")
-        if not (x.is_contiguous() and y.is_contiguous()):
-            raise SpmvError(OTHER_ERROR, "run_sym", "x and y must be contiguous")
-        here = torch.device(self.device)
-        idx = here.index or 0
-        for t in (x, y):
-            if t.device.type != here.type or (t.device.index or 0) != idx:
-                raise SpmvError(OTHER_ERROR, "run_sym", f"x and y must be on {here.type}:{idx}")
+        _check_vectors("run_sym", x, self.n_cols, y, self.n_rows, self.device, refuse=self._not_square())
         if self.plan is None:
             raise SpmvError(OTHER_ERROR, "run_sym", f"format {self.fmt} has no plan: no symmetric run")
-        st = stream if stream is not None else torch.cuda.current_stream(here)
-        _check(hip_lib().spmv_plan_run_sym(self.plan, _ptr(x), _ptr(y), st.cuda_stream),
+        _check(hip_lib().spmv_plan_run_sym(self.plan, _ptr(x), _ptr(y), _stream_handle(stream, self.device)),
                f"spmv_plan_run_sym ({self.fmt})")
 
     @property
@@ -1542,16 +1515,7 @@ class DeviceMatrix:
         """spmv_symmetric_multi_info as a dict (cap_cols, window_blocks and
         flush_entries are lists over the kernel widths 1, 2, 4, 8); mode as in
         symmetric_info."""
-        if self.plan is None:
-            raise SpmvError(OTHER_ERROR, "symmetric_multi_info", f"format {self.fmt} has no plan")
-        info = SymmetricMultiInfo()
-        _check(hip_lib().spmv_plan_get_symmetric_multi_info(self.plan, ctypes.byref(info)),
-               "spmv_plan_get_symmetric_multi_info")
-        out = {k: [int(v) for v in getattr(info, k)] for k in ("cap_cols", "window_blocks", "flush_entries")}
-        out.update({k: int(getattr(info, k)) for k in ("long_rows", "segments", "multi_owned_bytes")})
-        out["mode"] = {v: k for k, v in SYMMETRIC_MODES.items()}[info.mode]
-        out["kernel"] = info.kernel.decode()
-        return out
+        return self._plan_info("symmetric_multi_info", SymmetricMultiInfo, _SYMMETRIC_MODE_NAMES)
 
     def run_sym_multi(self, X, Y, stream=None) -> None:
         """Y = (S + S^T - diag S) X on `stream` for k vectors stored row-major
@@ -1559,47 +1523,19 @@ class DeviceMatrix:
         Y are (>= n, k), float64 on the matrix's device with inner stride 1;
         their row strides (>= k) are ldx and ldy.  Only Y[:n, :k] is written.
         Needs prepare_symmetric first."""
-        torch = _torch()
-        for t in (X, Y):
-            if not isinstance(t, torch.Tensor) or t.dtype != torch.float64:
-                raise SpmvError(OTHER_ERROR, "run_sym_multi", "X and Y must be float64 tensors")
-            if t.dim() != 2:
-                raise SpmvError(OTHER_ERROR, "run_sym_multi", "X and Y must be 2-D (rows, k)")
-        if self.n_rows != self.n_cols:
-            raise SpmvError(OTHER_ERROR, "run_sym_multi", "the matrix is not square")
-        k = X.shape[1]
-        if k < 1 or Y.shape[1] != k:
-            raise SpmvError(OTHER_ERROR, "run_sym_multi", "X and Y must have the same number k >= 1 of columns")
-        if X.shape[0] < self.n_cols or Y.shape[0] < self.n_rows:
-            raise SpmvError(OTHER_ERROR, "run_sym_multi", "X or Y has too few rows")
-        for t in (X, Y):  # as run_multi: raw data_ptr()s and strides go to the C-ABI
-            if (k > 1 and t.stride(1) != 1) or (t.shape[0] > 1 and t.stride(0) < k):
-                raise SpmvError(OTHER_ERROR, "run_sym_multi", "X and Y need inner stride 1 and a row stride >= k")
-        here = torch.device(self.device)
-        idx = here.index or 0
-        for t in (X, Y):
-            if t.device.type != here.type or (t.device.index or 0) != idx:
-                raise SpmvError(OTHER_ERROR, "run_sym_multi", f"X and Y must be on {here.type}:{idx}")
+        k, ldx, ldy = _check_blocks("run_sym_multi", X, self.n_cols, Y, self.n_rows, self.device,
+                                    refuse=self._not_square())
         if self.plan is None:
             raise SpmvError(OTHER_ERROR, "run_sym_multi", f"format {self.fmt} has no plan: no symmetric run")
-        ldx = X.stride(0) if X.shape[0] > 1 else k
-        ldy = Y.stride(0) if Y.shape[0] > 1 else k
-        st = stream if stream is not None else torch.cuda.current_stream(here)
-        _check(hip_lib().spmv_plan_run_sym_multi(self.plan, k, _ptr(X), ldx, _ptr(Y), ldy, st.cuda_stream),
+        st = _stream_handle(stream, self.device)
+        _check(hip_lib().spmv_plan_run_sym_multi(self.plan, k, _ptr(X), ldx, _ptr(Y), ldy, st),
                f"spmv_plan_run_sym_multi ({self.fmt})")
 
     @property
     def transpose_multi_info(self) -> dict:
         """spmv_transpose_multi_info as a dict (cap_cols and lds_blocks are
         lists over the kernel widths 1, 2, 4, 8); mode as in transpose_info."""
-        if self.plan is None:
-            raise SpmvError(OTHER_ERROR, "transpose_multi_info", f"format {self.fmt} has no plan")
-        info = TransposeMultiInfo()
-        _check(hip_lib().spmv_plan_get_transpose_multi_info(self.plan, ctypes.byref(info)),
-               "spmv_plan_get_transpose_multi_info")
-        return {"mode": {v: k for k, v in TRANSPOSE_MODES.items()}[info.mode],
-                "cap_cols": [int(v) for v in info.cap_cols], "lds_blocks": [int(v) for v in info.lds_blocks],
-                "kernel": info.kernel.decode()}
+        return self._plan_info("transpose_multi_info", TransposeMultiInfo, _TRANSPOSE_MODE_NAMES)
 
     def run_t_multi(self, X, Y, stream=None) -> None:
         """Y = A^T X on `stream` for k vectors stored row-major
@@ -1607,31 +1543,11 @@ class DeviceMatrix:
         float64 on the matrix's device with inner stride 1; their row strides
         (>= k) are ldx and ldy.  Only Y[:n_cols, :k] is written.  Needs
         prepare_transpose first."""
-        torch = _torch()
-        for t in (X, Y):
-            if not isinstance(t, torch.Tensor) or t.dtype != torch.float64:
-                raise SpmvError(OTHER_ERROR, "run_t_multi", "X and Y must be float64 tensors")
-            if t.dim() != 2:
-                raise SpmvError(OTHER_ERROR, "run_t_multi", "X and Y must be 2-D (rows, k)")
-        k = X.shape[1]
-        if k < 1 or Y.shape[1] != k:
-            raise SpmvError(OTHER_ERROR, "run_t_multi", "X and Y must have the same number k >= 1 of columns")
-        if X.shape[0] < self.n_rows or Y.shape[0] < self.n_cols:
-            raise SpmvError(OTHER_ERROR, "run_t_multi", "X or Y has too few rows")
-        for t in (X, Y):  # as run_multi: raw data_ptr()s and strides go to the C-ABI
-            if (k > 1 and t.stride(1) != 1) or (t.shape[0] > 1 and t.stride(0) < k):
-                raise SpmvError(OTHER_ERROR, "run_t_multi", "X and Y need inner stride 1 and a row stride >= k")
-        here = torch.device(self.device)
-        idx = here.index or 0
-        for t in (X, Y):
-            if t.device.type != here.type or (t.device.index or 0) != idx:
-                raise SpmvError(OTHER_ERROR, "run_t_multi", f"X and Y must be on {here.type}:{idx}")
+        k, ldx, ldy = _check_blocks("run_t_multi", X, self.n_rows, Y, self.n_cols, self.device)
         if self.plan is None:
             raise SpmvError(OTHER_ERROR, "run_t_multi", f"format {self.fmt} has no plan: no transposed run")
-        ldx = X.stride(0) if X.shape[0] > 1 else k
-        ldy = Y.stride(0) if Y.shape[0] > 1 else k
-        st = stream if stream is not None else torch.cuda.current_stream(here)
-        _check(hip_lib().spmv_plan_run_t_multi(self.plan, k, _ptr(X), ldx, _ptr(Y), ldy, st.cuda_stream),
+        st = _stream_handle(stream, self.device)
+        _check(hip_lib().spmv_plan_run_t_multi(self.plan, k, _ptr(X), ldx, _ptr(Y), ldy, st),
                f"spmv_plan_run_t_multi ({self.fmt})")
 
 
@@ -1706,17 +1622,15 @@ class BlockJacobi:
                 raise SpmvError(OTHER_ERROR, what, "a 1-D R or Z must be contiguous")
             if t.shape[0] < n:
                 raise SpmvError(OTHER_ERROR, what, "R or Z has too few rows")
-            if t.device.type != self.device.type or (t.device.index or 0) != (self.device.index or 0):
+            if not _on_device(t, self.device):
                 raise SpmvError(OTHER_ERROR, what, f"R and Z must be on {self.device}")
         k = R.shape[1] if R.dim() == 2 else 1
         if (Z.shape[1] if Z.dim() == 2 else 1) != k or k < 1:
             raise SpmvError(OTHER_ERROR, what, "R and Z must have the same number k >= 1 of columns")
-        ld = [t.stride(0) if t.dim() == 2 and t.shape[0] > 1 else k for t in (R, Z)]
-        return k, ld[0], ld[1]
+        return k, _ld(R, k), _ld(Z, k)  # a 1-D tensor of several entries is contiguous: its stride is k = 1
 
     def _stream(self, stream):
-        st = stream if stream is not None else _torch().cuda.current_stream(self.device)
-        return st.cuda_stream
+        return _stream_handle(stream, self.device)
 
     def apply(self, R, Z, stream=None) -> None:
         """Z = M^-1 R on `stream` (default: torch's current stream)."""
