@@ -41,7 +41,7 @@ LIB_HIP  := $(LIBDIR)/libspmv_hip.so
 LIB_HOST := $(LIBDIR)/libspmv_host.so
 ORACLE   := oracle/liboracle.so
 
-.PHONY: all default lib oracle probes lab test-san test-san-transpose test-san-transpose-multi test-san-multi-plan test-san-symmetric test-san-symmetric-multi test-san-precond test-san-cheb test-san-bicgstab test-san-bsr test-san-block test-cpu test-gpu clean $(TARGETS)
+.PHONY: all default lib oracle probes lab test-san test-san-transpose test-san-transpose-multi test-san-multi-plan test-san-symmetric test-san-symmetric-multi test-san-precond test-san-cheb test-san-bicgstab test-san-bsr test-san-block test-san-krylov test-cpu test-gpu clean $(TARGETS)
 
 default: all
 all: lib $(TARGETS) probes
@@ -245,6 +245,18 @@ build/san/block_harness: tests/san/block_harness.c $(HOST_SRC) include/spmv_host
 
 test-san-block: build/san/block_harness
 	$(SANENV) ASAN_OPTIONS=detect_leaks=1:exitcode=99 build/san/block_harness
+
+# the host statements of GMRES's three basis kernels (spmv_cpu_krylov_project,
+# spmv_cpu_krylov_combine, spmv_cpu_krylov_normalize) under ASan + UBSan: a
+# stand-alone program with exactly-sized buffers, ld == width and ld > width,
+# w_out == w, w_out a column of the basis, s = 0, n = 0 and the refused inputs
+# (tests/san/krylov_harness.c)
+build/san/krylov_harness: tests/san/krylov_harness.c $(HOST_SRC) include/spmv_host.h include/spmv_rc.h
+	@mkdir -p build/san
+	$(CC) -std=c11 -Wall -Wextra -Werror -fopenmp -Iinclude $(SANFLAGS) $< $(HOST_SRC) -o $@ -lm
+
+test-san-krylov: build/san/krylov_harness
+	$(SANENV) ASAN_OPTIONS=detect_leaks=1:exitcode=99 build/san/krylov_harness
 
 test-gpu: all oracle
 	python -m pytest tests/ -x -q -m gpu

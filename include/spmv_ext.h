@@ -521,6 +521,65 @@ int spmv_block_combine_multi(int64_t n, int32_t kc, const double *C, int32_t ka0
                              int64_t lda0, int32_t ka1, const double *A1, int64_t lda1, int32_t ka2,
                              const double *A2, int64_t lda2, double *Y, int64_t ldy, int device,
                              void *stream);
+/* The three basis kernels of restarted GMRES (iterate.gmres), by the
+ * conventions of the block vector kernels above: the Krylov basis is one
+ * row-major block V[i*ldv + j], j < c <= ldv, 8-byte alignment only (16-byte
+ * loads only where V's base and ldv allow them); the vectors w, w_out, t and v
+ * are single columns with a leading dimension of their own (element i at
+ * [i*ld], ld >= 1), so that each may be a column of a block; nothing outside
+ * V[i*ldv .. i*ldv + c) and those elements, i < n, is read or written;
+ * asynchronous on `stream`, no allocation, no synchronisation, no atomics.
+ * 1 <= c <= SPMV_KRYLOV_MAX_COLS: a basis has at most 32 columns, so GMRES
+ * restarts after at most 31 steps.  SPMV_OTHER_ERROR, before anything is
+ * written, for n < 0, c out of range, ldv < c, another ld below 1, a NULL
+ * argument that would be read or written or a workspace that is too small.
+ *
+ * spmv_krylov_project_dot: one Gram-Schmidt pass and the inner products the
+ * next pass needs, in one sweep over V.  h is a device array of c doubles, or
+ * NULL for "all zeros".
+ *   w_out[i] = s_c,  s_0 = w[i],  s_(j+1) = fma(-h[j], V[i][j], s_j), j = 0, 1, ...
+ * the device form of spmv_cpu_krylov_project (spmv_host.h), which fixes every
+ * bit whatever c, the leading dimensions, the alignment or the load width; with
+ * h == NULL, w_out[i] = w[i], and w_out may then be NULL: nothing is stored.
+ *   out[j] = sum_i V[i][j] w_out[i], j < c;   out[c] = sum_i w_out[i]^2
+ * over the NEW w_out, through spmv_dot_multi's fixed tree (the same
+ * workgroups, rows, accumulator pair and final kernel): out[j] is bit for bit
+ * what spmv_dot_multi(n, 1, V + j, ldv, w_out, ldo, ...) gives afterwards and
+ * out[c] what spmv_dot_multi(n, 1, w_out, ldo, w_out, ldo, ...) gives.  out is a
+ * device array of c + 1 doubles; n == 0 writes c + 1 zeros.  w_out may be w
+ * itself with the same ld (an element is read before it is written), and it
+ * may be a column of the allocation that holds V (column c with ldo == ldv,
+ * say) provided it is none of the c columns read; any other overlap between V,
+ * h, w, w_out, out and ws is the caller's error.  A thread owns a row of V and
+ * needs all of it before it can form a sum, so stage 1 is ONE kernel whatever
+ * c, compiled for ceil(c / 8) = 1, 2, 3 and 4 blocks of 8 columns (a short
+ * basis does not pay for 32 columns): TWO launches, stage 1 and the final one.
+ * ws holds spmv_dot_multi_ws_bytes(n, 8 * ceil(c / 8) + 1) bytes;
+ * spmv_dot_multi_ws_bytes(n, SPMV_KRYLOV_MAX_COLS + 1) serves every c.
+ *
+ * spmv_krylov_combine: t[i] = s_c, s_0 = 0.0, s_(j+1) = fma(V[i][j], y[j], s_j),
+ * the device form of spmv_cpu_krylov_combine.  y_host is a HOST array of c
+ * doubles: it is read before the call returns and travels in the kernel
+ * arguments (256 bytes; the rule of spmv_block_combine_multi's C).  t must not
+ * overlap the c columns read.  One launch; n == 0 writes nothing.
+ *
+ * spmv_krylov_normalize: v[i] = w[i] * r with r = 1 / sqrt(s[0]), and r = 0.0
+ * WHEN s[0] <= 0.0 (the zero-denominator rule of the ratio kernels: the norm of
+ * a vector that is exactly zero makes it stay zero, never NaN); s is one
+ * device double.  The device form of spmv_cpu_krylov_normalize.  copy is NULL or
+ * a contiguous vector of n doubles that receives the same values (a product's
+ * send buffer).  v may be w (same ld); copy must overlap neither.  One launch;
+ * n == 0 writes nothing.                                                    */
+#ifndef SPMV_KRYLOV_MAX_COLS
+#define SPMV_KRYLOV_MAX_COLS 32
+#endif
+int spmv_krylov_project_dot(int64_t n, int32_t c, const double *V, int64_t ldv, const double *h,
+                            const double *w, int64_t ldw, double *w_out, int64_t ldo, double *out,
+                            void *ws, size_t ws_bytes, int device, void *stream);
+int spmv_krylov_combine(int64_t n, int32_t c, const double *V, int64_t ldv, const double *y_host,
+                        double *t, int64_t ldt, int device, void *stream);
+int spmv_krylov_normalize(int64_t n, const double *s, const double *w, int64_t ldw, double *v,
+                          int64_t ldv, double *copy, int device, void *stream);
 /* Block-Jacobi preconditioner M = blockdiag(D_0, D_1, ...), bs x bs blocks of
  * the diagonal, 1 <= bs <= 16, for the CG solvers of iterate.py (cg, cg_multi).
  * spmv_bjacobi_build (spmv_host.h) defines the blocks (col_base,

@@ -492,6 +492,28 @@ int spmv_cpu_bicgstab_dir_multi(int64_t n, int32_t k, const double *rho_new, con
 int spmv_cpu_block_combine_multi(int64_t n, int32_t kc, const double *C, int32_t ka0, const double *A0,
                                  int64_t lda0, int32_t ka1, const double *A1, int64_t lda1, int32_t ka2,
                                  const double *A2, int64_t lda2, double *Y, int64_t ldy);
+/* The three basis statements of restarted GMRES (iterate.gmres): V is a
+ * row-major block (V[i*ldv + j], i < n, j < c <= ldv, 1 <= c <= 32), w, w_out,
+ * t and v single columns with a leading dimension of their own (element i at
+ * [i*ld], ld >= 1), h, y and s HOST arrays of c, c and 1 doubles.
+ * project:   w_out[i] = s after  s = w[i];  s = fma(-h[j], V[i][j], s), j = 0, 1, ...
+ *            (w_out may be w itself: an element is read before it is written)
+ * combine:   t[i] = s after  s = 0.0;  s = fma(V[i][j], y[j], s), j = 0, 1, ...
+ * normalize: v[i] = w[i] * r,  r = 1 / sqrt(s[0]), and 0.0 when s[0] <= 0.0;
+ *            copy, if not NULL, is a contiguous vector that receives the same
+ *            values; v may be w.
+ * These fix the bits of every element: the CPU statements of
+ * spmv_krylov_project_dot (its w_out; its sums are fixed by spmv_dot_multi),
+ * spmv_krylov_combine and spmv_krylov_normalize (spmv_ext.h).  Nothing else is
+ * read or written.  SPMV_OTHER_ERROR, before anything is written, for a
+ * negative n, c outside 1..32, ldv < c, another leading dimension below 1 or a
+ * NULL array that would be read or written.                                 */
+int spmv_cpu_krylov_project(int64_t n, int32_t c, const double *V, int64_t ldv, const double *h,
+                            const double *w, int64_t ldw, double *w_out, int64_t ldo);
+int spmv_cpu_krylov_combine(int64_t n, int32_t c, const double *V, int64_t ldv, const double *y,
+                            double *t, int64_t ldt);
+int spmv_cpu_krylov_normalize(int64_t n, const double *s, const double *w, int64_t ldw, double *v,
+                              int64_t ldv, double *copy);
 /* Y = A^T X for k >= 1 vectors stored row-major, the layout of
  * spmv_plan_run_t_multi (spmv.h): X[r*ldx + j], r < n_rows; Y[c*ldy + j],
  * c < n_cols; j < k; ldx >= k, ldy >= k.  Serial: zeroes Y[c*ldy + j], j < k,

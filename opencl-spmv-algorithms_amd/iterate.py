@@ -1,5 +1,5 @@
 """iterate.py — iterated SpMV over row shards: power iteration, CG,
-multi-right-hand-side CG, BiCGSTAB and the LOBPCG eigensolver.
+multi-right-hand-side CG, BiCGSTAB, restarted GMRES and the LOBPCG eigensolver.
 
 SURVEY.md §8f row 3: "Iterated SpMV (power iteration / CG) reusing the y
 all-gather as the next x".  The reference stops after one SpMV (reference
@@ -57,6 +57,12 @@ BiCGSTAB on the same layout, products and device-resident scalars, one
 recurrence per column, with three fused block kernels of its own
 (spmv_dot2_multi, spmv_bicgstab_update_dot_multi, spmv_bicgstab_dir_multi) so
 that an iteration is 10 launches; block Jacobi is its preconditioner.
+BiCGSTAB can break down and has no restart; gmres is the method that cannot:
+right-preconditioned restarted GMRES(m <= 31), one right-hand side, its basis
+one row-major block and three kernels of its own (spmv_krylov_project_dot,
+spmv_krylov_combine, spmv_krylov_normalize; csrc/krylov.hip).  The Hessenberg
+matrix and its Givens rotations live on the host, which reads three small
+results once per Arnoldi step.
 
 Eigenpairs (lobpcg): the k <= 8 smallest or largest eigenpairs of a symmetric
 operator by LOBPCG in its orthonormal-basis form, on the multi-vector products,
@@ -348,6 +354,41 @@ class HipKernels:
         ldy = sa._ld(Y, kc)
         sa._check(self.lib.spmv_block_combine_multi(n, kc, sa._ptr(C), *args, sa._ptr(Y), ldy, self.dev.index or 0,
                                                     self._s()), "spmv_block_combine_multi")
+
+    # the basis kernels of GMRES (csrc/krylov.hip): V is the (>= n, c <= 32)
+    # view of the basis' first c columns; w, w_out, t, v are (>= n, 1) views,
+    # each possibly a column of a block
+    def krylov_project_dot(self, n, V, h, w, w_out, out, ws) -> None:
+        """w_out = w - V h (h: c device scalars, or None for zeros; w_out may
+        then be None, and may be w or another column of V's block otherwise),
+        out[:c] = V^T w_out, out[c] = w_out . w_out; ws: krylov_project_ws(n)."""
+        sa._check(self.lib.spmv_krylov_project_dot(n, V.shape[1], sa._ptr(V), self._ld(V), sa._ptr(h), sa._ptr(w),
+                                                   self._ld(w), sa._ptr(w_out),
+                                                   0 if w_out is None else self._ld(w_out), sa._ptr(out),
+                                                   sa._ptr(ws), ws.numel(), self.dev.index or 0, self._s()),
+                  "spmv_krylov_project_dot")
+
+    def krylov_project_ws(self, n):
+        """The workspace of krylov_project_dot for any basis width."""
+        torch = sa._torch()
+        nbytes = self.lib.spmv_dot_multi_ws_bytes(n, sa.KRYLOV_MAX_COLS + 1)
+        return torch.empty(nbytes, dtype=torch.uint8, device=self.dev)
+
+    def krylov_combine(self, n, V, y, t) -> None:
+        """t = V y, y a HOST float64 array of c scalars that travels in the
+        kernel arguments."""
+        y = np.ascontiguousarray(y, np.float64)
+        if y.ndim != 1 or y.shape[0] != V.shape[1]:
+            raise sa.SpmvError(sa.OTHER_ERROR, "krylov_combine", f"y must hold {V.shape[1]} scalars, not {y.shape}")
+        sa._check(self.lib.spmv_krylov_combine(n, V.shape[1], sa._ptr(V), self._ld(V), sa._ptr(y), sa._ptr(t),
+                                               self._ld(t), self.dev.index or 0, self._s()), "spmv_krylov_combine")
+
+    def krylov_normalize(self, n, s, w, v, copy=None) -> None:
+        """v = w / sqrt(s[0]) (0 for s[0] <= 0; v may be w), and the same values
+        into the contiguous vector `copy` when one is given."""
+        sa._check(self.lib.spmv_krylov_normalize(n, sa._ptr(s), sa._ptr(w), self._ld(w), sa._ptr(v), self._ld(v),
+                                                 sa._ptr(copy), self.dev.index or 0, self._s()),
+                  "spmv_krylov_normalize")
 
     # the preconditioner M (sa.BlockJacobi over this rank's n rows):
     # Z = M^-1 R, out[:k] = column sums of R Z, out[k:2k] of R R
@@ -1116,13 +1157,13 @@ def bicgstab_multi(op: DistOperator, B_loc, comm: Comm | None = None, tol: float
         return _bicgstab(op, comm or Comm(), M, B_loc, True, tol, maxit, check_every)
 
 
-def _bicgstab_precond(op, precond):
+def _bicgstab_precond(op, precond, who: str = "bicgstab"):
     """_precond_of, refusing a Chebyshev polynomial before any device work: its
     bounds assume a real positive spectrum, which a non-symmetric matrix does
     not have."""
     M = _precond_of(op, precond)
     if isinstance(M, Chebyshev):
-        raise sa.SpmvError(sa.OTHER_ERROR, "bicgstab",
+        raise sa.SpmvError(sa.OTHER_ERROR, who,
                            "a Chebyshev preconditioner needs a real positive spectrum: use block Jacobi or none")
     return M
 
@@ -1233,6 +1274,164 @@ def _bicgstab(op: DistOperator, comm: Comm, M, B, multi: bool, tol: float, maxit
     k.dot_multi(rows, T, T, rv, ws)
     comm.allreduce(rv)
     return X, it, _rel(rv.cpu().numpy(), bb)
+
+
+# -------------------------------------------------------------------- GMRES
+def gmres(op: DistOperator, b_loc, comm: Comm | None = None, tol: float = 1e-10, maxit: int = 1000,
+          restart: int = 20, precond=None):
+    """Restarted GMRES(restart) for a general (non-symmetric) square matrix,
+    x0 = 0, preconditioned from the right, on the operator's kernel stream
+    (_gmres has the method and its launch and all-reduce counts).  Every
+    operator bicgstab accepts: any format including BSR, split / overlap,
+    several ranks.  precond as for bicgstab (_precond_of): a block-Jacobi
+    preconditioner or none; a Chebyshev one is refused.  restart is an integer
+    in 1..31 (the basis has restart + 1 <= 32 columns).  Returns (x_local,
+    iterations, rel): iterations counts Arnoldi steps (one product each, plus
+    one per cycle for the residual), rel is the TRUE relative residual
+    ||b - A x|| / ||b||.  The solver returns only when that residual is
+    <= tol, or at maxit steps.  Refusals (restart, the shape, dtype or device of
+    b_loc, the preconditioner) are an SpmvError before any device work."""
+    if not isinstance(restart, (int, np.integer)) or isinstance(restart, bool) or \
+            not 1 <= restart <= sa.KRYLOV_MAX_COLS - 1:
+        raise sa.SpmvError(sa.OTHER_ERROR, "gmres",
+                           f"restart must be an integer in 1..{sa.KRYLOV_MAX_COLS - 1}, not {restart!r}")
+    torch = sa._torch()
+    if not isinstance(b_loc, torch.Tensor) or b_loc.dim() != 1:
+        raise sa.SpmvError(sa.OTHER_ERROR, "gmres", f"b_loc must be a 1-D float64 tensor of {op.rows} entries")
+    _check_block(op, b_loc.unsqueeze(1), "gmres")
+    M = _bicgstab_precond(op, precond, "gmres")
+    with _kernel_stream(op):
+        return _gmres(op, comm or Comm(), M, b_loc, float(tol), int(maxit), int(restart))
+
+
+def _givens_column(H, cs, sn, g, j) -> None:
+    """Applies the j rotations so far to column j of the Hessenberg matrix H,
+    makes rotation j (it zeroes H[j + 1, j]) and applies it to H and to the
+    right-hand side g.  A zero column gets the identity rotation."""
+    for i in range(j):
+        a, b = H[i, j], H[i + 1, j]
+        H[i, j], H[i + 1, j] = cs[i] * a + sn[i] * b, cs[i] * b - sn[i] * a
+    a, b = H[j, j], H[j + 1, j]
+    d = float(np.hypot(a, b))
+    cs[j], sn[j] = (1.0, 0.0) if d == 0.0 else (a / d, b / d)
+    H[j, j], H[j + 1, j] = d, 0.0
+    g[j + 1] = -sn[j] * g[j]
+    g[j] = cs[j] * g[j]
+
+
+def _back_substitute(H, g, kk):
+    """y with H[:kk, :kk] y = g[:kk] for the upper triangle the rotations left;
+    a zero pivot (a singular matrix) gives y_i = 0, not a division by zero."""
+    y = np.zeros(kk)
+    for i in range(kk - 1, -1, -1):
+        s = g[i] - float(H[i, i + 1:kk] @ y[i + 1:])
+        y[i] = 0.0 if H[i, i] == 0.0 else s / H[i, i]
+    return y
+
+
+def _gmres(op: DistOperator, comm: Comm, M, b_loc, tol: float, maxit: int, m: int):
+    """Right-preconditioned GMRES(m), x0 = 0: A M^-1 u = b, x = M^-1 u.  The
+    basis V is one row-major (rows, m + 1) block; the Hessenberg matrix, the
+    Givens rotations and the small triangular solve live on the host.
+
+    Step j of a cycle (c = j + 1 basis columns so far), classical Gram-Schmidt
+    applied twice (CGS2), the sums of each pass fused into the pass before it:
+        send = M^-1 v_j                      precond_apply (1), or nothing: the
+                                             normalisation already wrote v_j there
+        w = A send                           the product (1; 3 on a split operator)
+        h1 = V^T w                           krylov_project_dot, h = None (2)
+        w' = w - V h1,  h2 = V^T w'          krylov_project_dot (2)
+        w'' = w' - V h2 into column c,       krylov_project_dot (2)
+          V^T w'' and ||w''||^2
+        v_c = w'' / ||w''||                  krylov_normalize (1)
+    8 launches without a preconditioner, 9 with one, whatever c; THREE
+    all-reduces of c + 1 scalars (each pass needs the sums of the one before),
+    and ONE host visit, which reads the three results together.  Then on the
+    host H[:c, j] = h1 + h2, H[c, j] = ||w''||, the rotations so far are applied
+    to the column and a new one is made (_givens_column); |g[c]| is the residual
+    norm of the least-squares problem.
+
+    A cycle ends after m steps, when |g[c]| <= tol ||b||, when H[c, j] = 0 (the
+    Krylov space is invariant: the solution lies in it) or at maxit steps.
+    Then y solves the triangular system, t = V y (krylov_combine, 1 launch),
+    x += M^-1 t, and the TRUE residual r = b - A x comes from one extra
+    product, as at the end of _bicgstab: the solver returns only when
+    ||r|| <= tol ||b||, or at maxit; otherwise r / ||r|| is the next cycle's v_0.
+    The estimate |g| can drift below the true residual in a long cycle; the
+    return value never rests on it.
+
+    Zero norms: b = 0 returns x = 0, 0 iterations, rel = 0.0.  ||w''|| = 0
+    makes v_c = 0 (krylov_normalize's rule) and ends the cycle; a zero pivot in
+    the triangle gives a zero coefficient.  Nothing becomes NaN."""
+    torch = sa._torch()
+    k = op.kernels
+    rows = op.rows
+
+    def zeros(*shape):
+        return torch.zeros(shape, dtype=torch.float64, device=op.device)
+
+    full, send = _gathered_pair(op, comm)
+    apply = _Apply(op, comm, full, send)
+    copy = send[:rows] if M is None else None  # where krylov_normalize leaves the product's input
+    Z = send[:rows].unsqueeze(1)
+    V = zeros(max(rows, 1), m + 1)
+    w, t = zeros(max(rows, 1)), zeros(max(rows, 1))
+    W, T = w.unsqueeze(1), t.unsqueeze(1)
+    B = b_loc.unsqueeze(1)
+    x = zeros(rows)
+    X = x.unsqueeze(1)
+    ws = k.krylov_project_ws(rows)
+    dws = k.dot_multi_ws(rows, 1)
+    d = zeros(3, m + 2)  # the sums of a step's three passes
+    rr, one = zeros(1), zeros(1) + 1.0
+    k.dot_multi(rows, B, B, rr, dws)
+    comm.allreduce(rr)
+    bb = float(rr.item())
+    if bb == 0.0:
+        return x, 0, 0.0
+    bnorm = float(np.sqrt(bb))
+    k.krylov_normalize(rows, rr, B, V[:, 0:1], copy)
+    res = bnorm
+    its = 0
+    while True:
+        H = np.zeros((m + 1, m))
+        cs, sn, g = np.zeros(m), np.zeros(m), np.zeros(m + 1)
+        g[0] = res
+        kk = 0
+        while kk < m and its < maxit:
+            j, c = kk, kk + 1
+            Vc, v_new = V[:, :c], V[:, c:c + 1]
+            if M is not None:
+                k.precond_apply(M, rows, V[:, j:j + 1], Z)
+            apply(w)  # gathers send
+            for p, (h, dst) in enumerate(((None, None), (d[0, :c], W), (d[1, :c], v_new))):
+                k.krylov_project_dot(rows, Vc, h, W, dst, d[p, :c + 1], ws)
+                comm.allreduce(d[p, :c + 1])
+            k.krylov_normalize(rows, d[2, c:c + 1], v_new, v_new, copy)
+            hd = d.cpu().numpy()  # the step's one host visit
+            H[:c, j] = hd[0, :c] + hd[1, :c]
+            H[c, j] = hnext = float(np.sqrt(max(hd[2, c], 0.0)))
+            _givens_column(H, cs, sn, g, j)
+            kk += 1
+            its += 1
+            if abs(g[kk]) <= tol * bnorm or hnext == 0.0:
+                break
+        if kk > 0:
+            k.krylov_combine(rows, V[:, :kk], _back_substitute(H, g, kk), T)
+            if M is not None:
+                k.precond_apply(M, rows, T, W)
+            k.axpy_ratio_multi(rows, one, one, 1.0, T if M is None else W, X)  # x += M^-1 V y
+        # the true residual b - A x: fma(-1, A x, b) is exact
+        send[:rows].copy_(x)
+        apply(w)
+        T[:rows].copy_(B)
+        k.axpy_ratio_multi(rows, one, one, -1.0, W, T)
+        k.dot_multi(rows, T, T, rr, dws)
+        comm.allreduce(rr)
+        res = float(np.sqrt(max(float(rr.item()), 0.0)))
+        if res <= tol * bnorm or its >= maxit or kk == 0:
+            return x, its, res / bnorm
+        k.krylov_normalize(rows, rr, T, V[:, 0:1], copy)
 
 
 # ------------------------------------------------------------------- LOBPCG

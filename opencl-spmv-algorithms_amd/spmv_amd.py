@@ -329,6 +329,10 @@ HIP_SYMBOLS = {
     "spmv_block_combine_multi": (ctypes.c_int, [_c_i64, ctypes.c_int32, _vp, ctypes.c_int32, _vp, _c_i64,
                                                 ctypes.c_int32, _vp, _c_i64, ctypes.c_int32, _vp, _c_i64, _vp, _c_i64,
                                                 ctypes.c_int, _vp]),
+    "spmv_krylov_project_dot": (ctypes.c_int, [_c_i64, ctypes.c_int32, _vp, _c_i64, _vp, _vp, _c_i64, _vp, _c_i64, _vp,
+                                               _vp, ctypes.c_size_t, ctypes.c_int, _vp]),
+    "spmv_krylov_combine": (ctypes.c_int, [_c_i64, ctypes.c_int32, _vp, _c_i64, _vp, _vp, _c_i64, ctypes.c_int, _vp]),
+    "spmv_krylov_normalize": (ctypes.c_int, [_c_i64, _vp, _vp, _c_i64, _vp, _c_i64, _vp, ctypes.c_int, _vp]),
     "spmv_bjacobi_create": (ctypes.c_int, [Dims, _vp, _vp, _vp, _c_i32, _c_i64, _c_i32, _PP]),
     "spmv_bjacobi_get_info": (ctypes.c_int, [_vp, ctypes.POINTER(BjacobiInfo)]),
     "spmv_bjacobi_inverse": (ctypes.c_int, [_vp, _PP]),
@@ -399,6 +403,9 @@ HOST_SYMBOLS = {
                                                    _c_i64]),
     "spmv_cpu_block_combine_multi": (ctypes.c_int, [_c_i64, _c_i32, _vp, _c_i32, _vp, _c_i64, _c_i32, _vp, _c_i64,
                                                     _c_i32, _vp, _c_i64, _vp, _c_i64]),
+    "spmv_cpu_krylov_project": (ctypes.c_int, [_c_i64, _c_i32, _vp, _c_i64, _vp, _vp, _c_i64, _vp, _c_i64]),
+    "spmv_cpu_krylov_combine": (ctypes.c_int, [_c_i64, _c_i32, _vp, _c_i64, _vp, _vp, _c_i64]),
+    "spmv_cpu_krylov_normalize": (ctypes.c_int, [_c_i64, _vp, _vp, _c_i64, _vp, _c_i64, _vp]),
     "spmv_csr_sort_rows": (ctypes.c_int, [_c_i64, _vp, _vp, _vp]),
     "spmv_csr_row_stats": (ctypes.c_int, [_c_i64, _vp, ctypes.POINTER(_c_i64), ctypes.POINTER(_c_i64), ctypes.POINTER(ctypes.c_double)]),
     "spmv_csr_pick_variant": (ctypes.c_int, [_c_i64, _vp]),
@@ -825,6 +832,60 @@ def cpu_block_combine_multi(n: int, C, blocks, Y: np.ndarray) -> None:
         args += [0, None, 0] if t is None else [t.shape[1], _ptr(t), ld(t, t.shape[1])]
     _check_host(host_lib().spmv_cpu_block_combine_multi(n, kc, _ptr(C), *args, _ptr(Y), ld(Y, kc)),
                 "spmv_cpu_block_combine_multi")
+
+
+KRYLOV_MAX_COLS = 32  # SPMV_KRYLOV_MAX_COLS (spmv_ext.h): the widest GMRES basis
+_COLUMN_NAMES = ("the vectors", "the vectors", "a vector")
+
+
+def _krylov_operands(what: str, n: int, V, c, columns, coef=None):
+    """The checks of the three GMRES host statements: V a 2-D float64 block
+    (>= n rows, unit inner stride) of which c columns (default: all, 1..32) are
+    read; every vector in `columns` a 2-D float64 (>= n rows, 1) array, which
+    may be a column view of a block; coef (h or y) a contiguous float64 array
+    of >= c entries.  Returns (c, ld)."""
+    if V is not None:
+        c, ld = _host_blocks(what, [(V, n)], c, _BLOCK_NAMES)
+        if not 1 <= c <= KRYLOV_MAX_COLS:
+            raise SpmvError(OTHER_ERROR, what, f"the basis has 1..{KRYLOV_MAX_COLS} columns, not {c}")
+    _, ld = _host_blocks(what, [(t, n) for t in columns], 1, _COLUMN_NAMES)
+    if coef is not None:
+        _host_vectors(what, (coef, c))
+    return c, ld
+
+
+def cpu_krylov_project(n: int, V, h, w, w_out, c: int | None = None) -> None:
+    """Host statement of one Gram-Schmidt pass (spmv_cpu_krylov_project):
+    w_out[i] = the chain s = w[i]; s = fma(-h[j], V[i][j], s), j < c.  V: a 2-D
+    float64 block (>= n rows, unit inner stride), c defaults to its width
+    (1..32); h: >= c float64 scalars; w and w_out: (>= n rows, 1) float64 arrays,
+    possibly column views; w_out may be w.  Only w_out[:n] is written."""
+    what = "cpu_krylov_project"
+    c, ld = _krylov_operands(what, n, V, c, (w, w_out), h)
+    _check_host(host_lib().spmv_cpu_krylov_project(n, c, _ptr(V), ld(V, c), _ptr(h), _ptr(w), ld(w), _ptr(w_out),
+                                                   ld(w_out)), "spmv_cpu_krylov_project")
+
+
+def cpu_krylov_combine(n: int, V, y, t, c: int | None = None) -> None:
+    """Host statement of t = V y (spmv_cpu_krylov_combine): t[i] = the chain
+    s = 0; s = fma(V[i][j], y[j], s), j < c.  Operands as cpu_krylov_project;
+    t must not overlap the columns read.  Only t[:n] is written."""
+    what = "cpu_krylov_combine"
+    c, ld = _krylov_operands(what, n, V, c, (t,), y)
+    _check_host(host_lib().spmv_cpu_krylov_combine(n, c, _ptr(V), ld(V, c), _ptr(y), _ptr(t), ld(t)),
+                "spmv_cpu_krylov_combine")
+
+
+def cpu_krylov_normalize(n: int, s, w, v, copy=None) -> None:
+    """Host statement of v = w / sqrt(s[0]) (spmv_cpu_krylov_normalize), v = 0
+    when s[0] <= 0.  s: one float64 scalar in an array; w and v: (>= n rows, 1)
+    float64 arrays, possibly column views, v may be w; copy: None or a contiguous
+    float64 vector of >= n entries that receives the same values."""
+    what = "cpu_krylov_normalize"
+    _, ld = _krylov_operands(what, n, None, None, (w, v))
+    _host_vectors(what, (s, 1), *(() if copy is None else ((copy, n),)))
+    _check_host(host_lib().spmv_cpu_krylov_normalize(n, _ptr(s), _ptr(w), ld(w), _ptr(v), ld(v), _ptr(copy)),
+                "spmv_cpu_krylov_normalize")
 
 
 def csr_sort_rows(n_rows: int, ptr, col, val) -> None:
